@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: Cornell Box 4096x4096, 8xAA (4x2), 64 shadow rays (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one frame.  With N ranks the ONE frame is split into
@@ -10,13 +10,17 @@ each rank renders its bands with the HIP kernel into its own HBM, the bands are 
 RCCL and rank 0 de-interleaves them into the final ARGB frame — total work is fixed, so "scaling" is
 "strong".  `value` is nominal Mrays/s = W*H*AA*(1+S) / time, whole job, frame resident in HBM of rank 0.
 
-Prints ONE JSON line (rank 0) with
+Prints ONE JSON line (rank 0).  A plain run only warms up, times the K steps and reports the headline figure
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `kernel_ms_per_launch`).  `--dump-outputs DIR`
+writes the frame of the last timed step to DIR (dump_outputs).  `--full` adds everything else it measures and checks:
   `roofline`      hardware-side: the bounding unit of this path is the FP32 vector ALU's instruction issue (DESIGN.md 5);
                   frac = VALU wave-instructions the timed kernel EXECUTES per launch (rocprofv3 PMC pass of this command,
                   profiles/r02_pmc.json) x 2 issue cycles / (1024 SIMDs x 2.4 GHz x the kernel time measured live here)
   `roofline_hbm`  the HBM view the north star asks for (<< 1 % by construction)
   `algorithmic_speedup_vs_bruteforce`  the reference's brute-force flop / kernel time — NOT a hardware fraction
   `cpu_baseline`  the CPU oracle (and the reference's own kernel built for x86-64) timed on this host's cores
+  and the work counters, host enqueue time, frame checksum, brute-force / host-buffer / animated-light legs, the
+  reference's own kernel on this GPU and the oracle checks of the frame.
 """
 import argparse
 import json
@@ -36,6 +40,8 @@ VALU_ISSUE_CYCLES = 2             # a wave64 VALU instruction occupies its SIMD-
 PMC_FILE = "r03_pmc.json"         # profiles/: counters per launch from the rocprofv3 --pmc passes of this command
 FLOP_PER_TRI_TEST = 46            # Moeller-Trumbore with e1,e2 precomputed
 FLOP_PER_SPHERE_TEST = 30
+DUMP_PIXELS = 1 << 21             # --dump-outputs: a frame with more pixels is sampled (4 float32 each: 32 MiB)
+DUMP_SEED = 20261016
 
 WORKLOADS = {
     # BASELINE.json configs[3] / metric: the headline frame
@@ -65,6 +71,21 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(out_dir, frame):
+    """`frame_argb.npy`: the ARGB8888 words the caller's buffer holds after the step, as float32 channel values
+    [pixels, 4] = (A, R, G, B), pixels in row order.  A frame of more than DUMP_PIXELS pixels is represented by the same
+    DUMP_PIXELS pixels on every run (seeded sample, kept in row order)."""
+    import torch
+    flat = frame.reshape(-1)
+    if flat.numel() > DUMP_PIXELS:
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), size=DUMP_PIXELS, replace=False))
+        flat = flat[torch.from_numpy(pix).to(flat.device)]
+    words = flat.cpu().numpy().view(np.uint32)
+    argb = np.stack([(words >> sh) & 0xFF for sh in (24, 16, 8, 0)], axis=1).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_argb.npy"), argb)
+
+
 def build_scene(workload, rt):
     """Cornell Box (LoadTestModel), plus what the named configuration adds to it."""
     scene = rt.Scene.cornell_box()
@@ -85,6 +106,12 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20,
                     help="untimed frames first (the device needs ~15 frames / 50 ms of load to reach its clocks, profiles/r02_wave_timeline.txt)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last one rendered to DIR/frame_argb.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure: work counters, roofline, host enqueue time, "
+                         "frame checksum, the brute-force / host-buffer / animated-light / CPU-baseline / reference legs, "
+                         "the oracle checks.  --no-cpu-baseline, --no-brute-force and --timed-only trim it")
     ap.add_argument("--workload", default="headline", choices=list(WORKLOADS))
     ap.add_argument("--band-rows", type=int, default=16,
                     help="rows per band of the interleaved partition (N > 1).  16: the shares of the ranks of 8 cost the same within 1 %% "
@@ -93,9 +120,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-brute-force", action="store_true", help="skip the cull-off comparison leg (N=1 only)")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only the warm-up and the timed steps (no work counters, no comparison / host-buffer / animated / "
-                         "CPU legs): what the rocprofv3 passes of tools/pmc_passes.sh run, so that every dispatch of the "
-                         "kernel in the profile is the timed workload")
+                    help="with --full: only the warm-up and the timed steps (no work counters, no comparison / host-buffer / "
+                         "animated / CPU legs): what the rocprofv3 passes of tools/pmc_passes.sh run, so that every dispatch "
+                         "of the kernel in the profile is the timed workload")
     ap.add_argument("--force-collective", action="store_true",
                     help="with one rank, still initialise the process group and run the band gather (exercises the "
                          "RCCL calls of the N>1 flow on a one-GPU box)")
@@ -108,6 +135,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the N>1 flow on a box with fewer GPUs than ranks (bands travel via host memory)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -134,6 +163,17 @@ def main():
     collective = world > 1 or args.force_collective
     part_world, part_rank = (emu[1], emu[0]) if emu else (world, rank)     # the band partition this process renders a part of
     saved_stdout = None
+
+    def emit(out):
+        sys.stdout.flush()
+        if saved_stdout is not None:
+            os.dup2(saved_stdout, 1)
+            os.close(saved_stdout)
+        print(json.dumps(out), flush=True)
+        if collective:
+            os.dup2(2, 1)           # (anything the teardown prints goes to stderr as well)
+            dist.destroy_process_group()
+
     if collective:
         # RCCL prints a version banner on stdout when its first communicator is made: keep stdout for the ONE JSON line
         sys.stdout.flush()
@@ -235,7 +275,7 @@ def main():
 
     # exact algorithmic work of this rank's bands (un-timed instrumented passes): `work` follows the
     # reference's loops literally (rt_count_work); `executed` is what the wave kernel really runs
-    if args.timed_only:
+    if args.timed_only or not args.full:
         args.no_cpu_baseline = args.no_brute_force = True
         work = {k: 0 for k, _ in abi.RtWork._fields_}
         executed = {}
@@ -258,6 +298,14 @@ def main():
         for _ in range(130 * part_world):
             step()
         sync()
+    elif not args.full:
+        # One GPU: --full's work-counting passes put ~0.3 s of load on the device before the warm-up; a plain run puts
+        # as much in un-timed steps, so that a short --warmup starts from the same clocks.
+        t_load = time.perf_counter()
+        while time.perf_counter() - t_load < 0.3:
+            for _ in range(4):
+                step()
+            sync()
     for _ in range(args.warmup):
         step()
     sync()
@@ -267,14 +315,17 @@ def main():
         step(ev[k])
     sync()
     elapsed = time.perf_counter() - t0
-    # the host's share of a step: a short burst enqueued into an EMPTY queue and not waited for (in the timed loop the
-    # host runs ahead until the queue is full and then waits for the GPU, which says nothing about its own cost)
-    burst = min(16, args.steps)
-    t1 = time.perf_counter()
-    for _ in range(burst):
-        step()
-    host_enqueue_s = (time.perf_counter() - t1) / burst * args.steps
-    sync()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame if collective else stripe)
+    if args.full:
+        # the host's share of a step: a short burst enqueued into an EMPTY queue and not waited for (in the timed loop the
+        # host runs ahead until the queue is full and then waits for the GPU, which says nothing about its own cost)
+        burst = min(16, args.steps)
+        t1 = time.perf_counter()
+        for _ in range(burst):
+            step()
+        host_enqueue_s = (time.perf_counter() - t1) / burst * args.steps
+        sync()
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
     keys, xkeys = list(work), list(executed)
@@ -290,7 +341,7 @@ def main():
     total_exec = {k: int(round(v)) for k, v in zip(xkeys, stats[2 + len(keys):])}
 
     # frame integrity: rank 0 sums the final frame (N=1: the stripe is the frame)
-    if rank == 0:
+    if rank == 0 and args.full:
         final = frame if collective else stripe
         frame_sum = int(final.to(torch.int64).bitwise_and(0xFFFFFFFF).sum().item())
 
@@ -301,8 +352,30 @@ def main():
 
     aa = cfg.aa_x * cfg.aa_y
     nominal_rays = W * H * aa * (1 + cfg.shadow_samples)
-    traced_rays = total_work["primary_rays"] + total_work["bounce_rays"] + total_work["shadow_rays"]
     ms_per_step = elapsed * 1e3 / args.steps
+    out = {
+        "metric": "Mrays/sec (nominal = W*H*AA*(1+S)/t), " + (
+            "Cornell Box 4096^2, 8xAA, 64 shadow rays" if args.workload == "headline" else
+            "workload %s: %dx%d, %dxAA, %d shadow rays, %d triangles (not the headline frame)" % (args.workload, W, H, aa, cfg.shadow_samples, len(scene))),
+        "value": nominal_rays / (ms_per_step * 1e-3) / 1e6,
+        "unit": "Mrays/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": "%s: Cornell Box %dx%d, %dx%d AA, %d shadow rays, %d spheres, <=%d bounces, %d triangles" % (
+            args.workload, W, H, cfg.aa_x, cfg.aa_y, cfg.shadow_samples, cfg.num_spheres, cfg.max_bounces, len(scene)),
+            "parallelism": "row bands of %d over %d GPU(s) + RCCL gather" % (band_rows, part_world) if collective else "1 GPU"},
+        "kernel_ms_per_launch": kernel_ms,
+    }
+    if not args.full:
+        emit(out)
+        return
+
+    traced_rays = total_work["primary_rays"] + total_work["bounce_rays"] + total_work["shadow_rays"]
     flops = (total_work["closest_tri_tests"] + total_work["shadow_tri_tests"]) * FLOP_PER_TRI_TEST + \
             (total_work["closest_sphere_tests"] + total_work["shadow_sphere_tests"]) * FLOP_PER_SPHERE_TEST
     # per launch = per rank: every rank runs the same kernel on 1/world of the frame
@@ -377,24 +450,8 @@ def main():
             "note": "work the shipped kernel really executes (rt_count_executed): the 64-sample test runs only for "
                     "(surface point, triangle) pairs the interval bounds leave undecided"}
 
-    out = {
-        "metric": "Mrays/sec (nominal = W*H*AA*(1+S)/t), " + (
-            "Cornell Box 4096^2, 8xAA, 64 shadow rays" if args.workload == "headline" else
-            "workload %s: %dx%d, %dxAA, %d shadow rays, %d triangles (not the headline frame)" % (args.workload, W, H, aa, cfg.shadow_samples, len(scene))),
-        "value": nominal_rays / (ms_per_step * 1e-3) / 1e6,
-        "unit": "Mrays/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": "%s: Cornell Box %dx%d, %dx%d AA, %d shadow rays, %d spheres, <=%d bounces, %d triangles" % (
-            args.workload, W, H, cfg.aa_x, cfg.aa_y, cfg.shadow_samples, cfg.num_spheres, cfg.max_bounces, len(scene)),
-            "parallelism": "row bands of %d over %d GPU(s) + RCCL gather" % (band_rows, part_world) if collective else "1 GPU"},
+    out.update({
         "host_enqueue_ms_per_step": host_enqueue_s * 1e3 / args.steps,
-        "kernel_ms_per_launch": kernel_ms,
         "traced_mrays_per_s": None if args.timed_only else traced_rays / (ms_per_step * 1e-3) / 1e6,
         "nominal_rays_per_frame": nominal_rays, "traced_rays_per_frame": None if args.timed_only else traced_rays,
         "work_per_frame": total_work,
@@ -412,7 +469,7 @@ def main():
                          "note": "algorithmic bytes = 4 B/pixel ARGB + 80 B/triangle once; <<1% by construction; "
                                  "traffic = HBM bytes per launch (2 x FETCH_SIZE + WRITE_SIZE, gfx950 correction) from the PMC "
                                  "passes in profiles/" + PMC_FILE},
-    }
+    })
 
     if emu:
         out["emulated_rank"] = {
@@ -612,14 +669,7 @@ def main():
         got = (stripe if world == 1 else frame).view(-1)[torch.from_numpy(pix.astype(np.int64)).to(dev)].cpu().numpy().view(np.uint32)
         out["cpu_baseline"]["gpu_frame_matches_oracle_on_sample"] = bool(np.array_equal(got, o_argb))
 
-    sys.stdout.flush()
-    if saved_stdout is not None:
-        os.dup2(saved_stdout, 1)
-        os.close(saved_stdout)
-    print(json.dumps(out), flush=True)
-    if collective:
-        os.dup2(2, 1)           # (anything the teardown prints goes to stderr as well)
-        dist.destroy_process_group()
+    emit(out)
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@ Runs only in the build container (needs /root/reference and the libraries oracle
 it): the reference kernel Source/kernels.cl, compiled for x86-64 where it lies, renders the frames; the
 reference's own LoadTestModel / load_obj produce the scene vectors.  What is stored is data — inputs and
 expected outputs — never reference source.  Re-run:  python tests/golden/make_golden.py
+(`--vs-ref`: only oracle_vs_ref.json, the hashes tests/test_oracle_vs_ref.py checks the oracle against)
 """
 import json
 import os
@@ -131,5 +132,30 @@ def main():
     print("golden vectors written to", HERE)
 
 
+def vs_ref():
+    """oracle_vs_ref.json: hashes of the reference kernel's frames for the cases of tests/test_oracle_vs_ref.py."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_vs_ref as T
+    aos = np.load(os.path.join(HERE, "scene_cornell_aos.npy"))
+    out = {"views": T.VIEWS, "cases": {}}
+    for name, kw in sorted(T.CASES.items()):
+        k = R.RefKernel(name)
+        frames = []
+        for scene_aos in T.scenes(aos):
+            v, n, c = R.pack_scene(scene_aos)
+            row = []
+            for yaw, pitch, cam, light in T.VIEWS:
+                argb, tap = k.render(v, n, c, R.rot_matrix(yaw, pitch), cam, light, focal_for(kw))
+                row.append({"argb": T.digest(argb), "tap": T.digest(tap)})
+            frames.append(row)
+        out["cases"][name] = {"config": kw, "frames": frames}
+    with open(os.path.join(HERE, "oracle_vs_ref.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    print("reference-kernel hashes written to", os.path.join(HERE, "oracle_vs_ref.json"))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--vs-ref"]:
+        vs_ref()
+    else:
+        main()

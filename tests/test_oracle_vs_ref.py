@@ -1,13 +1,19 @@
-"""CPU, container only (-m ref is implied by availability): the oracle restatement against the reference
-kernel itself (oracle/_ref, built from /root/reference by oracle/build_ref.py) on inputs beyond the
-committed fixtures — different views, lights and a modified scene."""
+"""CPU: the oracle restatement against the reference kernel itself on inputs beyond the committed frame fixtures —
+different views, lights and a modified scene.  The reference kernel (built from the reference's kernels.cl for x86-64
+by oracle/build_ref.py) rendered every case once: tests/golden/oracle_vs_ref.json holds the SHA-256 of its ARGB words
+and of its clamped 255*c taps per (case, scene, view), written by `python tests/golden/make_golden.py --vs-ref`.
+Equal hashes are equal bits: tolerance 0."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
 from oracle import pyref
 from uob_raytracer_amd import abi
 
-pytestmark = pytest.mark.skipif(not pyref.have_ref("default256"), reason="oracle/_ref not built (needs /root/reference)")
+G = os.path.join(os.path.dirname(__file__), "golden")
 
 VIEWS = [(0.0, 0.0, [0.0, 0.0, -3.2], [0.4, -0.5, -0.7]), (-0.5, 0.3, [-0.4, -0.2, -2.7], [0.0, 0.3, -0.2]),
          (1.2, 0.0, [1.5, 0.0, -1.5], [0.0, -0.9, 0.0])]
@@ -18,25 +24,45 @@ CASES = {"default256": dict(width=256, height=256),
          "cfg1": dict(width=256, height=256, aa_x=1, aa_y=1, shadow_samples=1, light_spread=0.0, spheres=())}
 
 
+def scenes(aos):
+    """The scene as loaded, and the same box with a mirror left wall and one glass face of the tall block."""
+    mod = aos.copy()
+    mod[[2, 3], 4, :] = (1.0, 1.0, 1.0, 0.0)      # left wall -> mirror
+    mod[[20, 21], 4, :] = (0.0, 0.0, 0.0, -1.0)   # one tall-block face -> glass
+    return [aos, mod]
+
+
+def digest(a):
+    """SHA-256 of an array's 32-bit words (ARGB words or float32 taps), with its shape."""
+    a = np.ascontiguousarray(a)
+    return {"shape": list(a.shape), "sha256": hashlib.sha256(a.view(np.uint32).tobytes()).hexdigest()}
+
+
+@pytest.fixture(scope="module")
+def golden():
+    with open(os.path.join(G, "oracle_vs_ref.json")) as f:
+        return json.load(f)
+
+
 @pytest.mark.parametrize("name", sorted(CASES))
-def test_oracle_equals_reference_kernel(name, scene, oracle):
+def test_oracle_equals_reference_kernel(name, scene, oracle, golden):
     kw = CASES[name]
     cfg = abi.make_config(**kw)
-    k = pyref.RefKernel(name)
-    aos = scene.aos.copy()
-    aos[[2, 3], 4, :] = (1.0, 1.0, 1.0, 0.0)      # left wall -> mirror
-    aos[[20, 21], 4, :] = (0.0, 0.0, 0.0, -1.0)   # one tall-block face -> glass
+    want = golden["cases"][name]
+    assert want["config"] == json.loads(json.dumps(kw)) and golden["views"] == json.loads(json.dumps(VIEWS))
     focal = 1100.0 * min(cfg.width, cfg.height) / 1024.0 * cfg.aa_x
-    for scene_aos in (scene.aos, aos):
+    for si, scene_aos in enumerate(scenes(scene.aos)):
         v, n, c = pyref.pack_scene(scene_aos)
-        for yaw, pitch, cam, light in VIEWS:
+        for vi, (yaw, pitch, cam, light) in enumerate(VIEWS):
             rot = pyref.rot_matrix(yaw, pitch)
-            a0, t0 = k.render(v, n, c, rot, cam, light, focal)
             a1, r1 = oracle.render(cfg, v, n, c, rot, cam, light, focal)
-            assert np.array_equal(a0, a1)
+            ref = want["frames"][si][vi]
+            assert digest(a1) == ref["argb"], "%s scene %d view %d: ARGB differs from the reference kernel" % (name, si, vi)
             _, tap = pyref.quantise(r1)
-            assert np.array_equal(tap.view(np.uint32), t0.view(np.uint32))
+            assert digest(tap) == ref["tap"], "%s scene %d view %d: taps differ from the reference kernel" % (name, si, vi)
 
 
 def test_product_scene_equals_reference_scene(scene):
-    assert np.array_equal(scene.aos.view(np.uint32), pyref.ref_load_test_model().view(np.uint32))
+    """scene_cornell_aos.npy is the reference's own LoadTestModel (tests/golden/make_golden.py)."""
+    want = np.load(os.path.join(G, "scene_cornell_aos.npy"))
+    assert np.array_equal(scene.aos.view(np.uint32), want.view(np.uint32))

@@ -6,7 +6,7 @@ import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 br = sys.argv[1] if len(sys.argv) > 1 else "8"
 def run(extra):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "300", "--warmup", "60", "--no-cpu-baseline"] + extra,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "300", "--warmup", "60", "--full", "--no-cpu-baseline"] + extra,
                        capture_output=True, text=True)
     return json.loads(p.stdout.strip().splitlines()[-1])
 one = run(["--timed-only"])

@@ -14,9 +14,9 @@ for w in headline cfg2 cfg3 cfg5 reference; do
   find $OUT/pmc_$w -name "*.db" -delete
 done
 cp profiles/r03_pmc.json profiles/r03_kernel_stats_*.csv $OUT/
-timeout -k 10 400 python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err; tail -c 300 $OUT/bench_n1.json; echo
-for w in cfg2 cfg3 cfg5 reference; do timeout -k 10 300 python bench.py --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err; done
-timeout -k 10 200 python bench.py --force-collective --no-cpu-baseline > $OUT/bench_rccl_gather_1rank.json 2> $OUT/bench_rccl.err
+timeout -k 10 400 python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err; tail -c 300 $OUT/bench_n1.json; echo
+for w in cfg2 cfg3 cfg5 reference; do timeout -k 10 300 python bench.py --full --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err; done
+timeout -k 10 200 python bench.py --full --force-collective --no-cpu-baseline > $OUT/bench_rccl_gather_1rank.json 2> $OUT/bench_rccl.err
 timeout -k 10 300 python tools/emulate_ranks.py 16 > $OUT/emulated_ranks.txt 2>&1; tail -4 $OUT/emulated_ranks.txt
 CONTEXTS="2 2" timeout -k 10 200 python tools/band_pipeline.py 8 4 2 1 > $OUT/band_time.txt 2>&1
 CONTEXTS="1 1" timeout -k 10 200 python tools/band_pipeline.py 8 4 2 1 >> $OUT/band_time.txt 2>&1

@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 passes over one bench workload (run on the GPU box from the repo root):
 #   bash tools/pmc_passes.sh <out-dir-under-gpurun_out> [--workload cfg5 ...]
-# Every pass profiles the SAME command: bench.py --timed-only --warmup 20 --steps 30 (only the warm-up and the timed
+# Every pass profiles the SAME command: bench.py --full --timed-only --warmup 20 --steps 30 (only the warm-up and the timed
 # steps run, so every dispatch in the profile belongs to the workload; tools/pmc_to_json.py drops the 20 warm-up steps).
 # Each --pmc set is its own run (8 SQ slots per pass; FETCH_SIZE and WRITE_SIZE cannot share one); the kernel trace is a
 # separate run again (gpurun refuses --pmc combined with the trace domains).
@@ -10,7 +10,7 @@ set -u
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1; shift
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 $GRAFT_REPO_ROOT/bench.py --steps 30 --warmup 20 --timed-only $*"
+BENCH="python3 bench.py --steps 30 --warmup 20 --full --timed-only $*"       # run from the repository root (cd below)
 cd $GRAFT_REPO_ROOT
 run() { name=$1; shift; rocprofv3 --pmc "$@" -d $OUT/pmc_$name --output-format csv -- $BENCH > $OUT/pmc_$name.log 2>&1 || echo "pass $name failed (see pmc_$name.log)"; }
 run insts   SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES

@@ -6,7 +6,7 @@ refuses to price counters of another build (roofline.stale).
 
     python tools/pmc_to_json.py gpurun_out/<dir> <workload> profiles/r03_pmc.json [--warmup W] [--steps K]
 
-W, K: warm-up and timed steps of the profiled `bench.py --timed-only` commands (defaults 20 / 30, as pmc_passes.sh runs).
+W, K: warm-up and timed steps of the profiled `bench.py --full --timed-only` commands (defaults 20 / 30, as pmc_passes.sh runs).
 """
 import collections
 import csv
@@ -91,7 +91,7 @@ def main():
             e["wave_cycle_shares"] = {k: c[k] / c["SQ_WAVE_CYCLES"] for k in ("SQ_ACTIVE_INST_ANY", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY") if k in c}
         return e
 
-    entry = {"source_sha256_16": source_hash(), "n_gpus": 1, "profiled_command": "bench.py --workload %s --timed-only --warmup %d --steps %d" % (workload, W, K),
+    entry = {"source_sha256_16": source_hash(), "n_gpus": 1, "profiled_command": "bench.py --workload %s --full --timed-only --warmup %d --steps %d" % (workload, W, K),
              "kernels": {}, "other_kernels": {}}
     step = collections.defaultdict(float)
     dominant, dom_ns = None, -1.0
