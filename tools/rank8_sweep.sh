@@ -10,5 +10,4 @@ run UOB_RT_GRID_PER_CU=5
 run UOB_RT_GRID_PER_CU=5 UOB_RT_JOB_TASKS=2
 run UOB_RT_HEAVY_FACTOR4=6
 run UOB_RT_HEAVY_FACTOR4=12
-run UOB_RT_SPLIT_LISTED=1
 run UOB_RT_PLAIN_ORDER=1

@@ -83,7 +83,6 @@ struct Tuning {
   bool no_specialise = false; // UOB_RT_NO_SPECIALISE: the generic wave-kernel instantiation also where a specialised one exists
   int grid_per_cu = 0;        // UOB_RT_GRID_PER_CU: workgroups per CU of the wave kernel's persistent grid (experiments)
   bool phase_profile = false; // UOB_RT_PHASE_PROFILE: rt_count_executed returns s_memtime shares per phase
-  int split_listed = 0;       // UOB_RT_SPLIT_LISTED=1: last frame's expensive jobs are handed out one task at a time
   bool timeline = false;      // UOB_RT_TIMELINE: the wave kernel records when its waves start and end (rt_debug_wave_timeline)
   int mask_debug = 0;         // UOB_RT_MASK_DEBUG: mesh kernel, switch single tile-mask stages off (fault isolation)
 };
@@ -183,7 +182,6 @@ static Tuning read_tuning(const rt_config& cfg) {
   if (const char* e = getenv("UOB_RT_GRID_PER_CU")) { const int v = atoi(e); if (v >= 1 && v <= 8) t.grid_per_cu = v; }
   t.phase_profile = getenv("UOB_RT_PHASE_PROFILE") != nullptr;
   t.timeline = getenv("UOB_RT_TIMELINE") != nullptr;
-  if (const char* e = getenv("UOB_RT_SPLIT_LISTED")) { const int v = atoi(e); if (v == 0 || v == 1) t.split_listed = v; }
   if (const char* e = getenv("UOB_RT_MASK_DEBUG")) t.mask_debug = atoi(e);
   return t;
 }
@@ -643,9 +641,6 @@ static void fill_params(const rt_ctx* c, const float rot[12], const float cam[3]
       jt *= 2;
     }
     P->job_tasks = jt;
-    // (measured on one rank's 512 rows of the headline frame, whose longest jobs last 0.5 of its 0.57 ms: 0.570 ms with,
-    // 0.566 without — the span is set by the work per wave and the ~60 us tail, not by the longest job; off unless asked for)
-    P->split_listed = c->tune.split_listed == 1 && jt > 1 && !big_chunks ? 1 : 0;
     P->no_specialise = c->tune.no_specialise ? 1 : 0;
     P->l1_inflate = c->tune.l1_inflate;
     P->job_hx = 0.5f * (float)(job_pixels * g.aa_x - 1);
@@ -1028,8 +1023,12 @@ int rt_count_executed(rt_ctx* c, const float rot[12], const float cam[3], const 
   fill_params(c, rot, cam, light, focal, &P);
   const bool generic = (c->cfg.flags & RT_FLAG_GENERIC_KERNEL) != 0;
   const bool mesh = !generic && !wave_kernel_supports(P) && !(c->cfg.flags & RT_FLAG_NO_CULL) && mesh_kernel_supports(P);
-  if (generic || (!wave_kernel_supports(P) && !mesh) || (!mesh && (P.S > 64 || P.aa_x * P.aa_y > 64))) {
+  if (generic || (!wave_kernel_supports(P) && !mesh) || (!mesh && P.S > 64)) {
     set_error("rt_count_executed: this configuration runs on the generic kernel, whose executed work is rt_count_work");
+    return RT_E_UNSUPPORTED;
+  }
+  if (!mesh && P.aa_x * P.aa_y > 64) {
+    set_error("rt_count_executed: more than 64 AA samples per pixel run on the wave kernel's chunked build, which has no counting build");
     return RT_E_UNSUPPORTED;
   }
   P.counters = c->d_counters;

@@ -21,22 +21,16 @@ namespace {
 template <bool COUNT>
 __device__ float direct_light(const LdsScene& S, const FrameParams& P, const Ray& ray, int global_id, Work& wk) {
   float total = 0.0f;
-  uint32_t r0 = xorshift((uint32_t)global_id);
-  uint32_t r1 = xorshift((uint32_t)((float)global_id * 91.0f));
-  uint32_t r2 = xorshift((uint32_t)((float)global_id * 19.0f));
-  const f3 light = mk(P.light[0], P.light[1], P.light[2]);
-  const f3 dir = light - ray.P;
-  const f3 start = ray.P + 0.0001f * dir;
-  const float radius_sq = dir.x * dir.x + dir.y * dir.y + dir.z * dir.z;
-  const float term = (16.0f * fmaxf(dot3(dir, ray.N), 0.0f)) / (4.0f * 3.14159274f * radius_sq);
+  uint32_t r0 = rng_seed(global_id, 0), r1 = rng_seed(global_id, 1), r2 = rng_seed(global_id, 2);
+  const LightSetup l = light_setup(mk(P.light[0], P.light[1], P.light[2]), ray);
   if (COUNT) wk.v[W_LIT]++;
   for (int i = 0; i < P.S; ++i) {
     r0 = xorshift(r0); r1 = xorshift(r1); r2 = xorshift(r2);
     const f3 jit = mk(crush1(r0, P.spread), crush1(r1, P.spread), crush1(r2, P.spread));
-    const bool sh = in_shadow<COUNT>(S, P, start, dir + jit, radius_sq, wk);
+    const bool sh = in_shadow<COUNT>(S, P, l.start, l.dir + jit, l.radius_sq, wk);
     if (COUNT) wk.v[W_SHADOW]++;
     // mask*(light_color*max(dot,0)) / (4 pi r^2): 1.0f*x == x exactly; a shadowed sample adds 0*x
-    total += sh ? 0.0f * term : term;
+    total += sh ? 0.0f * l.term : l.term;
   }
   return div_count(total, P.S, P.inv_S);
 }
@@ -91,8 +85,7 @@ __global__ __launch_bounds__(256) void rt_draw_generic(const FrameParams P) {
         }
       }
     }
-    const int aa = P.aa_x * P.aa_y;
-    const f3 c = mk(div_count(total.x, aa, P.inv_aa), div_count(total.y, aa, P.inv_aa), div_count(total.z, aa, P.inv_aa));
+    const f3 c = pixel_colour(total, P.aa_x * P.aa_y, P.inv_aa);
     const size_t o = (size_t)(P.out_global ? y : lr) * P.W + x;
     if (!COUNT) {
       P.out_argb[o] = pack_argb(c);

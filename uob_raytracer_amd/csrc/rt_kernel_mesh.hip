@@ -27,9 +27,7 @@ namespace uobrt {
 
 namespace {
 
-#ifndef RT_MESH_MIN_BLOCKS
-#define RT_MESH_MIN_BLOCKS 4
-#endif
+constexpr int kMeshMinBlocks = 4;          // workgroups per CU (launch bounds, persistent grid)
 constexpr int kTile = 64;                   // triangles per LDS tile
 constexpr int kBatch = 4;                   // candidate tiles staged per barrier round (4 records of each: 16 KB)
 constexpr int kSlot = 4 * kTile;            // float4 per staged tile
@@ -40,10 +38,7 @@ constexpr int kDirectSamples = 2;           // up to this many, level 2 is skipp
 // 226-triangle mesh, 10 samples: 0.70 ms with the limit at 8, 0.585 at 16; box + 4 680 triangles, 16 samples: 7.98 / 5.94;
 // 10 samples at 2048^2: 10.2 / 5.07; at 24 and 32 samples the two forms are level (0.73 / 0.72, 8.11 / 8.45), at 64 lane =
 // point is 1.7 x slower.
-#ifndef RT_MESH_POINT_SAMPLES
-#define RT_MESH_POINT_SAMPLES 16
-#endif
-constexpr int kPointSamples = RT_MESH_POINT_SAMPLES;
+constexpr int kPointSamples = 16;
 constexpr int kScreenCell = 32;             // pixels per side of a screen cell of the primary-ray tile masks
 constexpr int kScreenCellLog = 5;
 
@@ -170,6 +165,27 @@ __device__ __forceinline__ bool tile_clear_for_bundle(const float4* __restrict__
   return theta >= 8.95e-6f * (4.0f + 6.0f * ratio) * (bmax + emax) * eta;     // 150 * 2^-24 = 8.94e-6
 }
 
+// A closest hit carried across tiles: t, barycentrics, position in the reordered mesh (-1: none yet), original index
+struct TileHit { float t, u, v; int best, orig; };
+__device__ __forceinline__ TileHit no_hit() { return TileHit{RT_MAXFLOAT, 0.f, 0.f, -1, 0x7fffffff}; }
+// Does a hit at t on the triangle of original index `orig` replace h?  The reference visits the triangles in their ORIGINAL
+// order and replaces the hit only for a strictly smaller t (kernels.cl:120): of equal t the lowest original index stays —
+// whatever order the tiles come in.
+__device__ __forceinline__ bool closer(float t, int orig, const TileHit& h) {
+  return t < h.t || (t == h.t && h.best >= 0 && orig < h.orig);
+}
+// Cooperative block: the four waves hold the SAME rays and took a tile each — the closest hit over all of them, through
+// the workgroup's merge area (one TileHit per wave and lane)
+__device__ __forceinline__ void merge_hits(TileHit* area, int wave, int lane, TileHit& h) {
+  area[wave * 64 + lane] = h;
+  __syncthreads();
+  for (int w = 0; w < kMeshWaves; ++w) {
+    const TileHit o = area[w * 64 + lane];
+    if (o.best >= 0 && (h.best < 0 || closer(o.t, o.orig, h))) h = o;
+  }
+  __syncthreads();
+}
+
 // Geometry of a wave's 8x8 pixel block: its 64 pixels are numbered along a Z-order curve (x bits 0,2,4 / y bits
 // 1,3,5 of the number), task k covers the PT consecutive numbers from k*PT — for a power of two PT a compact
 // rectangle (4x2, 4x4, 8x4 ...), PTx >= PTy; for any other PT (AA grids such as 3x3: PT = 7) a compact run of the curve.
@@ -197,19 +213,11 @@ __device__ __forceinline__ void generate_streams(const FrameParams& P, const Mes
     const int qq = B.q(k, first_p + pp) < 64 ? B.q(k, first_p + pp) : 63;      // a pixel past the block is never lit
     const int px = B.x0 + zorder_x(qq);
     const int py = band_global_row(P, B.lr0 + zorder_y(qq));
-    const int gid = pixel_global_id(P, px, py);
-    const uint32_t seed = comp == 0 ? (uint32_t)gid : (uint32_t)((float)gid * (comp == 1 ? 91.0f : 19.0f));
-    uint32_t s = xorshift(seed);
-    uint32_t* dst = L.rng + pp * kRngStride + comp;
+    uint32_t s = rng_seed(pixel_global_id(P, px, py), comp);
     for (int it = 0; it < skip; ++it) s = xorshift(s);
-    if (seg > 0) s = rng_jump(s, seg);
-    const int it0 = seg * kRngSegLen;
-#pragma unroll 1
-    for (int j = 0; j < kRngSegLen; ++j) { s = xorshift(s); if (it0 + j < cnt) dst[(it0 + j) * 4] = s; }
+    rng_fill_segment(L.rng + pp * kRngStride + comp, s, seg, cnt);
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
 }
 
 }  // namespace
@@ -382,10 +390,7 @@ __global__ __launch_bounds__(64 * kMeshWaves) void rt_bin_shadow(const FramePara
   const int gi = t * kTile + lane;
   const size_t g = gi < n ? gi : t * kTile;
   const bool ok = gi < n && P.records[(size_t)5 * n + g].w != -1.0f;          // glass casts no shadow, :247
-  TriLane T1;
-  T1.v0 = xyz(P.records[g]); T1.e1 = xyz(P.records[(size_t)n + g]); T1.e2 = xyz(P.records[(size_t)2 * n + g]);
-  T1.c = xyz(P.records[(size_t)3 * n + g]);
-  T1.c1 = norm1(T1.c); T1.e1_1 = norm1(T1.e1); T1.e2_1 = norm1(T1.e2);
+  const TriLane T1 = tri_lane(P.records, P.records + n, P.records + (size_t)2 * n, P.records + (size_t)3 * n, (int)g);
   const f3 light = mk(P.light[0], P.light[1], P.light[2]);
   const float linf = P.light_inf;
   const float hbox = P.hbox;
@@ -465,27 +470,16 @@ __global__ __launch_bounds__(64 * kMeshWaves) void rt_bin_shadow(const FramePara
 
 // Grid: the workgroups the device holds at once (persistent, see the job loop); block = 4 waves = 2x2 blocks of 8x8 pixels.
 // COUNT: diagnostic build that also sums what the waves executed into P.counters[0..7] (rt_count_executed)
-// PROF: diagnostic build (never timed) that sums s_memtime cycles per phase over the waves instead
-#define MESH_STAMP(slot)                                                            \
-  if (PROF) {                                                                       \
-    unsigned long long now_;                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                              \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) :: "memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                              \
-    xw[slot] += now_ - tlast;                                                       \
-    tlast = now_;                                                                   \
-  }
-// AA_X, AA_Y, SS > 0: AA grid and sample count as compile-time constants (as rt_kernel_wave.hip); no such instantiation is
-// shipped (see launch_mesh).
-template <bool COUNT, bool PROF = false, int AA_X = 0, int AA_Y = 0, int SS = 0>
-__global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_mesh(const FrameParams P) {
+// PROF: diagnostic build (never timed) that sums s_memtime cycles per phase over the waves instead (RT_STAMP)
+template <bool COUNT, bool PROF = false>
+__global__ __launch_bounds__(64 * kMeshWaves, kMeshMinBlocks) void rt_draw_mesh(const FrameParams P) {
   unsigned long long xw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tlast = PROF ? __builtin_amdgcn_s_memtime() : 0ull;
   extern __shared__ float4 lds[];
   float4* tile = lds;                                   // kBatch staged tiles x 4 records x kTile triangles
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
-  const int wave_bytes = mesh_wave_lds_bytes((SS ? SS : P.S) > kPointSamples || P.nsph > 0);
+  const int wave_bytes = mesh_wave_lds_bytes(P.S > kPointSamples || P.nsph > 0);
   char* const wbase = reinterpret_cast<char*>(lds + kBatch * kSlot) + wave * wave_bytes;
   const MeshWaveLds L{reinterpret_cast<float4*>(wbase), reinterpret_cast<float4*>(wbase + 64 * 16),
                       reinterpret_cast<uint32_t*>(wbase + 64 * 32 + kMaxGroups * 64), reinterpret_cast<float4*>(wbase + 64 * 32)};
@@ -496,8 +490,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
                                                                     kMeshWaves * wave_bytes);
   unsigned long long* smask = pmask + nwords;
   // cooperative blocks (below): per lane, what each of the four waves found in its share of the tiles
-  struct CoopHit { float t, u, v; int best, orig; };
-  CoopHit* const coop_hit = reinterpret_cast<CoopHit*>(smask + nwords);                       // [kMeshWaves][64]
+  TileHit* const coop_hit = reinterpret_cast<TileHit*>(smask + nwords);                       // [kMeshWaves][64]
   unsigned long long* const coop_sh = reinterpret_cast<unsigned long long*>(coop_hit + kMeshWaves * 64);   // [kMeshWaves][64] blocked samples
   unsigned int* const coop_fl = reinterpret_cast<unsigned int*>(coop_sh + kMeshWaves * 64);  // [kMeshWaves][64] bit 0 blocked, bit 1 task_blocked
   const bool bins = PC(screen_masks) != nullptr;
@@ -548,11 +541,8 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
   __syncthreads();
   const LdsScene G = lds_scene(P.records, n);           // the whole mesh, in HBM (hit finalisation, bounce rays)
 
-  const int aa_x = AA_X ? AA_X : P.aa_x, aa_y = AA_Y ? AA_Y : P.aa_y;
-  const float sy = (AA_X && AA_Y) ? (float)AA_X / (float)(AA_Y ? AA_Y : 1) : P.sy;
+  const int aa_x = P.aa_x, aa_y = P.aa_y;
   const int aa = aa_x * aa_y;                           // <= 64 (mesh_kernel_supports()); lanes past PT * aa idle
-  const float inv_S = SS ? ((SS & (SS - 1)) == 0 ? 1.0f / (float)(SS ? SS : 1) : 0.0f) : P.inv_S;
-  const float inv_aa = (AA_X && AA_Y) ? (((AA_X * AA_Y) & (AA_X * AA_Y - 1)) == 0 ? 1.0f / (float)(AA_X * AA_Y ? AA_X * AA_Y : 1) : 0.0f) : P.inv_aa;
   const int PT = 64 / aa;                               // pixels per task
   const int ntask = (64 + PT - 1) / PT;                 // tasks per 8x8 block
   const int pt_magic = (65536 + PT - 1) / PT;           // q / PT == (q * pt_magic) >> 16 for q < 64
@@ -565,7 +555,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
   const int GL = GP * aa;
   const f3 light = mk(P.light[0], P.light[1], P.light[2]);
   const float hbox = P.hbox;
-  const int NS = SS ? SS : P.S;
+  const int NS = P.S;
   const int n_pass = (NS + 63) >> 6;                    // more than 64 shadow samples: passes of 64 sample lanes
   Work wk;
 
@@ -582,21 +572,43 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
     return t < ntiles ? t : -1;
   };
   auto load_batch = [&](int t0, int t1, int t2, int t3, int cnt, bool primary) {
-    const int rec = tid >> 6, i = tid & 63;
+    const int ltid = opaque(threadIdx.x);  // (the staging addresses are recomputed here instead of being kept live across the loops)
+    const int rec = ltid >> 6, i = ltid & 63;
     const int src = primary ? (rec == 0 ? 3 : rec == 1 ? 6 : rec == 2 ? 7 : 1) : rec;    // primary slot 3: e1 | original index
     __syncthreads();
     for (int sl = 0; sl < cnt; ++sl) {
       const int t = sl == 0 ? t0 : sl == 1 ? t1 : sl == 2 ? t2 : t3;
       const int gi = t * kTile + i;
-      tile[sl * kSlot + tid] = gi < n ? P.records[(size_t)src * n + gi] : make_float4(0.f, 0.f, 0.f, -1.0f);
+      tile[sl * kSlot + ltid] = gi < n ? P.records[(size_t)src * n + gi] : make_float4(0.f, 0.f, 0.f, -1.0f);
     }
     __syncthreads();
+  };
+  // The tiles named in `mask`, in rising order, kBatch per barrier round: before(cnt), the batch's load, loaded(cnt), then
+  // body(t, staged records) for every tile of the batch this wave works on — all of them, or in a cooperative block the
+  // one in slot `wave`
+  auto walk_tiles = [&](const unsigned long long* mask, bool primary, auto&& before, auto&& loaded, auto&& body) {
+    int bw = -1;
+    unsigned long long bm = 0ull;
+    for (;;) {
+      int t0 = -1, t1 = -1, t2 = -1, t3 = -1, cnt = 0;
+      if ((t0 = next_tile(mask, bw, bm)) >= 0) { cnt = 1;
+        if ((t1 = next_tile(mask, bw, bm)) >= 0) { cnt = 2;
+          if ((t2 = next_tile(mask, bw, bm)) >= 0) { cnt = 3;
+            if ((t3 = next_tile(mask, bw, bm)) >= 0) cnt = 4; } } }
+      if (cnt == 0) break;
+      before(cnt);
+      load_batch(t0, t1, t2, t3, cnt, primary);
+      loaded(cnt);
+      for (int sl = 0; sl < cnt; ++sl)
+        if (!coop || sl == wave) body(sl == 0 ? t0 : sl == 1 ? t1 : sl == 2 ? t2 : t3, tile + sl * kSlot);
+      if (cnt < kBatch) break;
+    }
   };
 
   f3 outc = mk(0.f, 0.f, 0.f);
   for (int k = 0; k < ntask; ++k) {
     // ---- phase 1: primary rays over all tiles -------------------------------------------------------
-    const int p = (AA_X && AA_Y) ? lane / (AA_X * AA_Y ? AA_X * AA_Y : 1) : (lane * P.aa_magic) >> 16;    // pixel of this lane within the task (lane / aa)
+    const int p = (lane * P.aa_magic) >> 16;    // pixel of this lane within the task (lane / aa)
     const int a = lane - p * aa;                // AA sample index dy*rx+dx, kernels.cl:395
     const bool in_task = p < PT && B.q(k, p) < 64;
     const int qz = in_task ? B.q(k, p) : B.q(k, 0);
@@ -604,8 +616,8 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
     const int lr = B.lr0 + zorder_y(qz);
     const bool valid = in_task && lr < P.owned_rows && x < P.W;
     const int y = band_global_row_cold(P, lr < P.owned_rows ? lr : 0);
-    const int ay = AA_X ? a / (AA_X ? AA_X : 1) : (a * P.aax_magic) >> 16;        // a / aa_x (a < 256)
-    Ray ray = primary_ray(P, x, y, a - ay * aa_x, ay, aa_x, aa_y, sy);
+    const int ay = (a * P.aax_magic) >> 16;        // a / aa_x (a < 256)
+    Ray ray = primary_ray(P, x, y, a - ay * aa_x, ay);
     f3 duc, eu;
     float dumax;
     {
@@ -615,8 +627,8 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
       const float xmin = wave_min_pos((float)x), xmax = wave_max_pos((float)x), ymin = wave_min_pos((float)yl), ymax = wave_max_pos((float)yl);
       const float Xlo = xmin * (float)aa_x - P.half_wx;
       const float Xhi = (xmax * (float)aa_x + (float)(aa_x - 1)) - P.half_wx;
-      const float Ylo = (ymin * (float)aa_y - P.half_hy) * sy;
-      const float Yhi = ((ymax * (float)aa_y + (float)(aa_y - 1)) - P.half_hy) * sy;
+      const float Ylo = (ymin * (float)aa_y - P.half_hy) * P.sy;
+      const float Yhi = ((ymax * (float)aa_y + (float)(aa_y - 1)) - P.half_hy) * P.sy;
       const float hx = 0.5f * (Xhi - Xlo), hy = 0.5f * (Yhi - Ylo);
       const f3 wc = mk(Xlo + hx, Ylo + hy, P.focal);
       const f3 r0 = mk(P.rot[0], P.rot[1], P.rot[2]), r1 = mk(P.rot[4], P.rot[5], P.rot[6]),
@@ -630,9 +642,8 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
     const bool sph_task = P.nsph > 0 && (!(dumax < 1e30f) ||
                           ballot(sphere_bundle_maybe(P, lane, mk(P.cam[0], P.cam[1], P.cam[2]), 0.0f, duc, bsqrt(dot3(duc, duc)),
                                                      1.0001f * bsqrt(dot3(eu, eu)), false)) != 0ull);
-    MESH_STAMP(0)
-    float current_t = RT_MAXFLOAT, bu = 0.f, bv = 0.f;
-    int best = -1, best_o = 0x7fffffff;          // best: position in the reordered mesh; best_o: its original index
+    RT_STAMP(xw, 0)
+    TileHit h = no_hit();
     const f3 ndp = -ray.dir;
     auto primary_tile = [&](int t, const float4* tb) {
       const float4 *t_c = tb, *t_pc = tb + kTile, *t_qc = tb + 2 * kTile, *t_or = tb + 3 * kTile;
@@ -654,54 +665,18 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
           const float tt = c4.w * detA_recip;
           const float u = detc(ndp, pc) * detA_recip;
           const float v = detc(ndp, qc) * detA_recip;
-          // the reference visits the triangles in their ORIGINAL order and replaces the hit only for a strictly smaller
-          // t (kernels.cl:120): of equal t the lowest original index stays — whatever order the tiles come in
           const int oi = __float_as_int(t_or[i].w);
-          if (u >= 0 && v >= 0 && (u + v) <= 1 && tt >= 0 && (tt < current_t || (tt == current_t && best >= 0 && oi < best_o))) {
-            best = t * kTile + i; best_o = oi; bu = u; bv = v; current_t = tt;
-          }
+          if (u >= 0 && v >= 0 && (u + v) <= 1 && tt >= 0 && closer(tt, oi, h)) h = TileHit{tt, u, v, t * kTile + i, oi};
         }
       }
     };
-    {
-      int bw = -1;
-      unsigned long long bm = 0ull;
-      for (;;) {
-        int t0 = -1, t1 = -1, t2 = -1, t3 = -1, cnt = 0;
-        if ((t0 = next_tile(pmask, bw, bm)) >= 0) { cnt = 1;
-          if ((t1 = next_tile(pmask, bw, bm)) >= 0) { cnt = 2;
-            if ((t2 = next_tile(pmask, bw, bm)) >= 0) { cnt = 3;
-              if ((t3 = next_tile(pmask, bw, bm)) >= 0) cnt = 4; } } }
-        if (cnt == 0) break;
-        MESH_STAMP(2)
-        load_batch(t0, t1, t2, t3, cnt, true);
-        MESH_STAMP(1)
-        for (int sl = 0; sl < cnt; ++sl)
-          if (!coop || sl == wave) primary_tile(sl == 0 ? t0 : sl == 1 ? t1 : sl == 2 ? t2 : t3, tile + sl * kSlot);
-        if (cnt < kBatch) break;
-      }
-    }
-    if (coop) {                                         // closest hit over all four waves' tiles: smallest (t, original index)
-      coop_hit[wave * 64 + lane] = CoopHit{current_t, bu, bv, best, best_o};
-      __syncthreads();
-      for (int w = 0; w < kMeshWaves; ++w) {
-        const CoopHit h = coop_hit[w * 64 + lane];
-        if (h.best >= 0 && (best < 0 || h.t < current_t || (h.t == current_t && h.orig < best_o))) {
-          current_t = h.t; bu = h.u; bv = h.v; best = h.best; best_o = h.orig;
-        }
-      }
-      __syncthreads();
-    }
-    MESH_STAMP(2)
+    walk_tiles(pmask, true, [&](int) { RT_STAMP(xw, 2) }, [&](int) { RT_STAMP(xw, 1) }, primary_tile);
+    if (coop) merge_hits(coop_hit, wave, lane, h);
+    RT_STAMP(xw, 2)
     bool lit = false, secondary = false;
     if (valid) {
-      if (best >= 0) {
-        ray.tri = best;
-        ray.P = (xyz(G.v0[best]) + bu * xyz(G.e1[best])) + bv * xyz(G.e2[best]);
-        ray.N = xyz(G.nrm[best]);
-        ray.col = G.col[best];
-      }
-      if (sph_task) closest_spheres<false>(P, ray, current_t, wk);
+      if (h.best >= 0) set_hit(G, ray, h.best, h.u, h.v);
+      if (sph_task) closest_spheres<false>(P, ray, h.t, wk);
       if (ray.tri != -1) {
         if (ray.col.w <= 0.0f) secondary = true;
         else lit = true;
@@ -718,46 +693,19 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
         if (__syncthreads_or(act ? 1 : 0) == 0) break;                // workgroup-uniform
         if (act) ray = (ray.col.w == 0.0f) ? reflect_ray(ray) : refract_ray(ray);
         const unsigned long long actm = ballot(act);
-        int mode = 2;                                                 // 0: nothing to test, 1: bound per tile, 2: every triangle
-        f3 s0 = mk(0.f, 0.f, 0.f), D0 = s0;
-        float es = 0.f, ed = 0.f, dl = 0.f;
-        if (actm != 0ull) {
-          const f3 o = ray.start, d = ray.dir;
-          const float mag = fmaxf(norm_inf(o), norm_inf(d));
-          const bool fin = act && mag < 1e30f;                         // false for NaN as well
-          const bool isnan_ = act && !(mag == mag);                    // a NaN ray hits nothing whatever the set
-          const unsigned long long finm = ballot(fin);
-          const bool odd = ballot(act && !fin && !isnan_) != 0ull;     // infinite coordinates: no bound
-          if (finm != 0ull && !odd) {
-            const float big = 3.0e38f;
-            const f3 olo = mk(wave_min(fin ? o.x : big), wave_min(fin ? o.y : big), wave_min(fin ? o.z : big));
-            const f3 ohi = mk(wave_max(fin ? o.x : -big), wave_max(fin ? o.y : -big), wave_max(fin ? o.z : -big));
-            const f3 dlo = mk(wave_min(fin ? d.x : big), wave_min(fin ? d.y : big), wave_min(fin ? d.z : big));
-            const f3 dhi = mk(wave_max(fin ? d.x : -big), wave_max(fin ? d.y : -big), wave_max(fin ? d.z : -big));
-            s0 = 0.5f * (olo + ohi); D0 = 0.5f * (dlo + dhi);
-            es = 0.5001f * fmaxf(fmaxf(ohi.x - olo.x, ohi.y - olo.y), ohi.z - olo.z) + 1e-6f * norm1(s0);
-            ed = 0.5001f * fmaxf(fmaxf(dhi.x - dlo.x, dhi.y - dlo.y), dhi.z - dlo.z) + 1e-6f * norm1(D0);
-            const float dmx = fmaxf(fmaxf(fmaxf(fabsf(dlo.x), fabsf(dhi.x)), fmaxf(fabsf(dlo.y), fabsf(dhi.y))), fmaxf(fabsf(dlo.z), fabsf(dhi.z)));
-            dl = 1.7321f * dmx * 1.0001f;                               // >= |d|_2 of every ray
-            mode = 1;
-          } else if (finm == 0ull && !odd) {
-            mode = 0;                                                   // only NaN rays
-          }
-        }
-        float cur = RT_MAXFLOAT, hu = 0.f, hv = 0.f;
-        int hit = -1, hit_o = 0x7fffffff;
+        // mode 0: nothing to test, 1: bound per tile, 2: every triangle (a wave without rays stays at 2 and tests nothing)
+        BounceBundle bnd{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f), 0.f, 0.f, 0.f, 2, false};
+        if (actm != 0ull) bnd = bounce_bundle(act, ray.start, ray.dir);
+        const int mode = bnd.mode;
+        TileHit hb = no_hit();
         const f3 ndb = -ray.dir;
         auto bounce_tile = [&](int t, const float4* tb) {
           const float4 *t_v0 = tb, *t_e1 = tb + kTile, *t_e2 = tb + 2 * kTile, *t_c = tb + 3 * kTile;
           if (actm == 0ull || mode == 0) return;                      // wave-uniform; the barriers are behind us
           const int nc = (n - t * kTile) < kTile ? (n - t * kTile) : kTile;
           unsigned long long Kb = nc == 64 ? ~0ull : ((1ull << nc) - 1ull);
-          if (mode == 1) {
-            TriLane Tb;
-            Tb.v0 = xyz(t_v0[lane]); Tb.e1 = xyz(t_e1[lane]); Tb.e2 = xyz(t_e2[lane]); Tb.c = xyz(t_c[lane]);
-            Tb.c1 = norm1(Tb.c); Tb.e1_1 = norm1(Tb.e1); Tb.e2_1 = norm1(Tb.e2);
-            Kb &= ~ballot(task_bound(Tb, s0, D0, es, ed, 2e-6f * dl, 0.0f, dl).clear);
-          }
+          if (mode == 1)
+            Kb &= ~ballot(task_bound(tri_lane(t_v0, t_e1, t_e2, t_c, lane), bnd.s0, bnd.D0, bnd.es, bnd.ed, 2e-6f * bnd.dl, 0.0f, bnd.dl).clear);
           if (act)
             for (unsigned long long m = uniform64(Kb); m != 0ull; m &= m - 1ull) {
               const int i = __builtin_ctzll(m);
@@ -769,9 +717,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
               const float u = detc(ndb, cof(bb, e2)) * detA_recip;
               const float v = detc(ndb, cof(e1, bb)) * detA_recip;
               const int oi = __float_as_int(e14.w);
-              if (u >= 0 && v >= 0 && (u + v) <= 1 && tt >= 0 && (tt < cur || (tt == cur && hit >= 0 && oi < hit_o))) {
-                hit = t * kTile + i; hit_o = oi; hu = u; hv = v; cur = tt;
-              }
+              if (u >= 0 && v >= 0 && (u + v) <= 1 && tt >= 0 && closer(tt, oi, hb)) hb = TileHit{tt, u, v, t * kTile + i, oi};
             }
         };
         // Which tiles?  lane = tile, 64 tiles per pass (tile_clear_for_bundle), the four waves' answers OR-ed into the
@@ -786,55 +732,26 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
           for (int base = 0; base < ntiles; base += 64) {
             const int t = base + lane;
             bool visit = t < ntiles;
-            if (pretest && visit) visit = !tile_clear_for_bundle(PC(tile_box) + (size_t)3 * t, s0, D0, es, ed, d2);
+            if (pretest && visit) visit = !tile_clear_for_bundle(PC(tile_box) + (size_t)3 * t, bnd.s0, bnd.D0, bnd.es, bnd.ed, d2);
             const unsigned long long vm = ballot(visit);
             if (lane == 0 && vm != 0ull) atomicOr(&smask[base >> 6], vm);
           }
         }
         __syncthreads();
-        {
-          int bw = -1;
-          unsigned long long bm = 0ull;
-          for (;;) {
-            int t0 = -1, t1 = -1, t2 = -1, t3 = -1, cnt = 0;
-            if ((t0 = next_tile(smask, bw, bm)) >= 0) { cnt = 1;
-              if ((t1 = next_tile(smask, bw, bm)) >= 0) { cnt = 2;
-                if ((t2 = next_tile(smask, bw, bm)) >= 0) { cnt = 3;
-                  if ((t3 = next_tile(smask, bw, bm)) >= 0) cnt = 4; } } }
-            if (cnt == 0) break;
-            load_batch(t0, t1, t2, t3, cnt, false);
-            if (COUNT && actm != 0ull) xw[0] += cnt;                     // (diagnostic: bounce-round tile visits count as primary visits)
-            for (int sl = 0; sl < cnt; ++sl)
-              if (!coop || sl == wave) bounce_tile(sl == 0 ? t0 : sl == 1 ? t1 : sl == 2 ? t2 : t3, tile + sl * kSlot);
-            if (cnt < kBatch) break;
-          }
-        }
-        if (coop) {      // cooperative block: the four waves hold the SAME rays and took a tile each — closest hit = smallest (t, original index)
-          coop_hit[wave * 64 + lane] = CoopHit{cur, hu, hv, hit, hit_o};
-          __syncthreads();
-          for (int w = 0; w < kMeshWaves; ++w) {
-            const CoopHit h = coop_hit[w * 64 + lane];
-            if (h.best >= 0 && (hit < 0 || h.t < cur || (h.t == cur && h.orig < hit_o))) { cur = h.t; hu = h.u; hv = h.v; hit = h.best; hit_o = h.orig; }
-          }
-          __syncthreads();
-        }
+        // (diagnostic: bounce-round tile visits count as primary visits)
+        walk_tiles(smask, false, [](int) {}, [&](int cnt) { if (COUNT && actm != 0ull) xw[0] += cnt; }, bounce_tile);
+        if (coop) merge_hits(coop_hit, wave, lane, hb);
         if (act) {
-          if (hit >= 0) {
-            ray.tri = hit;
-            ray.P = (xyz(G.v0[hit]) + hu * xyz(G.e1[hit])) + hv * xyz(G.e2[hit]);
-            ray.N = xyz(G.nrm[hit]);
-            ray.col = G.col[hit];
-          }
-          closest_spheres<false>(P, ray, cur, wk);
+          if (hb.best >= 0) set_hit(G, ray, hb.best, hb.u, hb.v);
+          closest_spheres<false>(P, ray, hb.t, wk);
           if (ray.tri != -1 && ray.col.w > 0.0f) { lit = true; bouncing = false; }
         }
       }
     }
     // per-lane light set-up of direct_light, kernels.cl:323-326
-    const f3 dir = light - ray.P;
-    const f3 start = ray.P + 0.0001f * dir;
-    const float radius_sq = dir.x * dir.x + dir.y * dir.y + dir.z * dir.z;
-    const float term = (16.0f * fmaxf(dot3(dir, ray.N), 0.0f)) / (4.0f * 3.14159274f * radius_sq);
+    const LightSetup ls = light_setup(light, ray);
+    const f3 dir = ls.dir, start = ls.start;
+    const float radius_sq = ls.radius_sq, term = ls.term;
     __builtin_amdgcn_wave_barrier();
     L.h0[lane] = make_float4(start.x, start.y, start.z, radius_sq);
     L.h1[lane] = make_float4(dir.x, dir.y, dir.z, 0.f);
@@ -845,12 +762,9 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
     const bool slit = lit && !(term == 0.0f);
     // ---- phase 3: shadows over all tiles ---------------------------------------------------------------
     const unsigned long long litmask = ballot(slit);
-    const float dlen = bsqrt(radius_sq);
-    const float hh = 1.002f * hbox + 2e-6f * (dlen + hbox);
-    float dminlen = dlen - 1.7321f * hh;
-    const bool sane = slit && (radius_sq > 1e-18f) && (radius_sq < 1e30f);
-    if (!sane || !(dminlen > 0.0f)) dminlen = 0.0f;
-    const float dk = dlen * 1.000004f;
+    const CullConsts cc = cull_consts(radius_sq, hbox, slit);
+    const float dlen = cc.dlen, hh = cc.hh;
+    const bool sane = cc.sane;
     // Level 1 bounds a SET of surface points, and is only as tight as the set is compact.  A task whose pixels
     // straddle a silhouette holds points on surfaces far apart, so the lit points are split into groups by
     // world cell (the last group takes whatever is left) and each group is bounded on its own.
@@ -890,9 +804,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
                                                __int_as_float(one_cell ? cj : -1), 0.f);
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
     }
     SphereBound sb;
     sb.maybe = false; sb.all_blocked = false;
@@ -902,7 +814,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
     uint32_t rs0 = 0u, rs1 = 0u, rs2 = 0u;
     if (NS <= kPointSamples) {
       const int gid = pixel_global_id(P, x, y);
-      rs0 = xorshift((uint32_t)gid); rs1 = xorshift((uint32_t)((float)gid * 91.0f)); rs2 = xorshift((uint32_t)((float)gid * 19.0f));
+      rs0 = rng_seed(gid, 0); rs1 = rng_seed(gid, 1); rs2 = rng_seed(gid, 2);
     }
     unsigned long long my_sh = 0ull;            // blocked samples of THIS lane's surface point (current pass), across tiles
     unsigned long long active = 0ull;           // sample lanes of the current pass
@@ -931,7 +843,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
       }
     }
     __syncthreads();
-    MESH_STAMP(3)
+    RT_STAMP(xw, 3)
     // the world-cell masks of this wave's groups, one 64-tile word at a time (lane g = group g): the tiles come in rising
     // order, so a word is loaded once per 64 tiles instead of once per tile and group in front of every bound
     int gm_word = -1;
@@ -958,9 +870,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
       unsigned long long K = casts;
       unsigned long long mymask = casts;          // the tile triangles THIS lane's surface point may still need
       if (task_ok) {                                               // level 1, lane = triangle, per group of points
-        TriLane T1;
-        T1.v0 = xyz(t_v0[lane]); T1.e1 = xyz(t_e1[lane]); T1.e2 = xyz(t_e2[lane]); T1.c = xyz(t_c[lane]);
-        T1.c1 = norm1(T1.c); T1.e1_1 = norm1(T1.e1); T1.e2_1 = norm1(T1.e2);
+        const TriLane T1 = tri_lane(t_v0, t_e1, t_e2, t_c, lane);
         const float v0n = norm1(T1.v0);
         const unsigned long long alive = ballot(slit && !blocked && (my_sh & active) != active);
         K = 0ull; mymask = 0ull;
@@ -988,7 +898,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
         }
         if (ballot(slit && !blocked) == 0ull) { task_blocked = true; return; }
       }
-      MESH_STAMP(5)
+      RT_STAMP(xw, 5)
       if (COUNT) { xw[2]++; xw[3] += __popcll(K); }
       if (K == 0ull) return;
       K = uniform64(K);                                            // the loops over K then run on the scalar unit
@@ -999,11 +909,11 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
         const int kq = __builtin_ctzll(kk);
         const bool part = ((mymask >> kq) & 1ull) != 0ull;
         if (ballot(part && slit && !blocked) == 0ull) continue;
-        const Bound pb = point_bound(start, dir, hh, dlen, dminlen, dk, xyz(t_v0[kq]), xyz(t_e1[kq]), xyz(t_e2[kq]), xyz(t_c[kq]), part && slit && !blocked);
+        const Bound pb = point_bound(start, dir, hh, dlen, cc.dminlen, cc.dk, xyz(t_v0[kq]), xyz(t_e1[kq]), xyz(t_e2[kq]), xyz(t_c[kq]), part && slit && !blocked);
         if (part && (!pb.clear || !sane)) need |= 1ull << kq;
         blocked = blocked || (part && sane && pb.all_blocked);
       }
-      MESH_STAMP(6)
+      RT_STAMP(xw, 6)
       const bool mine = slit && !blocked && need != 0ull && (my_sh & active) != active;
       const unsigned long long work = ballot(mine);
       if (NS <= kPointSamples) {
@@ -1077,24 +987,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
     active = cnt_s == 64 ? ~0ull : ((1ull << cnt_s) - 1ull);
     my_sh = 0ull;
     rng_group = -1;
-    {
-      int bw = -1;
-      unsigned long long bm = 0ull;
-      for (;;) {
-        int t0 = -1, t1 = -1, t2 = -1, t3 = -1, cnt = 0;
-        if ((t0 = next_tile(smask, bw, bm)) >= 0) { cnt = 1;
-          if ((t1 = next_tile(smask, bw, bm)) >= 0) { cnt = 2;
-            if ((t2 = next_tile(smask, bw, bm)) >= 0) { cnt = 3;
-              if ((t3 = next_tile(smask, bw, bm)) >= 0) cnt = 4; } } }
-        if (cnt == 0) break;
-        MESH_STAMP(7)
-        load_batch(t0, t1, t2, t3, cnt, false);
-        MESH_STAMP(4)
-        for (int sl = 0; sl < cnt; ++sl)
-          if (!coop || sl == wave) shadow_tile(sl == 0 ? t0 : sl == 1 ? t1 : sl == 2 ? t2 : t3, tile + sl * kSlot);
-        if (cnt < kBatch) break;
-      }
-    }
+    walk_tiles(smask, false, [&](int) { RT_STAMP(xw, 7) }, [&](int) { RT_STAMP(xw, 4) }, shadow_tile);
     if (coop) {                                         // any-hit over all four waves' tiles: OR of what each wave found
       coop_sh[wave * 64 + lane] = my_sh;
       coop_fl[wave * 64 + lane] = (blocked ? 1u : 0u) | (task_blocked ? 2u : 0u);
@@ -1137,16 +1030,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
     if (blocked || task_blocked) unshadowed = 0;
 
     // ---- phase 4: shading and the AA sum, as in rt_kernel_wave.hip ---------------------------------------
-    f3 contrib = mk(0.f, 0.f, 0.f);
-    if (lit) {
-      float total = 0.0f;
-      if (unshadowed < NS) total += 0.0f * term;
-#pragma unroll 8
-      for (int i = 0; i < NS; ++i) if (i < unshadowed) total += term;       // (one add per trip = one taken branch per add)
-      const float l = 0.5f + div_count(total, NS, inv_S);
-      if (secondary) { const float kk = 0.9f * l; contrib = mk(kk * ray.col.x, kk * ray.col.y, kk * ray.col.z); }
-      else contrib = mk(ray.col.x * l, ray.col.y * l, ray.col.z * l);
-    }
+    const f3 contrib = shade(lit, secondary, unshadowed, NS, term, P.inv_S, ray.col);
     const f3 acc = aa_sum(contrib, aa, (p < PT ? p : 0) * aa);
     {   // output lane l owns block pixel (l & 7, l >> 3): take its sum from the task and pixel that cover it
       const int qo = zorder_of(lane & 7, lane >> 3);
@@ -1156,13 +1040,13 @@ __global__ __launch_bounds__(64 * kMeshWaves, RT_MESH_MIN_BLOCKS) void rt_draw_m
       if (ok == k) outc = v;
     }
   }
-  MESH_STAMP(7)
+  RT_STAMP(xw, 7)
   if (COUNT) xw[7] += ntask;
   {
     const int x = B.x0 + (lane & 7);
     const int lr = B.lr0 + (lane >> 3);
     if (!COUNT && !PROF && (!coop || wave == 0) && lr < P.owned_rows && x < P.W) {      // the counting pass has no framebuffer
-      const f3 c = mk(div_count(outc.x, aa, inv_aa), div_count(outc.y, aa, inv_aa), div_count(outc.z, aa, inv_aa));
+      const f3 c = pixel_colour(outc, aa, P.inv_aa);
       const size_t o = (size_t)(PC(out_global) ? band_global_row_cold(P, lr) : lr) * P.W + x;
       PC(out_argb)[o] = pack_argb(c);
       if (PC(out_rgb)) PC(out_rgb)[o] = make_float4(c.x, c.y, c.z, 1.0f);
@@ -1244,7 +1128,7 @@ __global__ void rt_mesh_estimate(const FrameParams P, unsigned int* cost, int n_
   // A block that looks at a mirror or glass sphere sends bounce rays through every tile for up to `bounces` rounds: by far
   // the dearest blocks of a frame (configs[4] + the reference's spheres: a block on a sphere's rim 15 ms, the frame without
   // them 8 ms).  Counted as all tiles, twice: rt_mesh_order then enters them as cooperative jobs, whose four waves share each
-  // round's tiles — in the first frame already (30 -> ms, profiles/r03_mesh.txt).
+  // round's tiles — in the first frame already (30.4 -> 16.3 ms, profiles/r03_mesh.txt).
   if (P.bounces > 0) {
     const float xc = (float)(job_x * 16 + 8), yc = (float)(band_global_row(P, lrr + 8 < P.owned_rows ? lrr + 8 : P.owned_rows - 1));
     for (int i = 0; i < P.nsph; ++i) {
@@ -1290,7 +1174,7 @@ void launch_mesh(const FrameParams& P, bool count, bool prof, hipStream_t stream
     if (fork) hipStreamWaitEvent(stream, ev_join, 0);
   }
   const int n_jobs = ((P.W + 15) / 16) * ((P.owned_rows + 15) / 16);
-  const int resident = P.mesh_blocks > 0 ? P.mesh_blocks : 256 * RT_MESH_MIN_BLOCKS;
+  const int resident = P.mesh_blocks > 0 ? P.mesh_blocks : 256 * kMeshMinBlocks;
   const dim3 grid(n_jobs < resident ? (n_jobs > 0 ? n_jobs : 1) : resident);
   hipMemsetAsync(P.job_counter, 0, sizeof(unsigned int), stream);
   const size_t lds_bytes = kBatch * kSlot * sizeof(float4) + kMeshWaves * (size_t)mesh_wave_lds_bytes(P.S > kPointSamples || P.nsph > 0) + 2 * (size_t)nwords * 8 +
@@ -1312,6 +1196,6 @@ void launch_mesh(const FrameParams& P, bool count, bool prof, hipStream_t stream
     hipLaunchKernelGGL(rt_mesh_order, dim3(1), dim3(1024), 0, stream, P.mesh_cost, P.mesh_order_out, P.mesh_queue_len, n_jobs, (P.mask_debug & 8) ? 1 : 0);
 }
 
-int mesh_blocks_per_cu() { return RT_MESH_MIN_BLOCKS; }
+int mesh_blocks_per_cu() { return kMeshMinBlocks; }
 
 }  // namespace uobrt

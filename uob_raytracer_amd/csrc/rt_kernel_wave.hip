@@ -37,27 +37,13 @@
 #define RT_RNG_JUMP_IN_LDS
 #include "rt_wave_common.h"
 
-#ifndef RT_OPT_SPHJOB
-#define RT_OPT_SPHJOB 1
-#endif
-#ifndef RT_OPT_LIGHTSIDE
-#define RT_OPT_LIGHTSIDE 1
-#endif
-#ifndef RT_OPT_JOBK
-#define RT_OPT_JOBK 1       // level 1 of a wider point set, reused by the job's next tasks
-#endif
-#ifndef RT_OPT_TASKSPH
-#define RT_OPT_TASKSPH 1
-#endif
-#ifndef RT_CHUNK
-#define RT_CHUNK 4          // jobs per hand-out while the queue is long (2: 3.58 ms, 4: 3.50, 8: 3.64 on the headline frame)
-#endif
-
 #include <type_traits>
 
 namespace uobrt {
 
 namespace {
+
+constexpr int kChunk = 4;   // jobs per hand-out while the queue is long (2: 3.58 ms, 4: 3.50, 8: 3.64 on the headline frame)
 
 // Per-wave LDS.
 //   r0..r2 (brute-force path): sample-independent terms of (surface point, triangle i), written by
@@ -320,27 +306,17 @@ __device__ __forceinline__ void wave_unshadowed_packed(const FrameParams& P, con
 
 }  // namespace
 
-// Persistent waves: the grid is what fits the chip at once (CUs x RT_MIN_WAVES workgroups of 4 waves); each
+// Persistent waves: the grid is what fits the chip at once (CUs x kMinWaves workgroups of 4 waves); each
 // wave pulls 64-pixel segments (jobs) from an atomic counter until none is left, so a wave slot is never idle
 // while work remains.  (With one workgroup per 4 segments the cost spread between fully lit and penumbra
 // segments left on average 2 of 4-5 possible waves per SIMD resident: workgroup resources are only released
 // when the slowest wave of the workgroup ends.)  The exit condition is reached by every wave: the counter
 // only grows.
 // (one wave per workgroup measured 20 % slower than four: 22.1 vs 18.3 ms on the headline frame)
-#ifndef RT_WAVES_PER_BLOCK
-#define RT_WAVES_PER_BLOCK 4
-#endif
-constexpr int kWavesPerBlock = RT_WAVES_PER_BLOCK;
-// PROF builds (diagnostic only, never timed): per-phase s_memtime shares, summed over waves, in counters[0..7]
-#define RT_STAMP(slot)                                                              \
-  if (PROF) {                                                                       \
-    unsigned long long now_;                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                              \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) :: "memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                              \
-    prof[slot] += now_ - tlast;                                                     \
-    tlast = now_;                                                                   \
-  }
+constexpr int kWavesPerBlock = 4;
+// 5 waves per SIMD (<= 96 VGPRs; what spills is written once per wave, outside the loops): the kernel is bound by
+// instruction issue and needs the waves — 5 per SIMD measured 3.76 ms against 4.10 ms at 4 (128 VGPRs)
+constexpr int kMinWaves = 5;
 // STRIDE > 0: the LDS record arrays have a fixed stride of STRIDE triangles (n <= STRIDE) and the whole LDS
 // layout is static, so every array base is an immediate of the ds_read instead of a VGPR; 0 = packed by n.
 template <int STRIDE, bool CULL>
@@ -356,13 +332,9 @@ __host__ __device__ constexpr int wave_fixed_lds_float4() {
 // BIGAA: 65..256 AA samples per pixel (the reference's grid is a pair of constants, kernels.cl:12-14): a pixel's samples are
 // worked off in chunks of 64 — a task is one chunk of ONE pixel, a job's tasks run pixel by pixel, chunk by chunk, and the
 // pixel's running sum (final_color_total +=, :415-425, in sample order) is carried from chunk to chunk.
+// PROF: per-phase s_memtime shares (RT_STAMP), summed over waves, in counters[0..7]
 template <bool CULL, bool COUNT, bool PROF = false, int STRIDE = 0, bool MULTI = false, int AA_X = 0, int AA_Y = 0, int SS = 0, bool BIGAA = false>
-// 5 waves per SIMD (<= 96 VGPRs; what spills is written once per wave, outside the loops): the kernel is bound by
-// instruction issue and needs the waves — 5 per SIMD measured 3.76 ms against 4.10 ms at 4 (128 VGPRs)
-#ifndef RT_MIN_WAVES
-#define RT_MIN_WAVES 5
-#endif
-__global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wave(const FrameParams P) {
+__global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(const FrameParams P) {
   unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tlast = PROF ? __builtin_amdgcn_s_memtime() : 0ull;
   extern __shared__ float4 lds_dyn[];
@@ -386,7 +358,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
     const unsigned long long m = ballot(casts);
     if (casts) sidx[__popcll(m & ((1ull << lane) - 1ull))] = lane;
   }
-  RT_STAMP(7)                               // 7: staging work before the workgroup barrier
+  RT_STAMP(prof, 7)                         // 7: staging work before the workgroup barrier
   __syncthreads();
   // the shadow-casting triangles' (v0,e1,e2,c) once more, in caster order: levels 2 and 3 index them by
   // the bit position of the candidate mask, with no index indirection in their dependent chains
@@ -423,12 +395,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
   const int tl = lane < ns ? lane : 0;
   TriLane T;
   if (!CULL) {
-    T.v0 = xyz(SC.v0[tl]); T.e1 = xyz(SC.e1[tl]); T.e2 = xyz(SC.e2[tl]); T.c = xyz(SC.c[tl]);
-    T.c1 = norm1(T.c); T.e1_1 = norm1(T.e1); T.e2_1 = norm1(T.e2);
+    T = tri_lane(SC.v0, SC.e1, SC.e2, SC.c, tl);
     L.r0[lane] = make_float4(T.c.x, T.c.y, T.c.z, 0.f);   // static part of record 0
   }
 
-  RT_STAMP(0)                               // 0: staging + set-up
+  RT_STAMP(prof, 0)                         // 0: staging + set-up
   Work wk, xw;                               // xw: executed-work counters of this wave (COUNT builds only)
   if (COUNT) for (int q = 0; q < 8; ++q) xw.v[q] = 0;
   // ---- job loop.  The queue has kJobHeads heads; a wave pulls from its home head until that one's jobs are
@@ -459,7 +430,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
   if (timeline && lane == 0) { tls[0] = __builtin_amdgcn_s_memrealtime(); tls[1] = 0ull; }
   bool phase_a = n_heavy != 0u;
   // Several jobs per hand-out (a hand-out is a returning device-scope atomic that stalls its wave for microseconds), fewer
-  // as the queue runs out: RT_CHUNK while more than 2 T jobs per wave remain, two while more than T, then one, with T = 8 for
+  // as the queue runs out: kChunk while more than 2 T jobs per wave remain, two while more than T, then one, with T = 8 for
   // 64-pixel jobs and T = 1 for the halved jobs of short frames, which hold ~16 jobs per wave in all and would otherwise
   // never see a full hand-out (measured, ms: 1024 rows, 64-pixel jobs: 0.92 with T = 8, 1.00 with T = 1; 512 rows, 32-pixel
   // jobs: 0.570 against 0.540).
@@ -467,22 +438,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
   const int per_wave = PC(job_tasks) * PT > 32 ? 8 * grid_waves : grid_waves;
   int next_job = -1, chunk_left = 0;                    // the rest of the last hand-out, still to do
   unsigned int listed = 0u;                             // bit i: job i of the rest of the hand-out is on last frame's list
-  int chunk = PC(njobs) > 2 * per_wave ? RT_CHUNK : (PC(njobs) > per_wave ? 2 : 1);      // size of the next hand-out
+  int chunk = PC(njobs) > 2 * per_wave ? kChunk : (PC(njobs) > per_wave ? 2 : 1);      // size of the next hand-out
   for (;;) {
   int job = 0;
-  const int jt = PC(job_tasks);                 // tasks of this hand-out
-  int k0 = 0, k1 = jt;                        // the tasks of the job this hand-out covers
+  const int jt = PC(job_tasks);                 // tasks of a job
   if (phase_a) {
     if (lane == 0) job = (int)atomicAdd(PC(job_counter) + (kJobHeads + head) * kJobHeadStride, 1u);
-    unsigned int unit = (unsigned int)__builtin_amdgcn_readfirstlane(job) * kJobHeads + (unsigned int)head;
-    if (PC(split_listed)) {
-      // UOB_RT_SPLIT_LISTED=1: the listed jobs go out one TASK at a time (unit u = task u / n of listed job u % n, all
-      // first tasks before all second ones) — for frames so short that one job's 64 undecided surface points per task
-      // (25x an ordinary task, profiles/r02_wave_timeline.txt) could be the critical path.  Measured: they are not.
-      const unsigned int q = unit / n_heavy;
-      if (q >= (unsigned int)jt) { phase_a = false; continue; }
-      unit -= q * n_heavy; k0 = (int)q; k1 = k0 + 1;
-    } else if (unit >= n_heavy) { phase_a = false; continue; }
+    const unsigned int unit = (unsigned int)__builtin_amdgcn_readfirstlane(job) * kJobHeads + (unsigned int)head;
+    if (unit >= n_heavy) { phase_a = false; continue; }
     job = (int)PC(heavy_prev)[unit];
     if (job < 0 || job >= PC(njobs)) continue;
   } else {
@@ -501,7 +464,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
       }
       // what this head has left decides the next hand-out
       const int left = PC(njobs) - next_job;
-      chunk = left > 2 * per_wave ? RT_CHUNK : (left > per_wave ? 2 : 1);
+      chunk = left > 2 * per_wave ? kChunk : (left > per_wave ? 2 : 1);
     }
     if (job >= PC(njobs)) {
       // This head is empty: look at ALL heads at once (lane h reads head h: one memory round trip, not one per head — walking
@@ -517,8 +480,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
     }
     if ((listed & 1u) != 0u) continue;                                    // listed: taken care of by phase A
   }
-  k0 = __builtin_amdgcn_readfirstlane(k0); k1 = __builtin_amdgcn_readfirstlane(k1);   // (the same in every lane; see `wave` above)
-  RT_STAMP(7)                               // 7: waiting for the hand-out (PROF builds)
+  RT_STAMP(prof, 7)                         // 7: waiting for the hand-out (PROF builds)
   if (timeline && lane == 0) tls[1] += 1ull;
   const unsigned long long job_t0 = lpt ? __builtin_amdgcn_s_memtime() : 0ull;
   // Rows are handed out from the middle of the rank's rows outwards: segments differ 10x in cost, and the kernel
@@ -556,12 +518,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
     const bool clear = primary_clear(duc, eu, dumax, xyz(c4), c4.w, xyz(S.pc[ti]), xyz(S.qc[ti]));
     if (dumax < 1e30f) Kp_job &= ~ballot(clear);
     // ... and whether any of them can touch a sphere at all (else the two quadratic tests per ray are skipped)
-    if (RT_OPT_SPHJOB && P.nsph > 0 && dumax < 1e30f)
+    if (P.nsph > 0 && dumax < 1e30f)
       sph_job = ballot(sphere_bundle_maybe(P, lane, mk(P.cam[0], P.cam[1], P.cam[2]), 0.0f, duc, bsqrt(dot3(duc, duc)),
                                            1.0001f * bsqrt(dot3(eu, eu)), false)) != 0ull;
   }
-  RT_STAMP(0)                               // 0: job set-up (primary-ray bounds of the job)
-  for (int k = k0; k < k1; ++k) {
+  RT_STAMP(prof, 0)                         // 0: job set-up (primary-ray bounds of the job)
+  for (int k = 0; k < jt; ++k) {
     const int lnA = opaque(lane);
     // ---- phase 1: 64 primary rays, lnA = (pixel, AA sample) -----------------------------------------
     const int kp = BIGAA ? k / chunks : k;     // BIGAA: the pixel (within the job) this task belongs to, and which chunk of its samples
@@ -600,30 +562,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
         unsigned long long Kb = n == 64 ? ~0ull : ((1ull << n) - 1ull);
         {
           const int lnK = opaque(lane);
-          const f3 o = ray.start, d = ray.dir;
-          const float mag = fmaxf(norm_inf(o), norm_inf(d));
-          const bool fin = act && mag < 1e30f;                         // false for NaN as well
-          const bool isnan_ = act && !(mag == mag);                    // a NaN ray hits nothing whatever the set
-          const unsigned long long finm = ballot(fin);
-          if (finm != 0ull && ballot(act && !fin && !isnan_) == 0ull) {
-            const float big = 3.0e38f;
-            const f3 olo = mk(wave_min(fin ? o.x : big), wave_min(fin ? o.y : big), wave_min(fin ? o.z : big));
-            const f3 ohi = mk(wave_max(fin ? o.x : -big), wave_max(fin ? o.y : -big), wave_max(fin ? o.z : -big));
-            const f3 dlo = mk(wave_min(fin ? d.x : big), wave_min(fin ? d.y : big), wave_min(fin ? d.z : big));
-            const f3 dhi = mk(wave_max(fin ? d.x : -big), wave_max(fin ? d.y : -big), wave_max(fin ? d.z : -big));
-            const f3 s0 = 0.5f * (olo + ohi), D0 = 0.5f * (dlo + dhi);
-            const float es = 0.5001f * fmaxf(fmaxf(ohi.x - olo.x, ohi.y - olo.y), ohi.z - olo.z) + 1e-6f * norm1(s0);
-            const float ed = 0.5001f * fmaxf(fmaxf(dhi.x - dlo.x, dhi.y - dlo.y), dhi.z - dlo.z) + 1e-6f * norm1(D0);
-            const float dmx = fmaxf(fmaxf(fmaxf(fabsf(dlo.x), fabsf(dhi.x)), fmaxf(fabsf(dlo.y), fabsf(dhi.y))), fmaxf(fabsf(dlo.z), fabsf(dhi.z)));
-            TriLane Tb;
-            const int tb_i = lnK < n ? lnK : 0;
-            Tb.v0 = xyz(S.v0[tb_i]); Tb.e1 = xyz(S.e1[tb_i]); Tb.e2 = xyz(S.e2[tb_i]); Tb.c = xyz(S.c[tb_i]);
-            Tb.c1 = norm1(Tb.c); Tb.e1_1 = norm1(Tb.e1); Tb.e2_1 = norm1(Tb.e2);
-            const float dl = 1.7321f * dmx * 1.0001f;                   // >= |d|_2 of every ray
-            const Bound bb = task_bound(Tb, s0, D0, es, ed, 2e-6f * dl, 0.0f, dl);
-            Kb &= ~ballot(bb.clear);
-          } else if (finm == 0ull) {
-            Kb = 0ull;                                                  // only NaN rays: they hit nothing
+          const BounceBundle bnd = bounce_bundle(act, ray.start, ray.dir);
+          if (bnd.mode == 1) {
+            const TriLane Tb = tri_lane(S.v0, S.e1, S.e2, S.c, lnK < n ? lnK : 0);
+            Kb &= ~ballot(task_bound(Tb, bnd.s0, bnd.D0, bnd.es, bnd.ed, 2e-6f * bnd.dl, 0.0f, bnd.dl).clear);
+          } else if (!bnd.finite) {
+            Kb = 0ull;                                                  // no ray with finite coordinates: no triangle test
           }
         }
         if (act) {
@@ -632,13 +576,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
         }
       }
     }
-    RT_STAMP(1)                             // 1: primary rays + bounces
+    RT_STAMP(prof, 1)                       // 1: primary rays + bounces
     const int lnB = opaque(lane);
     // per-lnB light set-up of direct_light, :323-326
-    const f3 dir = light - ray.P;
-    const f3 start = ray.P + 0.0001f * dir;
-    const float radius_sq = dir.x * dir.x + dir.y * dir.y + dir.z * dir.z;
-    const float term = (16.0f * fmaxf(dot3(dir, ray.N), 0.0f)) / (4.0f * 3.14159274f * radius_sq);
+    const LightSetup ls = light_setup(light, ray);
+    const f3 dir = ls.dir, start = ls.start;
+    const float radius_sq = ls.radius_sq, term = ls.term;
 
     // A surface point that faces away from the light — term == 0: max(dot, 0) is 0 (:335) — adds (mask * 0) / (4 pi r^2) = +-0 per
     // sample whatever its masks are, and the sum stays +0: its samples need no test at all.  (Exactly zero only: a NaN or
@@ -653,13 +596,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
     unsigned long long K = tri_lanes, sphmask = P.nsph > 0 ? ~0ull : 0ull;
     need_t need = (need_t)~(need_t)0;
     if (CULL && work != 0ull) {
-      // bounds used by the cull (never by the shading): |dir|, jitter half-width with rounding slack
-      const float dlen = bsqrt(radius_sq);
-      const float hh = 1.002f * hbox + 2e-6f * (dlen + hbox);
-      float dminlen = dlen - 1.7321f * hh;
-      const bool sane = slit && (radius_sq > 1e-18f) && (radius_sq < 1e30f);
-      if (!sane || !(dminlen > 0.0f)) dminlen = 0.0f;                  // disables the distance rule
-      const float dk = dlen * 1.000004f;
+      const CullConsts cc = cull_consts(radius_sq, hbox, slit);
+      const float dlen = cc.dlen, hh = cc.hh;
+      const bool sane = cc.sane;
       // level 1: all such points of the task at once, lnB = triangle
       bool task_blocked = false;
       SphereBound sb;
@@ -677,14 +616,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
         // (Per-component widths — the points of a row on a plane differ along one line — keep fewer casters still, but three
         // reductions and the weighted sums cost more than that: 2.58; profiles/r03_l1_width.txt.)
         bool reuse = false;
-        if (RT_OPT_JOBK && jk_valid && all_sane) {
+        if (jk_valid && all_sane) {
           const f3 dj = dir - jk_D0;
           reuse = wave_max_pos(slit ? norm_inf(dj) : 0.0f) <= jk_ed;
         }
         if (reuse) {
           K = jk_K; task_sph = jk_sph; task_blocked = jk_blocked;
         } else {
-        const int jr = RT_OPT_JOBK ? 63 - __builtin_clzll(work) : __builtin_ctzll(work);
+        const int jr = 63 - __builtin_clzll(work);
         const f3 s0 = mk(rl(start.x, jr), rl(start.y, jr), rl(start.z, jr));
         const f3 D0 = mk(rl(dir.x, jr), rl(dir.y, jr), rl(dir.z, jr));
         // One wave reduction instead of four: the points' start and dir move together (start = X + 1e-4 dir,
@@ -694,8 +633,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
         const float ed_task = wave_max_pos(slit ? norm_inf(dd) : 0.0f);
         // (no wider than the tasks this job still has to come can use: its last task — and every task of a one-task job, the
         // 16-pixel jobs of a 1024^2 frame — bounds its own set)
-        const float left = (float)(k1 - 1 - k);
-        const float ed = RT_OPT_JOBK ? ed_task * (left > 0.0f ? fminf(PC(l1_inflate), left + 0.5f) : 1.0f) : ed_task;
+        const float left = (float)(jt - 1 - k);
+        const float ed = ed_task * (left > 0.0f ? fminf(PC(l1_inflate), left + 0.5f) : 1.0f);
         const float dlen0 = rl(dlen, jr);
         const float dlen_max = (dlen0 + 1.7321f * ed) * 1.000001f;
         const float dlen_min = fmaxf(dlen0 - 1.7321f * ed, 0.0f) * 0.999999f;
@@ -703,33 +642,25 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
         jk_valid = false;
         if (all_sane && es < 1e30f && ed < 1e30f) {                    // finite, non-degenerate
           const float hh_task = 1.002f * hbox + 2e-6f * (dlen_max + hbox);
-          if (RT_OPT_TASKSPH && P.nsph > 0)       // every sample direction lies within sqrt(3) (ed + hh) of D0, every start within es of s0
+          if (P.nsph > 0)       // every sample direction lies within sqrt(3) (ed + hh) of D0, every start within es of s0
             task_sph = ballot(sphere_bundle_maybe(P, lane, s0, es, D0, dlen0, 1.7321f * (1.001f * ed + hh_task), true)) != 0ull;
-          TriLane T1;
-          T1.v0 = xyz(SC.v0[(lnB < ns ? lnB : 0)]); T1.e1 = xyz(SC.e1[(lnB < ns ? lnB : 0)]); T1.e2 = xyz(SC.e2[(lnB < ns ? lnB : 0)]); T1.c = xyz(SC.c[(lnB < ns ? lnB : 0)]);
-          T1.c1 = norm1(T1.c); T1.e1_1 = norm1(T1.e1); T1.e2_1 = norm1(T1.e2);
+          const TriLane T1 = tri_lane(SC.v0, SC.e1, SC.e2, SC.c, lnB < ns ? lnB : 0);
           // The bound from the LIGHT's side (rt_wave_common.h light_bundle_bound, the mesh kernel's level 1): start and direction
           // of a shadow ray are tied together (start = X + 1e-4 dir, X = light - dir), so the direction box counts once instead
           // of widening both the start box and the direction box as task_bound must for an arbitrary point set: fewer
           // survivors K for level 2.
-#if RT_OPT_LIGHTSIDE
           const Bound tb = light_bundle_bound(T1, light, s0, es, D0, ed, hh_task, dlen_min, dlen_max, P.light_inf + dlen_max + norm1(T1.v0));
-#else
-          const Bound tb = task_bound(T1, s0, D0, es, ed, hh_task, dlen_min, dlen_max);
-#endif
           K = tri_lanes & ~ballot(tb.clear);
           task_blocked = (tri_lanes & ballot(tb.all_blocked)) != 0ull;
-          if (RT_OPT_JOBK) {
-            // what the next tasks compare with: directions within 0.9999 ed of D0 (the bound itself allows 1.001 ed and more)
-            jk_valid = true; jk_D0 = D0; jk_ed = uniform(ed * 0.9999f); jk_K = K; jk_sph = task_sph; jk_blocked = task_blocked;
-          }
+          // what the next tasks compare with: directions within 0.9999 ed of D0 (the bound itself allows 1.001 ed and more)
+          jk_valid = true; jk_D0 = D0; jk_ed = uniform(ed * 0.9999f); jk_K = K; jk_sph = task_sph; jk_blocked = task_blocked;
         }
         }
       }
       if (task_sph && !task_blocked && sane) sb = spheres_point(P, start, dir, dlen, hh);
       sphmask = ballot(slit && P.nsph > 0 && (sb.maybe || !sane));
       const bool sph_blocked = sane && sb.all_blocked;
-      RT_STAMP(2)                           // 2: light set-up + level 1
+      RT_STAMP(prof, 2)                     // 2: light set-up + level 1
       if (task_blocked) {
         unshadowed = 0; work = 0ull;
         if (COUNT) xw.v[5] += 1;
@@ -747,7 +678,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
           const float nA0_ = detc(start - xyz(SC.v0[kq]), c_), D0_ = detc(-dir, c_), Dl_ = hh * norm1(c_);
           const bool tneg = sane && ((D0_ - Dl_ > 0.0f && nA0_ < -1e-18f) || (D0_ + Dl_ < 0.0f && nA0_ > 1e-18f));
           if (ballot(slit && !tneg) == 0ull) continue;
-          const Bound pb = point_bound(start, dir, hh, dlen, dminlen, dk, xyz(SC.v0[kq]), xyz(SC.e1[kq]), xyz(SC.e2[kq]),
+          const Bound pb = point_bound(start, dir, hh, dlen, cc.dminlen, cc.dk, xyz(SC.v0[kq]), xyz(SC.e1[kq]), xyz(SC.e2[kq]),
                                        xyz(SC.c[kq]), slit && !tneg && !blocked);
           if (!pb.clear || !sane) need |= (need_t)((need_t)1 << pos);
           blocked = blocked || (sane && pb.all_blocked);
@@ -758,7 +689,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
       }
     }
 
-    RT_STAMP(3)                             // 3: level 2
+    RT_STAMP(prof, 3)                       // 3: level 2
     const int lnC = opaque(lane);
     // level 3 reads the surface points lane = sample: they go to LDS only for the tasks that get there
     if (work != 0ull) {
@@ -782,23 +713,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
       const int seg = (q3 * gp_magic) >> 16, pp = q3 - seg * GP;         // q3 / GP, q3 % GP
       if (seg < kRngSegs) {
         uint32_t* dst = L.rng + pp * kRngStride + comp;
-        uint32_t s;
-        if (!MULTI || pass == 0) {
-          const int gid = pixel_global_id(P, x0 + kp * PT + g * GP + pp, y);
-          const uint32_t seed = comp == 0 ? (uint32_t)gid : (uint32_t)((float)gid * (comp == 1 ? 91.0f : 19.0f));
-          s = xorshift(seed);
-        } else {
-          s = dst[63 * 4];                                               // the stream goes on where the last pass left it
-        }
-        if (seg > 0) s = rng_jump(s, seg);
-        const int it0 = seg * kRngSegLen;
-#pragma unroll 1
-        for (int j = 0; j < kRngSegLen; ++j) { s = xorshift(s); if (it0 + j < cnt_s) dst[(it0 + j) * 4] = s; }
+        const uint32_t s = (!MULTI || pass == 0) ? rng_seed(pixel_global_id(P, x0 + kp * PT + g * GP + pp, y), comp)
+                                                 : dst[63 * 4];        // the stream goes on where the last pass left it
+        rng_fill_segment(dst, s, seg, cnt_s);
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      RT_STAMP(4)                           // 4: xorshift streams
+      wave_lds_sync();
+      RT_STAMP(prof, 4)                     // 4: xorshift streams
       if (CULL && !COUNT && !MULTI && ((SS > 0 && SS <= 32) || (SS == 0 && STRIDE == 32 && !BIGAA && NS <= 16))) {
         // few samples: lane = (surface point, sample), 64 / SP points of one pixel per instance, two instances per pass
         // (the instantiations specialised on the sample count; the static-layout generic one for up to 16 samples)
@@ -857,9 +777,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
       if (MULTI) __builtin_amdgcn_wave_barrier();      // the next pass rewrites the scratch
       }                                                 // passes
       __builtin_amdgcn_wave_barrier();          // scratch is rewritten by the next group
-      RT_STAMP(5)                           // 5: level 3 sample tests
+      RT_STAMP(prof, 5)                     // 5: level 3 sample tests
     }
-    RT_STAMP(5)
+    RT_STAMP(prof, 5)
 
     const int lnD = opaque(lane);
     // ---- phase 4: shade lnD-parallel (direct_light's sum :335, then :354 / :421-422) ----------------
@@ -867,26 +787,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
       xw.v[6] += (unsigned)__popcll(work & ballot(lit && unshadowed == NS));
       xw.v[7] += (unsigned)__popcll(work & ballot(lit && unshadowed == 0));
     }
-    f3 contrib = mk(0.f, 0.f, 0.f);
-    {
-      // direct_light's running sum (:335): the same term added once per unblocked sample, in sequence.
-      // Most tasks have every lit lnD fully lit: then the adds need no per-lnD predicate.
-      float total = 0.0f;
-      // (eight adds per trip: one add per trip is a taken branch per add, and the chain is on every task's critical path)
-      if (ballot(lit && unshadowed != NS) == 0ull) {
-#pragma unroll 8
-        for (int i = 0; i < NS; ++i) total += term;
-      } else {
-        if (unshadowed < NS) total += 0.0f * term;        // a blocked sample adds 0*term (NaN/inf-faithful)
-#pragma unroll 8
-        for (int i = 0; i < NS; ++i) if (i < unshadowed) total += term;
-      }
-      if (lit) {
-        const float l = 0.5f + div_count(total, NS, inv_S);
-        if (secondary) { const float kk = 0.9f * l; contrib = mk(kk * ray.col.x, kk * ray.col.y, kk * ray.col.z); }
-        else contrib = mk(ray.col.x * l, ray.col.y * l, ray.col.z * l);
-      }
-    }
+    const f3 contrib = shade(lit, secondary, unshadowed, NS, term, inv_S, ray.col);
     // sum the AA rays of each pixel in index order (final_color_total +=, :415-425); a ray without a
     // contribution adds +0, which leaves the running sum unchanged bit for bit
     if (BIGAA) {
@@ -905,24 +806,24 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, RT_MIN_WAVES) void rt_draw_wav
         if (rel >= 0 && rel < PT) outc = v;
       }
     }
-    RT_STAMP(6)                             // 6: shading + AA sum
+    RT_STAMP(prof, 6)                       // 6: shading + AA sum
   }
   // ---- store: the job's consecutive pixels, one coalesced access per wave ------------------------------
   const int x = x0 + lane;
-  if (!COUNT && !PROF && (BIGAA ? lane < JP : (lane >= k0 * PT && lane < k1 * PT)) && x < P.W) {
-    const f3 c = mk(div_count(outc.x, aa_full, inv_aa), div_count(outc.y, aa_full, inv_aa), div_count(outc.z, aa_full, inv_aa));
+  if (!COUNT && !PROF && (BIGAA ? lane < JP : lane < jt * PT) && x < P.W) {
+    const f3 c = pixel_colour(outc, aa_full, inv_aa);
     const size_t o = (size_t)(PC(out_global) ? y : lr) * P.W + x;
     PC(out_argb)[o] = pack_argb(c);
     if (PC(out_rgb)) PC(out_rgb)[o] = make_float4(c.x, c.y, c.z, 1.0f);
   }
   if (lpt) {
     const unsigned long long cost = __builtin_amdgcn_s_memtime() - job_t0;
-    if (lane == 0) { cost_acc[0] += cost; cost_acc[1] += (unsigned long long)(k1 - k0); }
+    if (lane == 0) { cost_acc[0] += cost; cost_acc[1] += (unsigned long long)jt; }
     // Listed once per frame, by whichever wave finds one of its tasks expensive first — together with its two neighbours in
     // the row (lanes 1, 2): next frame's light or camera has moved, and with them the penumbra, by less than a job's width
     // (update() moves the light by at most 0.025 per frame, skeleton.cpp:290-298); a neighbour that turns out cheap only
-    // starts early.  (animated light, 20 frames: 3.39 -> ms mean with the static frame unchanged)
-    if (cost > heavy_thr * (unsigned long long)(k1 - k0) && lane < (PC(heavy_dilate) ? 3 : 1)) {
+    // starts early.  (The static frame is unchanged by this)
+    if (cost > heavy_thr * (unsigned long long)jt && lane < (PC(heavy_dilate) ? 3 : 1)) {
       const int jn = job + (lane == 1 ? -1 : (lane == 2 ? 1 : 0));
       const int col = jn - jrow * PC(nseg);
       if (col >= 0 && col < PC(nseg)) {
@@ -982,10 +883,10 @@ static size_t wave_kernel_lds(const FrameParams& P, bool cull) {
          (size_t)P.n_shadow * 4 * sizeof(float4) + kWavesPerBlock * (size_t)wave_lds_bytes(cull);
 }
 
-int wave_blocks_per_cu(bool leave_room) { return leave_room ? RT_MIN_WAVES - 1 : RT_MIN_WAVES; }
+int wave_blocks_per_cu(bool leave_room) { return leave_room ? kMinWaves - 1 : kMinWaves; }
 
 static dim3 wave_grid(const FrameParams& P) {
-  const int resident = P.wave_blocks > 0 ? P.wave_blocks : 256 * RT_MIN_WAVES;     // set per device by the host API
+  const int resident = P.wave_blocks > 0 ? P.wave_blocks : 256 * kMinWaves;     // set per device by the host API
   const int needed = (P.njobs + kWavesPerBlock - 1) / kWavesPerBlock;
   return dim3(needed < resident ? (needed > 0 ? needed : 1) : resident);
 }

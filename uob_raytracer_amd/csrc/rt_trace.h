@@ -79,6 +79,14 @@ enum { W_PRIMARY, W_BOUNCE, W_SHADOW, W_CTRI, W_CSPH, W_STRI, W_SSPH, W_LIT };
 #define RT_GLASS 1.52f
 #define RT_MAXFLOAT 3.402823466e+38f
 
+// The hit of `ray` on triangle i at barycentrics (u, v): kernels.cl:123-126 (== :198-201)
+__device__ __forceinline__ void set_hit(const LdsScene& S, Ray& ray, int i, float u, float v) {
+  ray.tri = i;
+  ray.P = (xyz(S.v0[i]) + u * xyz(S.e1[i])) + v * xyz(S.e2[i]);
+  ray.N = xyz(S.nrm[i]);
+  ray.col = S.col[i];
+}
+
 // Sphere part of the closest-hit search, kernels.cl:208-239 (== :132-163)
 template <bool COUNT>
 __device__ __forceinline__ void closest_spheres(const FrameParams& P, Ray& ray, float& current_t, Work& wk) {
@@ -151,12 +159,7 @@ __device__ void closest_hit_primary(const LdsScene& S, const FrameParams& P, Ray
       best = i; bu = u; bv = v; current_t = t;
     }
   }
-  if (best >= 0) {
-    ray.tri = best;
-    ray.P = (xyz(S.v0[best]) + bu * xyz(S.e1[best])) + bv * xyz(S.e2[best]);
-    ray.N = xyz(S.nrm[best]);
-    ray.col = S.col[best];
-  }
+  if (best >= 0) set_hit(S, ray, best, bu, bv);
   closest_spheres<COUNT>(P, ray, current_t, wk);
 }
 
@@ -182,12 +185,7 @@ __device__ inline void closest_hit_primary_masked(const LdsScene& S, const Frame
     const bool hit = (t < current_t) & (u >= 0) & (v >= 0) & ((u + v) <= 1) & (t >= 0);
     best = hit ? i : best; bu = hit ? u : bu; bv = hit ? v : bv; current_t = hit ? t : current_t;
   }
-  if (best >= 0) {
-    ray.tri = best;
-    ray.P = (xyz(S.v0[best]) + bu * xyz(S.e1[best])) + bv * xyz(S.e2[best]);
-    ray.N = xyz(S.nrm[best]);
-    ray.col = S.col[best];
-  }
+  if (best >= 0) set_hit(S, ray, best, bu, bv);
   Work wk;
   if (spheres) closest_spheres<false>(P, ray, current_t, wk);
 }
@@ -210,12 +208,7 @@ __device__ inline void closest_hit_masked(const LdsScene& S, const FrameParams& 
       best = i; bu = u; bv = v; current_t = t;
     }
   }
-  if (best >= 0) {
-    ray.tri = best;
-    ray.P = (xyz(S.v0[best]) + bu * xyz(S.e1[best])) + bv * xyz(S.e2[best]);
-    ray.N = xyz(S.nrm[best]);
-    ray.col = S.col[best];
-  }
+  if (best >= 0) set_hit(S, ray, best, bu, bv);
   Work wk;
   closest_spheres<false>(P, ray, current_t, wk);
 }
@@ -352,6 +345,33 @@ __device__ __forceinline__ uint32_t pack_argb(f3 c) {
 // kernels.cl:380 — the pixel id is formed in FP32
 __device__ __forceinline__ int pixel_global_id(const FrameParams& P, int x, int y) {
   return (int)((float)y * P.w_f + (float)x);
+}
+
+// The pixel's colour from the sum of its aa AA rays, kernels.cl:426.  (The callers store it themselves: the wave-mapped
+// kernels read the output pointers from the kernarg segment at the store; loaded in front of the colour, they cost the
+// reference-constants frame 4 % in scalar-register spills.)
+__device__ __forceinline__ f3 pixel_colour(f3 sum, int aa, float inv_aa) {
+  return mk(div_count(sum.x, aa, inv_aa), div_count(sum.y, aa, inv_aa), div_count(sum.z, aa, inv_aa));
+}
+
+// The state of component comp (0, 1, 2 = x, y, z) of pixel gid's jitter stream after the seed call, kernels.cl:319:
+// the seeds are gid, gid * 91 and gid * 19, the products formed in FP32
+__device__ __forceinline__ uint32_t rng_seed(int gid, int comp) {
+  return xorshift(comp == 0 ? (uint32_t)gid : (uint32_t)((float)gid * (comp == 1 ? 91.0f : 19.0f)));
+}
+
+// The per-point light set-up of direct_light, kernels.cl:323-326
+struct LightSetup {
+  f3 dir, start;
+  float radius_sq, term;
+};
+__device__ __forceinline__ LightSetup light_setup(f3 light, const Ray& ray) {
+  LightSetup l;
+  l.dir = light - ray.P;
+  l.start = ray.P + 0.0001f * l.dir;
+  l.radius_sq = l.dir.x * l.dir.x + l.dir.y * l.dir.y + l.dir.z * l.dir.z;
+  l.term = (16.0f * fmaxf(dot3(l.dir, ray.N), 0.0f)) / (4.0f * 3.14159274f * l.radius_sq);
+  return l;
 }
 
 }  // namespace uobrt
