@@ -13,8 +13,8 @@
  * State a context carries from frame to frame: the wave kernel hands out the row segments that were expensive
  * in the context's PREVIOUS frame first (scheduling only — no pixel depends on it; RT_FLAG_PLAIN_ORDER
  * switches it off).  Tuning knobs are read ONCE, in rt_init, from the environment (UOB_RT_JOB_TASKS,
- * UOB_RT_HEAVY_FACTOR4, UOB_RT_FULL_GRID, UOB_RT_TIMELINE: see DESIGN.md 4.1); nothing reads the
- * environment afterwards.
+ * UOB_RT_HEAVY_FACTOR4, UOB_RT_FULL_GRID, UOB_RT_TIMELINE, UOB_RT_TILE_ORDER: see DESIGN.md 4.1); nothing reads the
+ * environment afterwards, rt_update_scene included.
  */
 #ifndef UOB_RT_H
 #define UOB_RT_H
@@ -109,6 +109,27 @@ int32_t rt_config_owned_rows(const rt_config* cfg);
 int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4, const float* colors4,
             int32_t n_triangles, rt_ctx** out_ctx);
 
+/* Replace the context's triangles between frames (animated geometry).  Same packed layout and ownership as rt_init
+ * (data copied before the call returns); n must equal the context's triangle count.  Later frames render the new scene
+ * exactly as a context rt_init'ed with it would (bit-identical); the scheduling state ("last frame's expensive jobs
+ * first") is kept.  Validation is rt_init's (finite, |x| <= 2^16); on any such error the context keeps its previous scene.
+ * Meshes (n > 64): the tiles of rt_init are kept and their data recomputed on the device (refit), or, with
+ * RT_UPDATE_REORDER, the triangles are sorted into tiles again on the host as rt_init does (DESIGN.md 4.2 "Scene updates").
+ * The update waits for the context's previous frame, on whichever stream it runs; a multi-device context updates every
+ * device.  Blocking.                                                                                               */
+#define RT_UPDATE_REORDER 1u
+int rt_update_scene(rt_ctx* ctx, const float* vertices4, const float* normals4, const float* colors4, int32_t n,
+                    uint32_t flags);
+
+/* Same, from device memory on the context's device (devices[0] of a multi-device context: the other devices receive the
+ * scene by peer copy), enqueued on hip_stream (NULL = default stream) after the caller's earlier work on it.  A first pass
+ * on the device checks the bound and reduces what the context keeps of the scene; the call returns once that has been
+ * read back (this synchronises hip_stream up to that point) — the copies and the refit may still be running.  Later frames
+ * of the context, on any stream, wait for them; the source buffers must not change until hip_stream has passed the
+ * update.  RT_UPDATE_REORDER stages the scene through the host.                                                     */
+int rt_update_scene_device(rt_ctx* ctx, const void* d_vertices4, const void* d_normals4, const void* d_colors4, int32_t n,
+                           uint32_t flags, void* hip_stream);
+
 /* Render one frame and read it back: rot = 3 rows x (x,y,z,pad) exactly as rot_matrix[12] at
  * skeleton.cpp:149-151; cam/light = first 12 bytes of camera_position / light_position (:162,:164);
  * focal = focal_length (:166), in units of AA sub-pixels along x.  out_argb receives
@@ -168,6 +189,12 @@ int rt_debug_block_costs(rt_ctx* ctx, uint32_t* out, int32_t cap);
  * the kernel's own order; a cell no surface point can start from reads 0).  Writes min(count, cap) words, returns the word
  * count G^3 * words and stores G and words, or RT_E_UNSUPPORTED when the context builds no tile masks.                       */
 int rt_debug_world_masks(rt_ctx* ctx, uint64_t* out, int64_t cap, int32_t* grid, int32_t* words);
+
+/* Diagnostic, mesh kernel (n > 64): the tiled order and the per-tile data the kernel uses.  orig[j] = original index of the
+ * triangle at tiled position j (n entries); tiles = 12 floats per tile (rt_device.h FrameParams::tile_box: box lo.xyz | eta,
+ * box hi.xyz | emax, normal-cone axis | chi).  cap_tiles = 0 asks for the tile count only.  Returns the tile count, or
+ * RT_E_UNSUPPORTED when the context keeps no tiled copy (n <= 64, RT_FLAG_GENERIC_KERNEL).                              */
+int rt_debug_tile_data(rt_ctx* ctx, int32_t* orig, float* tiles, int32_t cap_tiles);
 
 /* Optional: let the device write the frame STRAIGHT into the caller's host framebuffer (screen->buffer,
  * SDLauxiliary.h:105) instead of rendering into device memory and copying 4 bytes per pixel back after the kernel

@@ -11,6 +11,7 @@ RT_FLAG_NO_TILE_BINS = 8
 RT_FLAG_PLAIN_ORDER = 16
 RT_FLAG_STAGED_GATHER = 32
 RT_TRACE_IN_SHADOW, RT_TRACE_CLOSEST_HIT = 0, 1
+RT_UPDATE_REORDER = 1
 
 
 class RtSphere(C.Structure):

@@ -11,6 +11,8 @@
 //
 //   uob_raytracer [--size N] [--frames K] [--aa X Y] [--shadows S] [--keys "left m:12,-3 . left i"] [--out file.bmp]
 //                 [--obj mesh.obj]            append load_obj(mesh.obj) to the box, as skeleton.cpp:102-103 does
+//                 [--move DX,DY,DZ]           with --obj: update() slides the mesh by (DX,DY,DZ) every frame (float32
+//                                             adds to its vertices; normals do not change), rt_update_scene before the frame
 //                 [--gpus N | --devices a,b,..]  render every frame on several GPUs inside the one context
 //                 [--copy-back]                  device buffer + blocking read-back instead of rt_register_output
 #include <chrono>
@@ -41,6 +43,9 @@ vector<rt_triangle> triangles;                                 // :72
 static rt_ctx* g_rt = nullptr;
 static vector<string> g_keys;                                  // scripted key presses, one per frame
 static size_t g_key_at = 0;
+static size_t g_obj_first = 0;                                 // --move: the loaded mesh is triangles[g_obj_first..]
+static bool g_move = false;
+static float g_move_by[3] = {0.0f, 0.0f, 0.0f};
 
 static void die(const char* op) {                              // checkError(), :499-507
   fprintf(stderr, "Error during operation '%s': %s\n", op, rt_last_error());
@@ -52,6 +57,14 @@ void opencl_initialise(const rt_config& cfg) {                 // :366-497
   vector<float> v(12 * (size_t)n), nr(4 * (size_t)n), col(4 * (size_t)n);
   rt_scene_pack(triangles.data(), n, v.data(), nr.data(), col.data());     // :474-484
   if (rt_init(&cfg, v.data(), nr.data(), col.data(), n, &g_rt) != RT_OK) die("rt_init");
+}
+
+// The moved scene to the device before the frame: the scene is no longer fixed after opencl_initialise
+void update_scene() {
+  const int n = (int)triangles.size();
+  vector<float> v(12 * (size_t)n), nr(4 * (size_t)n), col(4 * (size_t)n);
+  rt_scene_pack(triangles.data(), n, v.data(), nr.data(), col.data());
+  if (rt_update_scene(g_rt, v.data(), nr.data(), col.data(), n, 0) != RT_OK) die("rt_update_scene");
 }
 
 void offload_rendering(screen* screen) {                       // :146-182
@@ -71,6 +84,10 @@ bool update() {                                                // :282-361
     if (diff < 0.001f) lor = true;
     light_position[0] += diff / 20.0f;
   }
+  if (g_move)                                                  // the moving object: a translation of the loaded mesh
+    for (size_t t = g_obj_first; t < triangles.size(); ++t)
+      for (float* p : {triangles[t].v0, triangles[t].v1, triangles[t].v2})
+        for (int k = 0; k < 3; ++k) p[k] += g_move_by[k];
   while (g_key_at < g_keys.size()) {                           // while(SDL_PollEvent(&e)), :300-301
     const string& k = g_keys[g_key_at++];
     if (k == ".") return false;                                // no more events this frame
@@ -111,6 +128,10 @@ int main(int argc, char* argv[]) {
     else if (a == "--keys" && i + 1 < argc) { istringstream in(argv[++i]); string k; while (in >> k) g_keys.push_back(k); }
     else if (a == "--out" && i + 1 < argc) out = argv[++i];
     else if (a == "--obj" && i + 1 < argc) obj = argv[++i];
+    else if (a == "--move" && i + 1 < argc) {
+      if (sscanf(argv[++i], "%f,%f,%f", &g_move_by[0], &g_move_by[1], &g_move_by[2]) != 3) { fprintf(stderr, "--move DX,DY,DZ\n"); return 2; }
+      g_move = true;
+    }
     else if (a == "--copy-back") direct_out = false;           // render into device memory + blocking copy, as the reference reads back
     else if (a == "--gpus" && i + 1 < argc) {
       cfg.num_devices = atoi(argv[++i]);
@@ -130,6 +151,8 @@ int main(int argc, char* argv[]) {
   const int n = rt_scene_cornell_box(triangles.data(), 64);                   // LoadTestModel, :101
   if (n < 0) die("rt_scene_cornell_box");
   triangles.resize(n);
+  g_obj_first = triangles.size();
+  if (g_move && !obj) { fprintf(stderr, "--move needs --obj\n"); return 2; }
   if (obj) {                                                                   // load_obj + insert, :102-103
     const int m = rt_scene_load_obj(obj, nullptr, 0);
     if (m < 0) die("rt_scene_load_obj");
@@ -147,6 +170,7 @@ int main(int argc, char* argv[]) {
   SDL_Renderframe(screen);
   for (int f = 0; f < frames && !quit; ++f) {                                  // :117-138
     update();
+    if (g_move) update_scene();
     auto start = high_resolution_clock::now();
     offload_rendering(screen);
     auto stop = high_resolution_clock::now();

@@ -56,6 +56,9 @@ void launch_wave_prof(const FrameParams& P, hipStream_t stream);
 bool wave_kernel_supports(const FrameParams& P);
 int wave_blocks_per_cu(bool leave_room);
 int mesh_blocks_per_cu();
+int launch_scene_check(const float4* v, const float4* col, int n, unsigned int* out, hipStream_t stream);
+void launch_scene_refit(const float4* v, const float4* nrm, const float4* col, const int* orig, int n, float4* vm, float4* nm,
+                        float4* cm, float4* tile_box, hipStream_t stream);
 
 }  // namespace uobrt
 
@@ -85,6 +88,7 @@ struct Tuning {
   bool phase_profile = false; // UOB_RT_PHASE_PROFILE: rt_count_executed returns s_memtime shares per phase
   bool timeline = false;      // UOB_RT_TIMELINE: the wave kernel records when its waves start and end (rt_debug_wave_timeline)
   int mask_debug = 0;         // UOB_RT_MASK_DEBUG: mesh kernel, switch single tile-mask stages off (fault isolation)
+  bool tile_morton = false;   // UOB_RT_TILE_ORDER=morton: the mesh kernel's tiles in plain Morton order (tiled_order)
 };
 
 struct rt_ctx {
@@ -134,6 +138,10 @@ struct rt_ctx {
   hipEvent_t ev_go = nullptr;       // parent: "the caller's stream has reached this frame"
   hipEvent_t ev_done = nullptr;     // child: "this device's bands have been delivered"
   bool peer_ok = true;              // child: its device can copy 2-D into the destination device directly
+  // rt_update_scene_device: the latest update, enqueued on the caller's stream; later frames (any stream) wait for it
+  hipEvent_t ev_upd = nullptr;
+  bool upd_pending = false;
+  unsigned int* d_check = nullptr;  // rt_scene_check's result block (rt_scene_update.hip)
 };
 
 static int validate_config(const rt_config* c) {
@@ -183,7 +191,35 @@ static Tuning read_tuning(const rt_config& cfg) {
   t.phase_profile = getenv("UOB_RT_PHASE_PROFILE") != nullptr;
   t.timeline = getenv("UOB_RT_TIMELINE") != nullptr;
   if (const char* e = getenv("UOB_RT_MASK_DEBUG")) t.mask_debug = atoi(e);
+  if (const char* e = getenv("UOB_RT_TILE_ORDER")) t.tile_morton = !strcmp(e, "morton");
   return t;
+}
+
+// Coordinate bound: the range over which the exact culls are verified and which keeps every
+// determinant of the intersection tests below 2^126, where the v_rcp_f32 + Newton reciprocal equals IEEE
+// division bit for bit (rt_math.h rcp_exact).
+static int validate_vertices(const float* vertices4, int n) {
+  for (size_t k = 0; k < (size_t)n * 12; ++k) {
+    if ((k & 3) != 3 && !(fabsf(vertices4[k]) <= kMaxCoordinate)) {
+      set_error("vertex %zu: coordinates must be finite and |x| <= 2^16", k / 4); return RT_E_INVALID;
+    }
+  }
+  return RT_OK;
+}
+
+static void vertex_box(const float* vertices4, int n, float lo[3], float hi[3]) {
+  for (int k = 0; k < 3; ++k) { lo[k] = 3.0e38f; hi[k] = -3.0e38f; }
+  for (size_t v = 0; v < (size_t)n * 3; ++v)
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = fminf(lo[k], vertices4[4 * v + k]);
+      hi[k] = fmaxf(hi[k], vertices4[4 * v + k]);
+    }
+}
+
+static int count_shadow_casters(const float* colors4, int n) {
+  int cnt = 0;
+  for (int i = 0; i < n; ++i) cnt += (colors4[4 * i + 3] != -1.0f);
+  return cnt;
 }
 
 // Keeps the calling thread's current device unchanged across an API call (the caller may be a torch process)
@@ -207,7 +243,10 @@ static uint32_t spread3(uint32_t v) {
 // any-hit, and the closest-hit search resolves equal t by the ORIGINAL index (the reference's loop order, kernels.cl:120)
 // — so the triangles are sorted into spatially compact tiles of 64: a task's rays then meet few tiles.  Triangles whose
 // extent exceeds a quarter of the scene's (walls) come first, the rest in Morton order of their centroids.
-static int upload_tiled_scene(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n) {
+// Three parts, shared by rt_init and rt_update_scene(RT_UPDATE_REORDER): the order (tiled_order), the per-tile data for an
+// order (tile_data_host; rt_scene_update.hip's refit computes the same floats on the device) and the upload (upload_tiled).
+// Returns orig: orig[j] = original index of the triangle at tiled position j.
+static std::vector<int> tiled_order(const float* v4, int n, bool morton) {
   float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
   for (size_t v = 0; v < (size_t)n * 3; ++v)
     for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], v4[4 * v + k]); hi[k] = fmaxf(hi[k], v4[4 * v + k]); }
@@ -232,15 +271,14 @@ static int upload_tiled_scene(rt_ctx* c, const float* v4, const float* n4, const
     key[(size_t)i] = std::make_pair(code, i);
   }
   std::stable_sort(key.begin(), key.end(), [](const std::pair<uint32_t, int>& x, const std::pair<uint32_t, int>& y) { return x.first < y.first; });
-  // UOB_RT_TILE_ORDER=kd (default): the small triangles are not left in Morton order (runs of 64 along a space-filling curve
+  // UOB_RT_TILE_ORDER=kd (default, Tuning::tile_morton): the small triangles are not left in Morton order (runs of 64 along a space-filling curve
   // jump between octants: a quarter of this round's test mesh's tiles had a normal-cone chord above 0.8) but split top-down at
   // the median of the longest axis of their centroids' box, every cut on a tile boundary, until a range is one tile: compact
   // boxes, compact normal cones.  =morton keeps round 2's order (A/B).  The order is a free choice (see above).
   {
-    const char* mode = getenv("UOB_RT_TILE_ORDER");
     int nb = 0;
     while (nb < n && key[(size_t)nb].first == 0u) ++nb;                  // the large triangles, in original order
-    if (!(mode && !strcmp(mode, "morton")) && n - nb > 64) {
+    if (!morton && n - nb > 64) {
       std::vector<float> cen((size_t)n * 3);
       for (int i = 0; i < n; ++i)
         for (int k = 0; k < 3; ++k) cen[(size_t)3 * i + k] = (v4[(size_t)12 * i + k] + v4[(size_t)12 * i + 4 + k] + v4[(size_t)12 * i + 8 + k]) * (1.0f / 3.0f);
@@ -271,16 +309,18 @@ static int upload_tiled_scene(rt_ctx* c, const float* v4, const float* n4, const
       for (int j = nb; j < n; ++j) key[(size_t)j].second = idx[(size_t)(j - nb)];
     }
   }
-  const int ntiles = mesh_tiles(n);
-  std::vector<float> pv((size_t)n * 12), pn((size_t)n * 4), pc((size_t)n * 4), box((size_t)ntiles * 12);
   std::vector<int> orig((size_t)n);
+  for (int j = 0; j < n; ++j) orig[(size_t)j] = key[(size_t)j].second;
+  return orig;
+}
+
+// The tiles' data for the order orig, 12 floats per tile (rt_device.h FrameParams::tile_box), from the ORIGINAL-order vertices
+static std::vector<float> tile_data_host(const float* v4, const int* orig, int n) {
+  const int ntiles = mesh_tiles(n);
+  std::vector<float> box((size_t)ntiles * 12);
   for (int t = 0; t < ntiles; ++t) { for (int k = 0; k < 3; ++k) { box[(size_t)12 * t + k] = 3.0e38f; box[(size_t)12 * t + 4 + k] = -3.0e38f; } box[(size_t)12 * t + 3] = box[(size_t)12 * t + 7] = 0.0f; }
   for (int j = 0; j < n; ++j) {
-    const int i = key[(size_t)j].second;
-    orig[(size_t)j] = i;
-    memcpy(&pv[(size_t)12 * j], v4 + (size_t)12 * i, 48);
-    memcpy(&pn[(size_t)4 * j], n4 + (size_t)4 * i, 16);
-    memcpy(&pc[(size_t)4 * j], c4 + (size_t)4 * i, 16);
+    const int i = orig[j];
     float* b = &box[(size_t)12 * (j / 64)];
     for (int v = 0; v < 3; ++v)
       for (int k = 0; k < 3; ++k) { b[k] = fminf(b[k], v4[(size_t)12 * i + 4 * v + k]); b[4 + k] = fmaxf(b[4 + k], v4[(size_t)12 * i + 4 * v + k]); }
@@ -289,14 +329,15 @@ static int upload_tiled_scene(rt_ctx* c, const float* v4, const float* n4, const
   //   lo.w  eta   = max over the tile's triangles of max(|e1|, |e2|, |e2 - e1|) / |e1 x e2|   (inverse altitudes)
   //   hi.w  emax  = max edge length
   //   third float4: unit axis of the triangles' normals (signs aligned) | chi = max |n_T - axis|_2 (chord of the normal cone)
-  // A tile with a degenerate triangle gets chi = 4: never certified clear, always visited.
+  // A tile with a degenerate triangle gets chi = 4: never certified clear, always visited.  (rt_scene_update.hip
+  // rt_scene_refit is the same arithmetic, one lane per triangle: change both together.)
   for (int t = 0; t < ntiles; ++t) {
     const int j0 = t * 64, j1 = (j0 + 64 < n) ? j0 + 64 : n;
     double ax[3] = {0, 0, 0}, eta = 0.0, emax = 0.0;
     bool degenerate = false;
     std::vector<double> nn((size_t)(j1 - j0) * 3);
     for (int j = j0; j < j1; ++j) {
-      const float* a = &pv[(size_t)12 * j];
+      const float* a = v4 + (size_t)12 * orig[j];
       const double e1[3] = {(double)a[4] - a[0], (double)a[5] - a[1], (double)a[6] - a[2]};
       const double e2[3] = {(double)a[8] - a[0], (double)a[9] - a[1], (double)a[10] - a[2]};
       double cr[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
@@ -329,20 +370,41 @@ static int upload_tiled_scene(rt_ctx* c, const float* v4, const float* n4, const
     b[3] = (float)(eta * 1.0001); b[7] = (float)(emax * 1.0001);
     b[8] = (float)ax[0]; b[9] = (float)ax[1]; b[10] = (float)ax[2]; b[11] = (float)(chi * 1.0001 + 1e-6);
   }
+  return box;
+}
+
+// The tiled copy into the context's buffers (allocated on first use), on c->stream; blocking
+static int upload_tiled(rt_ctx* c, const float* v4, const float* n4, const float* c4, const std::vector<int>& orig,
+                        const std::vector<float>& box) {
+  const int n = c->n, ntiles = mesh_tiles(n);
+  std::vector<float> pv((size_t)n * 12), pn((size_t)n * 4), pc((size_t)n * 4);
+  for (int j = 0; j < n; ++j) {
+    const int i = orig[(size_t)j];
+    memcpy(&pv[(size_t)12 * j], v4 + (size_t)12 * i, 48);
+    memcpy(&pn[(size_t)4 * j], n4 + (size_t)4 * i, 16);
+    memcpy(&pc[(size_t)4 * j], c4 + (size_t)4 * i, 16);
+  }
   const size_t nb = (size_t)n * sizeof(float4);
-  if (hipMalloc(&c->d_verts_m, 3 * nb) != hipSuccess || hipMalloc(&c->d_normals_m, nb) != hipSuccess ||
-      hipMalloc(&c->d_colors_m, nb) != hipSuccess || hipMalloc(&c->d_orig, (size_t)n * sizeof(int)) != hipSuccess ||
-      hipMalloc(&c->d_tile_box, (size_t)ntiles * 3 * sizeof(float4)) != hipSuccess) {
+  if (!c->d_verts_m &&
+      (hipMalloc(&c->d_verts_m, 3 * nb) != hipSuccess || hipMalloc(&c->d_normals_m, nb) != hipSuccess ||
+       hipMalloc(&c->d_colors_m, nb) != hipSuccess || hipMalloc(&c->d_orig, (size_t)n * sizeof(int)) != hipSuccess ||
+       hipMalloc(&c->d_tile_box, (size_t)ntiles * 3 * sizeof(float4)) != hipSuccess)) {
     set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
   }
-  if (hipMemcpy(c->d_verts_m, pv.data(), 3 * nb, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->d_normals_m, pn.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->d_colors_m, pc.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->d_orig, orig.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->d_tile_box, box.data(), (size_t)ntiles * 3 * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipMemcpyAsync(c->d_verts_m, pv.data(), 3 * nb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(c->d_normals_m, pn.data(), nb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(c->d_colors_m, pc.data(), nb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(c->d_orig, orig.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(c->d_tile_box, box.data(), (size_t)ntiles * 3 * sizeof(float4), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) {
     set_error("scene upload failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
   }
   return RT_OK;
+}
+
+static int upload_tiled_scene(rt_ctx* c, const float* v4, const float* n4, const float* c4) {
+  const std::vector<int> orig = tiled_order(v4, c->n, c->tune.tile_morton);
+  return upload_tiled(c, v4, n4, c4, orig, tile_data_host(v4, orig.data(), c->n));
 }
 
 extern "C" {
@@ -371,6 +433,20 @@ int32_t rt_config_owned_rows(const rt_config* c) {
   int rows = 0;
   for (int y = 0; y < c->height; ++y) rows += ((y / c->band_rows) % c->band_count) == c->band_index;
   return rows;
+}
+
+// Every surface point lies on a triangle or a sphere: their bounding box, from the vertices' (the world grid of the
+// mesh kernel's shadow-ray tile masks spans it: fill_params)
+static void set_scene_box(rt_ctx* c, const float vlo[3], const float vhi[3]) {
+  for (int k = 0; k < 3; ++k) { c->box_lo[k] = vlo[k]; c->box_hi[k] = vhi[k]; }
+  const rt_config* cfg = &c->cfg;
+  for (int i = 0; i < cfg->num_spheres; ++i) {
+    const float r = sqrtf(fmaxf(cfg->spheres[i].radius_sq, 0.0f)) * 1.0001f + 1e-6f;
+    for (int k = 0; k < 3; ++k) {
+      c->box_lo[k] = fminf(c->box_lo[k], cfg->spheres[i].center[k] - r);
+      c->box_hi[k] = fmaxf(c->box_hi[k], cfg->spheres[i].center[k] + r);
+    }
+  }
 }
 
 static int init_parent(const rt_config* cfg, const float* vertices4, const float* normals4, const float* colors4,
@@ -437,14 +513,8 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
   int rc = validate_config(cfg);
   if (rc != RT_OK) return rc;
   if (n < 0 || (n > 0 && (!vertices4 || !normals4 || !colors4))) { set_error("scene arrays missing"); return RT_E_INVALID; }
-  // Coordinate bound: the range over which the exact culls are verified and which keeps every
-  // determinant of the intersection tests below 2^126, where the v_rcp_f32 + Newton reciprocal equals IEEE
-  // division bit for bit (rt_math.h rcp_exact).
-  for (size_t k = 0; k < (size_t)n * 12; ++k) {
-    if ((k & 3) != 3 && !(fabsf(vertices4[k]) <= kMaxCoordinate)) {
-      set_error("vertex %zu: coordinates must be finite and |x| <= 2^16", k / 4); return RT_E_INVALID;
-    }
-  }
+  rc = validate_vertices(vertices4, n);
+  if (rc != RT_OK) return rc;
   if (n > 4000000) { set_error("triangle list of %d exceeds the supported maximum of 4000000", n); return RT_E_UNSUPPORTED; }
   DeviceGuard guard;
   if (cfg->num_devices > 1) return init_parent(cfg, vertices4, normals4, colors4, n, out_ctx);
@@ -488,20 +558,9 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
         hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
       set_error("stream/event creation failed"); return fail(RT_E_DEVICE);
     }
-    // every surface point lies on a triangle or a sphere: their bounding box (the world grid spans it)
-    for (int k = 0; k < 3; ++k) { c->box_lo[k] = 3.0e38f; c->box_hi[k] = -3.0e38f; }
-    for (size_t v = 0; v < (size_t)n * 3; ++v)
-      for (int k = 0; k < 3; ++k) {
-        c->box_lo[k] = fminf(c->box_lo[k], vertices4[4 * v + k]);
-        c->box_hi[k] = fmaxf(c->box_hi[k], vertices4[4 * v + k]);
-      }
-    for (int i = 0; i < cfg->num_spheres; ++i) {
-      const float r = sqrtf(fmaxf(cfg->spheres[i].radius_sq, 0.0f)) * 1.0001f + 1e-6f;
-      for (int k = 0; k < 3; ++k) {
-        c->box_lo[k] = fminf(c->box_lo[k], cfg->spheres[i].center[k] - r);
-        c->box_hi[k] = fmaxf(c->box_hi[k], cfg->spheres[i].center[k] + r);
-      }
-    }
+    float lo[3], hi[3];
+    vertex_box(vertices4, n, lo, hi);
+    set_scene_box(c, lo, hi);
   }
   {   // wave kernel: lists of last frame's expensive jobs (sized for the smallest job, one 64-ray task)
     const int aa = cfg->aa_x * cfg->aa_y;
@@ -541,10 +600,9 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
       set_error("sphere table upload failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_DEVICE);
     }
   }
-  c->n_shadow = 0;
-  for (int i = 0; i < n; ++i) c->n_shadow += (colors4[4 * i + 3] != -1.0f);
+  c->n_shadow = count_shadow_casters(colors4, n);
   if (n > 64 && !(cfg->flags & RT_FLAG_GENERIC_KERNEL)) {
-    rc = upload_tiled_scene(c, vertices4, normals4, colors4, n);
+    rc = upload_tiled_scene(c, vertices4, normals4, colors4);
     if (rc != RT_OK) return fail(rc);
     if (!c->tune.plain_order) {
       const size_t jobs = (size_t)((cfg->width + 15) / 16) * (size_t)((c->owned_rows + 15) / 16);
@@ -676,6 +734,11 @@ static void fill_params(const rt_ctx* c, const float rot[12], const float cam[3]
   }
 }
 
+// Frames and diagnostics read the scene that the context's latest rt_update_scene_device left, on whichever stream they run
+static hipError_t wait_scene(const rt_ctx* c, hipStream_t s) {
+  return c->upd_pending ? hipStreamWaitEvent(s, c->ev_upd, 0) : hipSuccess;
+}
+
 // The mesh kernel works on the reordered copy of the scene (upload_tiled_scene)
 static void use_tiled_scene(const rt_ctx* c, FrameParams* P) {
   P->verts = c->d_verts_m; P->normals = c->d_normals_m; P->colors = c->d_colors_m;
@@ -702,6 +765,7 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
   HIP_TRY(hipSetDevice(c->device));
   // one frame of a context at a time: the queue heads, the expensive-job lists and the tile masks are shared
   if (c->timed && stream != c->last_stream) HIP_TRY(hipStreamWaitEvent(stream, c->ev1, 0));
+  HIP_TRY(wait_scene(c, stream));          // before ev0: rt_last_kernel_ms times the frame's kernels only
   HIP_TRY(hipEventRecord(c->ev0, stream));
   const bool wave_paths = !(c->cfg.flags & RT_FLAG_GENERIC_KERNEL);
   if (wave_paths && wave_kernel_supports(P) && (P.aa_x * P.aa_y <= 64 || !(c->cfg.flags & RT_FLAG_NO_CULL))) {
@@ -752,6 +816,185 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
   c->last_stream = stream;
   return RT_OK;
 }
+
+// ---- scene updates (rt_update_scene / rt_update_scene_device) ----------------------------------------------
+// The tiling of rt_init is kept: tile membership is a free choice (the closest hit resolves ties by the original index,
+// d_orig), so only the tiles' data are recomputed for the new vertices (rt_scene_update.hip rt_scene_refit), unless the
+// caller asks for the tiles to be sorted again (RT_UPDATE_REORDER: the rt_init path on the host).
+
+// An update enqueued on `s` first waits for everything that may still read the buffers it overwrites: the context's
+// previous frame (ev1, on whichever stream it ran) and its previous update
+static int update_begin(rt_ctx* c, hipStream_t s) {
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->timed) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
+  HIP_TRY(wait_scene(c, s));
+  return RT_OK;
+}
+
+// What the checks of a new scene derive from it, before any buffer is touched
+struct SceneSummary {
+  int n_shadow = 0;
+  float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // the vertices' box
+};
+
+static void update_state(rt_ctx* c, const SceneSummary& sum) {
+  c->n_shadow = sum.n_shadow;
+  if (c->d_screen_masks) set_scene_box(c, sum.lo, sum.hi);
+}
+
+// Host arrays (validated) into one single-device context; blocking
+static int update_host_one(rt_ctx* c, const float* v4, const float* n4, const float* c4, uint32_t flags, const SceneSummary& sum) {
+  const int n = c->n;
+  int rc = update_begin(c, c->stream);
+  if (rc != RT_OK) return rc;
+  const size_t nb = (size_t)n * sizeof(float4);
+  HIP_TRY(hipMemcpyAsync(c->d_verts, v4, 3 * nb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_normals, n4, nb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->d_colors, c4, nb, hipMemcpyHostToDevice, c->stream));
+  if (c->d_verts_m) {
+    if (flags & RT_UPDATE_REORDER) {
+      const std::vector<int> orig = tiled_order(v4, n, c->tune.tile_morton);
+      rc = upload_tiled(c, v4, n4, c4, orig, tile_data_host(v4, orig.data(), n));
+      if (rc != RT_OK) return rc;
+    } else {
+      launch_scene_refit(c->d_verts, c->d_normals, c->d_colors, c->d_orig, n, c->d_verts_m, c->d_normals_m, c->d_colors_m,
+                         c->d_tile_box, c->stream);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  update_state(c, sum);
+  return RT_OK;
+}
+
+// Device arrays on device src_dev (validated) into one single-device context, enqueued on `s` (a stream of c->device)
+static int update_device_one(rt_ctx* c, const void* dv, const void* dn, const void* dc, int src_dev, hipStream_t s,
+                             const SceneSummary& sum) {
+  const int n = c->n;
+  int rc = update_begin(c, s);
+  if (rc != RT_OK) return rc;
+  if (!c->ev_upd) HIP_TRY(hipEventCreateWithFlags(&c->ev_upd, hipEventDisableTiming));
+  const size_t nb = (size_t)n * sizeof(float4);
+  if (src_dev == c->device) {
+    HIP_TRY(hipMemcpyAsync(c->d_verts, dv, 3 * nb, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->d_normals, dn, nb, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->d_colors, dc, nb, hipMemcpyDeviceToDevice, s));
+  } else {                                   // the other devices of a multi-device context: by peer copy, as the bands
+    HIP_TRY(hipMemcpyPeerAsync(c->d_verts, c->device, dv, src_dev, 3 * nb, s));
+    HIP_TRY(hipMemcpyPeerAsync(c->d_normals, c->device, dn, src_dev, nb, s));
+    HIP_TRY(hipMemcpyPeerAsync(c->d_colors, c->device, dc, src_dev, nb, s));
+  }
+  if (c->d_verts_m) {
+    launch_scene_refit(c->d_verts, c->d_normals, c->d_colors, c->d_orig, n, c->d_verts_m, c->d_normals_m, c->d_colors_m,
+                       c->d_tile_box, s);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(c->ev_upd, s));
+  c->upd_pending = true;
+  update_state(c, sum);
+  return RT_OK;
+}
+
+static int check_update_args(const rt_ctx* c, const void* v, const void* nr, const void* col, int32_t n, uint32_t flags) {
+  if (!c) { set_error("NULL context"); return RT_E_INVALID; }
+  if (n != c->n) { set_error("rt_update_scene: n = %d, but the context holds %d triangles", n, c->n); return RT_E_INVALID; }
+  if (n > 0 && (!v || !nr || !col)) { set_error("scene arrays missing"); return RT_E_INVALID; }
+  if (flags & ~RT_UPDATE_REORDER) { set_error("rt_update_scene: unknown flags 0x%x", flags); return RT_E_INVALID; }
+  return RT_OK;
+}
+
+static float key_to_float(unsigned int k) {   // inverse of rt_scene_update.hip order_key
+  const unsigned int u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+
+extern "C" {
+
+int rt_update_scene(rt_ctx* c, const float* vertices4, const float* normals4, const float* colors4, int32_t n, uint32_t flags) {
+  int rc = check_update_args(c, vertices4, normals4, colors4, n, flags);
+  if (rc != RT_OK) return rc;
+  rc = validate_vertices(vertices4, n);        // once, before any device is touched
+  if (rc != RT_OK) return rc;
+  if (n == 0) return RT_OK;
+  SceneSummary sum;
+  sum.n_shadow = count_shadow_casters(colors4, n);
+  vertex_box(vertices4, n, sum.lo, sum.hi);
+  DeviceGuard guard;
+  if (c->kids.empty()) return update_host_one(c, vertices4, normals4, colors4, flags, sum);
+  for (rt_ctx* k : c->kids) {
+    rc = update_host_one(k, vertices4, normals4, colors4, flags, sum);
+    if (rc != RT_OK) return rc;
+  }
+  return RT_OK;
+}
+
+int rt_update_scene_device(rt_ctx* c, const void* d_vertices4, const void* d_normals4, const void* d_colors4, int32_t n,
+                           uint32_t flags, void* hip_stream) {
+  int rc = check_update_args(c, d_vertices4, d_normals4, d_colors4, n, flags);
+  if (rc != RT_OK) return rc;
+  if (n == 0) return RT_OK;
+  DeviceGuard guard;
+  const hipStream_t s = (hipStream_t)hip_stream;
+  // first pass: check the bound and reduce n_shadow and the box; the live buffers stay untouched until it has passed
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->d_check) HIP_TRY(hipMalloc(&c->d_check, 8 * sizeof(unsigned int)));
+  if (launch_scene_check((const float4*)d_vertices4, (const float4*)d_colors4, n, c->d_check, s) != 0) {
+    set_error("scene check launch failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
+  }
+  unsigned int res[8];
+  HIP_TRY(hipMemcpyAsync(res, c->d_check, sizeof res, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (res[0] != 0u) { set_error("%u vertex coordinate(s) not finite or |x| > 2^16", res[0]); return RT_E_INVALID; }
+  SceneSummary sum;
+  sum.n_shadow = (int)res[1];
+  for (int k = 0; k < 3; ++k) { sum.lo[k] = key_to_float(res[2 + k]); sum.hi[k] = key_to_float(res[5 + k]); }
+  if (flags & RT_UPDATE_REORDER) {             // the tiles are sorted on the host: stage the scene through it
+    std::vector<float> v((size_t)n * 12), nr((size_t)n * 4), col((size_t)n * 4);
+    HIP_TRY(hipMemcpyAsync(v.data(), d_vertices4, v.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(nr.data(), d_normals4, nr.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(col.data(), d_colors4, col.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (c->kids.empty()) return update_host_one(c, v.data(), nr.data(), col.data(), flags, sum);
+    for (rt_ctx* k : c->kids) {
+      rc = update_host_one(k, v.data(), nr.data(), col.data(), flags, sum);
+      if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+  }
+  if (c->kids.empty()) return update_device_one(c, d_vertices4, d_normals4, d_colors4, c->device, s, sum);
+  // several devices: every child copies from devices[0] on its own stream after the caller's earlier work, and the
+  // caller's stream passes the update only when every child has its copy
+  HIP_TRY(hipEventRecord(c->ev_go, s));
+  for (rt_ctx* k : c->kids) {
+    HIP_TRY(hipSetDevice(k->device));
+    HIP_TRY(hipStreamWaitEvent(k->stream, c->ev_go, 0));
+    rc = update_device_one(k, d_vertices4, d_normals4, d_colors4, c->device, k->stream, sum);
+    if (rc != RT_OK) return rc;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  for (rt_ctx* k : c->kids) HIP_TRY(hipStreamWaitEvent(s, k->ev_upd, 0));
+  return RT_OK;
+}
+
+int rt_debug_tile_data(rt_ctx* c, int32_t* orig, float* tiles, int32_t cap_tiles) {
+  if (!c || cap_tiles < 0 || (cap_tiles > 0 && (!orig || !tiles))) { set_error("NULL argument"); return RT_E_INVALID; }
+  if (!c->kids.empty()) c = c->kids[0];
+  if (!c->d_tile_box) { set_error("rt_debug_tile_data: this context keeps no tiled copy of the scene"); return RT_E_UNSUPPORTED; }
+  const int ntiles = mesh_tiles(c->n);
+  if (cap_tiles == 0) return ntiles;
+  if (cap_tiles < ntiles) { set_error("rt_debug_tile_data: room for %d tiles, %d needed", cap_tiles, ntiles); return RT_E_INVALID; }
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(wait_scene(c, c->stream));
+  HIP_TRY(hipMemcpyAsync(orig, c->d_orig, (size_t)c->n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(tiles, c->d_tile_box, (size_t)ntiles * 3 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return ntiles;
+}
+
+}  // extern "C"
 
 // ---- several devices --------------------------------------------------------------------------------------
 // Child k of a parent with N children owns the bands k, k+N, ... of `dbr` rows; its stripe holds them packed.
@@ -997,6 +1240,7 @@ int rt_count_work(rt_ctx* c, const float rot[12], const float cam[3], const floa
   fill_params(c, rot, cam, light, focal, &P);
   P.counters = c->d_counters;
   HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(wait_scene(c, c->stream));
   HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt_work), c->stream));
   launch_generic(P, true, c->stream);
   HIP_TRY(hipGetLastError());
@@ -1034,6 +1278,7 @@ int rt_count_executed(rt_ctx* c, const float rot[12], const float cam[3], const 
   P.counters = c->d_counters;
   HIP_TRY(hipSetDevice(c->device));
   if (c->timed) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev1, 0));
+  HIP_TRY(wait_scene(c, c->stream));
   HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt_work), c->stream));
   if (mesh) { use_tiled_scene(c, &P); launch_stage_records(P, c->stream); launch_mesh(P, true, c->tune.phase_profile, c->stream, nullptr, nullptr, nullptr); }
   else if (c->tune.phase_profile) launch_wave_prof(P, c->stream);   // diagnostic: s_memtime per phase
@@ -1095,6 +1340,7 @@ int rt_debug_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float
   };
   if (rc == RT_OK) {
     if (c->timed) ok(hipStreamWaitEvent(c->stream, c->ev1, 0), "hipStreamWaitEvent");
+    ok(wait_scene(c, c->stream), "hipStreamWaitEvent");
     ok(hipMemcpyAsync(d_rays, rays6, (size_t)nray * 24, hipMemcpyHostToDevice, c->stream), "ray upload");
     if (radius_sq) ok(hipMemcpyAsync(d_r2, radius_sq, (size_t)nray * 4, hipMemcpyHostToDevice, c->stream), "ray upload");
     if (d_out) ok(hipMemsetAsync(d_out, 0, (size_t)nray * 40, c->stream), "hipMemsetAsync");
@@ -1194,6 +1440,7 @@ void rt_destroy(rt_ctx* c) {
   if (c->ev_join) hipEventDestroy(c->ev_join);
   if (c->ev_go) hipEventDestroy(c->ev_go);
   if (c->ev_done) hipEventDestroy(c->ev_done);
+  if (c->ev_upd) hipEventDestroy(c->ev_upd);
   hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);
   hipFree(c->d_argb); hipFree(c->d_rgb); hipFree(c->d_counters); hipFree(c->d_records); hipFree(c->d_jobctr);
   hipFree(c->d_screen_masks); hipFree(c->d_world_masks); hipFree(c->d_world_occ);
@@ -1201,6 +1448,7 @@ void rt_destroy(rt_ctx* c) {
   hipFree(c->d_heavy[0]); hipFree(c->d_heavy[1]); hipFree(c->d_heavy_flags); hipFree(c->d_timeline);
   hipFree(c->d_mesh_cost); hipFree(c->d_mesh_order); hipFree(c->d_spheres);
   hipFree(c->d_verts_m); hipFree(c->d_normals_m); hipFree(c->d_colors_m); hipFree(c->d_orig); hipFree(c->d_tile_box);
+  hipFree(c->d_check);
   delete c;
 }
 

@@ -27,7 +27,7 @@ EXPORTS = (
     "rt_render_device", "rt_count_work", "rt_count_executed", "rt_last_kernel_ms", "rt_destroy", "rt_scene_cornell_box",
     "rt_scene_load_obj", "rt_scene_load_obj_ex", "rt_triangle_compute_normal", "rt_scene_pack", "rt_rotation_matrix",
     "rt_selftest_rcp", "rt_selftest_normalize", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_register_output", "rt_unregister_output",
-    "rt_debug_band_copy_plan",
+    "rt_debug_band_copy_plan", "rt_update_scene", "rt_update_scene_device", "rt_debug_tile_data",
 )
 
 _lib = None
@@ -53,6 +53,9 @@ def lib():
         L.rt_config_default.restype = None
         L.rt_config_owned_rows.argtypes = [C.POINTER(abi.RtConfig)]
         L.rt_init.argtypes = [C.POINTER(abi.RtConfig), fp, fp, fp, C.c_int32, C.POINTER(vp)]
+        L.rt_update_scene.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_uint32]
+        L.rt_update_scene_device.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint32, vp]
+        L.rt_debug_tile_data.argtypes = [vp, C.POINTER(C.c_int32), fp, C.c_int32]
         L.rt_render.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(C.c_uint32), fp]
         L.rt_render_device.argtypes = [vp, fp, fp, fp, C.c_float, vp, vp, vp]
         L.rt_count_work.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(abi.RtWork)]
@@ -167,6 +170,20 @@ class Scene:
         aos[list(indices), 4, :] = np.asarray(rgba, np.float32)
         return Scene(aos)
 
+    def transformed(self, indices, matrix, offset=(0.0, 0.0, 0.0)):
+        """A new Scene whose triangles `indices` have every vertex v replaced by matrix @ v + offset (float32, the products
+        summed left to right) and their normals recomputed by rt_triangle_compute_normal (ComputeNormal, TestModelH.h:26)."""
+        m = np.asarray(matrix, np.float32).reshape(3, 3)
+        o = np.asarray(offset, np.float32).reshape(3)
+        aos = self.aos.copy()
+        idx = np.arange(len(self))[indices] if not isinstance(indices, (list, tuple)) else np.asarray(indices, np.int64)
+        v = aos[idx, 0:3, 0:3]
+        aos[idx, 0:3, 0:3] = ((v[..., 0:1] * m[:, 0] + v[..., 1:2] * m[:, 1]) + v[..., 2:3] * m[:, 2]) + o
+        tris = (abi.RtTriangle * len(self)).from_buffer(aos)
+        for i in idx:
+            lib().rt_triangle_compute_normal(C.byref(tris[int(i)]))
+        return Scene(aos)
+
     def packed(self):
         """The three float4 arrays uploaded at skeleton.cpp:474-496."""
         n = len(self)
@@ -192,6 +209,29 @@ class RayTracer:
         self.width = cfg.width
         self.n_triangles = len(scene)
         self.rows = lib().rt_config_owned_rows(C.byref(cfg))
+
+    def update_scene(self, scene, reorder=False):
+        """Replace the context's triangles (same count) between frames (rt_update_scene): refit the mesh kernel's tiles on
+        the device, or sort them again on the host with reorder=True."""
+        v, nr, c = scene.packed()
+        _check(lib().rt_update_scene(self._h, _fp(v), _fp(nr), _fp(c), len(scene),
+                                     abi.RT_UPDATE_REORDER if reorder else 0))
+        self.scene = scene
+        self._keep = (v, nr, c)
+
+    def update_scene_device(self, v_ptr, n_ptr, c_ptr, n, stream=None, reorder=False):
+        """The same from device memory (raw pointers, e.g. torch .data_ptr() of float32 [3n,4] / [n,4] / [n,4]), enqueued
+        on `stream` (rt_update_scene_device).  The source buffers must stay unchanged until the stream has passed it."""
+        _check(lib().rt_update_scene_device(self._h, C.c_void_p(v_ptr), C.c_void_p(n_ptr), C.c_void_p(c_ptr), n,
+                                            abi.RT_UPDATE_REORDER if reorder else 0, C.c_void_p(stream or 0)))
+
+    def tile_data(self):
+        """Mesh kernel: (orig int32 [n], tiles float32 [ntiles, 12]) — the tiled order and per-tile data (rt_debug_tile_data)."""
+        nt = _check(lib().rt_debug_tile_data(self._h, None, None, 0))
+        orig = np.zeros(self.n_triangles, np.int32)
+        tiles = np.zeros((nt, 12), np.float32)
+        _check(lib().rt_debug_tile_data(self._h, orig.ctypes.data_as(C.POINTER(C.c_int32)), _fp(tiles), nt))
+        return orig, tiles
 
     def close(self):
         if getattr(self, "_h", None):
