@@ -178,6 +178,26 @@ enum { RT_TRACE_IN_SHADOW = 0, RT_TRACE_CLOSEST_HIT = 1 };
 int rt_debug_trace_rays(rt_ctx* ctx, int32_t what, const float* rays6, const float* radius_sq, int64_t nray,
                         int32_t* out_tri, float* out10);
 
+/* Ray queries (picking, line of sight, probes) on the context's scene as its latest update left it: the same `what` modes,
+ * arrays and results as rt_debug_trace_rays (bit-identical), on a tile-culled kernel (rt_ray_query.hip).
+ * rays6 = float32 [nray][6] (start, direction), 4-byte aligned; out10 is nullable for RT_TRACE_CLOSEST_HIT (written with
+ * zeros on a miss) and not written for RT_TRACE_IN_SHADOW.  A NULL ctx / rays6 / out_tri, an unknown mode, nray < 0 and a
+ * missing radius_sq in RT_TRACE_IN_SHADOW are RT_E_INVALID; nray == 0 is a no-op.  Queries write nothing a frame reads:
+ * frames do not wait for them, and they do not wait for frames; the context's next query and scene update (and rt_destroy)
+ * wait for them.  A multi-device context runs its queries on devices[0].
+ * Host arrays, blocking.                                                                                                 */
+int rt_trace_rays(rt_ctx* ctx, int32_t what, const float* rays6, const float* radius_sq, int64_t nray,
+                  int32_t* out_tri, float* out10);
+/* Device memory on the context's device (devices[0] of a multi-device context), enqueued on hip_stream (NULL = default
+ * stream) after the caller's earlier work; returns without synchronising.                                                */
+int rt_trace_rays_device(rt_ctx* ctx, int32_t what, const void* d_rays6, const void* d_radius_sq, int64_t nray,
+                         void* d_out_tri, void* d_out10, void* hip_stream);
+/* Diagnostic: work counters of the context's most recent rt_trace_rays / rt_trace_rays_device (synchronises it; zeros
+ * before the first).  out[0] rays, out[1] 64-ray waves, out[2] tiles of the scene (0 without a tiled copy), out[3] (wave,
+ * tile) pairs left by the bundle test, out[4] (wave, tile) pairs whose triangles were tested, out[5] lane-level triangle
+ * tests, out[6] rays traced without culling (outside the certificates' domain; every ray without a tiled copy), out[7] 0. */
+int rt_debug_trace_stats(rt_ctx* ctx, uint64_t out[8]);
+
 /* Diagnostic, mesh kernel (n > 64): the cost of every 16x16-pixel block of the most recent frame in s_memtime ticks
  * (shader cycles) — the scheduling state "last frame's expensive blocks first" is built from it.  Row-major over
  * ceil(owned_rows/16) x ceil(width/16) blocks; writes min(count, cap) values, returns the block count, or

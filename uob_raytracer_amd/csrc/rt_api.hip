@@ -59,6 +59,9 @@ int mesh_blocks_per_cu();
 int launch_scene_check(const float4* v, const float4* col, int n, unsigned int* out, hipStream_t stream);
 void launch_scene_refit(const float4* v, const float4* nrm, const float4* col, const int* orig, int n, float4* vm, float4* nm,
                         float4* cm, float4* tile_box, hipStream_t stream);
+int query_stats_words();
+void launch_query(const FrameParams& P, bool tiled, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
+                  float* d_out10, unsigned long long* stats, int cus, hipStream_t stream);
 
 }  // namespace uobrt
 
@@ -142,6 +145,15 @@ struct rt_ctx {
   hipEvent_t ev_upd = nullptr;
   bool upd_pending = false;
   unsigned int* d_check = nullptr;  // rt_scene_check's result block (rt_scene_update.hip)
+  // ray queries (rt_trace_rays_device, rt_ray_query.hip): they read only the scene, so frames need not wait for them; later
+  // queries (they share the counters and staging below) and scene updates do, through ev_query
+  hipEvent_t ev_query = nullptr;
+  bool query_pending = false;
+  unsigned long long* d_qstats = nullptr;   // the latest query's work counters (+ the tiled kernel's queue head)
+  int query_tiles = 0;                      // tiles of the latest query's scene (0: no tiled copy)
+  float4* d_qrecords = nullptr;             // no tiled copy, beyond one LDS stage: the queries' own records (d_records is the frames')
+  char* d_qio = nullptr;                    // rt_trace_rays: device copies of the caller's host arrays
+  size_t qio_bytes = 0;
 };
 
 static int validate_config(const rt_config* c) {
@@ -823,10 +835,11 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
 // caller asks for the tiles to be sorted again (RT_UPDATE_REORDER: the rt_init path on the host).
 
 // An update enqueued on `s` first waits for everything that may still read the buffers it overwrites: the context's
-// previous frame (ev1, on whichever stream it ran) and its previous update
+// previous frame (ev1, on whichever stream it ran), its latest ray query (ev_query) and its previous update
 static int update_begin(rt_ctx* c, hipStream_t s) {
   HIP_TRY(hipSetDevice(c->device));
   if (c->timed) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
+  if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));    // ray queries still reading the scene
   HIP_TRY(wait_scene(c, s));
   return RT_OK;
 }
@@ -1357,6 +1370,95 @@ int rt_debug_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float
   return rc;
 }
 
+// ---- ray queries (rt_trace_rays / rt_trace_rays_device, rt_ray_query.hip) ---------------------------------------------
+static int check_query_args(const rt_ctx* c, int32_t what, const void* rays6, const void* radius_sq, int64_t nray,
+                            const void* out_tri, const char* fn) {
+  if (!c || !rays6 || !out_tri) { set_error("%s: NULL argument", fn); return RT_E_INVALID; }
+  if (what != RT_TRACE_IN_SHADOW && what != RT_TRACE_CLOSEST_HIT) { set_error("%s: unknown mode %d", fn, what); return RT_E_INVALID; }
+  if (nray < 0 || nray > (int64_t(1) << 36)) { set_error("%s: nray = %lld outside [0, 2^36]", fn, (long long)nray); return RT_E_INVALID; }
+  if (what == RT_TRACE_IN_SHADOW && !radius_sq) { set_error("%s: radius_sq missing", fn); return RT_E_INVALID; }
+  return RT_OK;
+}
+
+// One query of a single-device context on stream s (device buffers of c->device); nray > 0, arguments checked
+static int enqueue_query(rt_ctx* c, int32_t what, const float* d_rays, const float* d_r2, long nray, int* d_tri, float* d_out10,
+                         hipStream_t s) {
+  HIP_TRY(hipSetDevice(c->device));
+  const bool tiled = c->d_verts_m != nullptr;
+  const bool records = !tiled && generic_needs_records(c->n);
+  const size_t stats_bytes = (size_t)query_stats_words() * sizeof(unsigned long long);
+  if (!c->ev_query) HIP_TRY(hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
+  if ((!c->d_qstats && hipMalloc(&c->d_qstats, stats_bytes) != hipSuccess) ||
+      (records && !c->d_qrecords && hipMalloc(&c->d_qrecords, (size_t)c->n * kRecordsPerTriangle * sizeof(float4)) != hipSuccess)) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
+  }
+  const float zero3[3] = {0.f, 0.f, 0.f}, ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  FrameParams P;
+  fill_params(c, ident, zero3, zero3, 1.0f, &P);
+  if (tiled) use_tiled_scene(c, &P);
+  P.records = records ? c->d_qrecords : nullptr;
+  HIP_TRY(wait_scene(c, s));
+  if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));
+  HIP_TRY(hipMemsetAsync(c->d_qstats, 0, stats_bytes, s));
+  if (records) launch_stage_records(P, s);
+  launch_query(P, tiled, what, d_rays, d_r2, nray, d_tri, what == RT_TRACE_CLOSEST_HIT ? d_out10 : nullptr, c->d_qstats, c->cus, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev_query, s));
+  c->query_pending = true;
+  c->query_tiles = tiled ? mesh_tiles(c->n) : 0;
+  return RT_OK;
+}
+
+int rt_trace_rays_device(rt_ctx* c, int32_t what, const void* d_rays6, const void* d_radius_sq, int64_t nray, void* d_out_tri,
+                         void* d_out10, void* hip_stream) {
+  const int rc = check_query_args(c, what, d_rays6, d_radius_sq, nray, d_out_tri, "rt_trace_rays_device");
+  if (rc != RT_OK || nray == 0) return rc;
+  if (!c->kids.empty()) c = c->kids[0];
+  DeviceGuard guard;
+  return enqueue_query(c, what, (const float*)d_rays6, (const float*)d_radius_sq, (long)nray, (int*)d_out_tri, (float*)d_out10,
+                       (hipStream_t)hip_stream);
+}
+
+int rt_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float* radius_sq, int64_t nray, int32_t* out_tri, float* out10) {
+  int rc = check_query_args(c, what, rays6, radius_sq, nray, out_tri, "rt_trace_rays");
+  if (rc != RT_OK || nray == 0) return rc;
+  if (!c->kids.empty()) c = c->kids[0];
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  const bool shadow = what == RT_TRACE_IN_SHADOW, want10 = !shadow && out10;
+  const size_t n = (size_t)nray;
+  const size_t o_r2 = n * 24, o_tri = o_r2 + (shadow ? n * 4 : 0), o_out = o_tri + n * 4, bytes = o_out + (want10 ? n * 40 : 0);
+  if (bytes > c->qio_bytes) {                 // (only this blocking entry uses the buffer: nothing can still be reading it)
+    hipFree(c->d_qio);
+    c->d_qio = nullptr; c->qio_bytes = 0;
+    if (hipMalloc(&c->d_qio, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
+    c->qio_bytes = bytes;
+  }
+  char* const d = c->d_qio;
+  HIP_TRY(hipMemcpyAsync(d, rays6, n * 24, hipMemcpyHostToDevice, c->stream));
+  if (shadow) HIP_TRY(hipMemcpyAsync(d + o_r2, radius_sq, n * 4, hipMemcpyHostToDevice, c->stream));
+  rc = enqueue_query(c, what, (const float*)d, shadow ? (const float*)(d + o_r2) : nullptr, (long)nray, (int*)(d + o_tri),
+                     want10 ? (float*)(d + o_out) : nullptr, c->stream);
+  if (rc != RT_OK) { hipStreamSynchronize(c->stream); return rc; }
+  HIP_TRY(hipMemcpyAsync(out_tri, d + o_tri, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (want10) HIP_TRY(hipMemcpyAsync(out10, d + o_out, n * 40, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_debug_trace_stats(rt_ctx* c, uint64_t out[8]) {
+  if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
+  memset(out, 0, 8 * sizeof(uint64_t));
+  if (!c->kids.empty()) c = c->kids[0];
+  if (!c->query_pending) return RT_OK;
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->ev_query));
+  HIP_TRY(hipMemcpy(out, c->d_qstats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  out[2] = (uint64_t)c->query_tiles;
+  return RT_OK;
+}
+
 int rt_debug_band_copy_plan(int32_t num_devices, int32_t k, int32_t device_band_rows, int32_t width, int32_t height,
                             int32_t elem_bytes, int32_t dev_to_dev, int32_t peer_ok, int32_t same_device,
                             rt_band_copy* out, int32_t cap) {
@@ -1441,6 +1543,8 @@ void rt_destroy(rt_ctx* c) {
   if (c->ev_go) hipEventDestroy(c->ev_go);
   if (c->ev_done) hipEventDestroy(c->ev_done);
   if (c->ev_upd) hipEventDestroy(c->ev_upd);
+  if (c->ev_query) { hipEventSynchronize(c->ev_query); hipEventDestroy(c->ev_query); }
+  hipFree(c->d_qstats); hipFree(c->d_qrecords); hipFree(c->d_qio);
   hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);
   hipFree(c->d_argb); hipFree(c->d_rgb); hipFree(c->d_counters); hipFree(c->d_records); hipFree(c->d_jobctr);
   hipFree(c->d_screen_masks); hipFree(c->d_world_masks); hipFree(c->d_world_occ);

@@ -28,7 +28,11 @@ EXPORTS = (
     "rt_scene_load_obj", "rt_scene_load_obj_ex", "rt_triangle_compute_normal", "rt_scene_pack", "rt_rotation_matrix",
     "rt_selftest_rcp", "rt_selftest_normalize", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_register_output", "rt_unregister_output",
     "rt_debug_band_copy_plan", "rt_update_scene", "rt_update_scene_device", "rt_debug_tile_data",
+    "rt_trace_rays", "rt_trace_rays_device", "rt_debug_trace_stats",
 )
+
+# rt_debug_trace_stats slots (include/uob_rt.h)
+TRACE_STATS_KEYS = ("rays", "waves", "tiles", "bundle_tiles", "tested_tiles", "triangle_tests", "unculled_rays", "reserved")
 
 _lib = None
 
@@ -67,6 +71,9 @@ def lib():
         L.rt_scene_load_obj.argtypes = [C.c_char_p, C.POINTER(abi.RtTriangle), C.c_int32]
         L.rt_scene_load_obj_ex.argtypes = [C.c_char_p, fp, C.c_float, fp, C.POINTER(abi.RtTriangle), C.c_int32]
         L.rt_debug_trace_rays.argtypes = [vp, C.c_int32, fp, fp, C.c_int64, C.POINTER(C.c_int32), fp]
+        L.rt_trace_rays.argtypes = [vp, C.c_int32, fp, fp, C.c_int64, C.POINTER(C.c_int32), fp]
+        L.rt_trace_rays_device.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, vp, vp, vp]
+        L.rt_debug_trace_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_debug_block_costs.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int32]
         L.rt_debug_world_masks.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.rt_debug_wave_timeline.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -209,6 +216,8 @@ class RayTracer:
         self.width = cfg.width
         self.n_triangles = len(scene)
         self.rows = lib().rt_config_owned_rows(C.byref(cfg))
+        # the device the context's queries run on (devices[0]; None: the device that was current at rt_init)
+        self.device = cfg.devices[0] if cfg.num_devices >= 1 else (cfg.device if cfg.device >= 0 else None)
 
     def update_scene(self, scene, reorder=False):
         """Replace the context's triangles (same count) between frames (rt_update_scene): refit the mesh kernel's tiles on
@@ -313,6 +322,77 @@ class RayTracer:
         _check(lib().rt_debug_trace_rays(self._h, abi.RT_TRACE_CLOSEST_HIT, _fp(rays), None, rays.shape[0],
                                          tri.ctypes.data_as(C.POINTER(C.c_int32)), _fp(out)))
         return tri, out
+
+    def query_in_shadow(self, rays, radius_sq):
+        """Tile-culled in_shadow (rt_trace_rays) on caller rays [k,6] = start, direction -> uint8 [k]; the same bits as
+        trace_in_shadow."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        r2 = np.ascontiguousarray(radius_sq, np.float32).reshape(-1)
+        if r2.shape[0] != rays.shape[0]:
+            raise ValueError("radius_sq must have one entry per ray")
+        out = np.zeros(rays.shape[0], np.int32)
+        _check(lib().rt_trace_rays(self._h, abi.RT_TRACE_IN_SHADOW, _fp(rays), _fp(r2), rays.shape[0],
+                                   out.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        return out.astype(np.uint8)
+
+    def query_closest_hit(self, rays):
+        """Tile-culled closest hit (rt_trace_rays) on caller rays -> (tri [k], out [k,10]); the same bits as
+        trace_closest_hit."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        tri = np.zeros(rays.shape[0], np.int32)
+        out = np.zeros((rays.shape[0], 10), np.float32)
+        _check(lib().rt_trace_rays(self._h, abi.RT_TRACE_CLOSEST_HIT, _fp(rays), None, rays.shape[0],
+                                   tri.ctypes.data_as(C.POINTER(C.c_int32)), _fp(out)))
+        return tri, out
+
+    def query_device(self, what, rays, radius_sq=None, out_tri=None, out10=None, stream=None):
+        """Enqueue a ray query on torch tensors of the context's device (rt_trace_rays_device), without synchronising.
+        rays: float32 [k,6]; radius_sq: float32 [k] (RT_TRACE_IN_SHADOW); out_tri: int32 [k]; out10: float32 [k,10]
+        (RT_TRACE_CLOSEST_HIT, optional).  Missing outputs are allocated.  stream: a torch stream or a raw hipStream_t
+        (default: torch's current stream).  Returns (out_tri, out10) for closest hit, out_tri for in_shadow."""
+        import torch
+        if what not in (abi.RT_TRACE_IN_SHADOW, abi.RT_TRACE_CLOSEST_HIT):
+            raise ValueError("unknown query mode %r" % (what,))
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+
+        def _need(name, t, dtype, shape):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch tensor" % name)
+            if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
+                                 % (name, dtype, shape, dev, t.dtype, tuple(t.shape), t.device))
+
+        if not isinstance(rays, torch.Tensor) or rays.dim() != 2:
+            raise ValueError("rays must be a torch tensor of shape [k, 6]")
+        k = rays.shape[0]
+        _need("rays", rays, torch.float32, (k, 6))
+        shadow = what == abi.RT_TRACE_IN_SHADOW
+        if shadow:
+            if radius_sq is None:
+                raise ValueError("in_shadow queries need radius_sq")
+            _need("radius_sq", radius_sq, torch.float32, (k,))
+        if out_tri is None:
+            out_tri = torch.empty(k, dtype=torch.int32, device=dev)
+        _need("out_tri", out_tri, torch.int32, (k,))
+        if not shadow:
+            if out10 is None:
+                out10 = torch.empty((k, 10), dtype=torch.float32, device=dev)
+            _need("out10", out10, torch.float32, (k, 10))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        raw = getattr(stream, "cuda_stream", stream) or 0
+        if k:
+            _check(lib().rt_trace_rays_device(self._h, what, C.c_void_p(rays.data_ptr()),
+                                              C.c_void_p(radius_sq.data_ptr() if shadow else 0), k,
+                                              C.c_void_p(out_tri.data_ptr()), C.c_void_p(0 if shadow else out10.data_ptr()),
+                                              C.c_void_p(raw)))
+        return out_tri if shadow else (out_tri, out10)
+
+    def trace_stats(self):
+        """Work counters of the context's most recent query (rt_debug_trace_stats): dict of TRACE_STATS_KEYS."""
+        out = (C.c_uint64 * 8)()
+        _check(lib().rt_debug_trace_stats(self._h, out))
+        return {key: int(out[i]) for i, key in enumerate(TRACE_STATS_KEYS)}
 
     def wave_timeline(self):
         """Wave kernel, context created with UOB_RT_TIMELINE=1: start / end statistics of the last frame's persistent waves
