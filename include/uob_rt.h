@@ -198,6 +198,48 @@ int rt_trace_rays_device(rt_ctx* ctx, int32_t what, const void* d_rays6, const v
  * tests, out[6] rays traced without culling (outside the certificates' domain; every ray without a tiled copy), out[7] 0. */
 int rt_debug_trace_stats(rt_ctx* ctx, uint64_t out[8]);
 
+/* ---- AOV pass: what every pixel of a view sees (rt_aov.hip) ------------------------------------------
+ * The planes describe the PRIMARY HIT of the frame that rt_render would render with the same rot, cam and focal on the
+ * context's current scene (after rt_update_scene).  No light is involved.
+ * Every pointer is nullable: a NULL plane is not computed / not written.  At least one must be set.                      */
+typedef struct rt_aov_buffers {
+  int32_t* prim;        /* -1 miss, -2 sphere, >= 0 ORIGINAL triangle index (as rt_trace_rays' out_tri)      */
+  float*   depth;       /* 1 float: |P - cam| (definition below); +INFINITY on a miss                        */
+  float*   position4;   /* float4: intersect.xyz, w = 1 on a hit; all zero on a miss                          */
+  float*   normal4;     /* float4: intersect_normal.xyz, w = 0; all zero on a miss                            */
+  float*   albedo4;     /* float4: intersect_color.xyzw (w = material flag: >0 diffuse, 0 mirror, <0 glass);
+                           all zero on a miss                                                                 */
+  float*   direction4;  /* float4: the primary ray's normalised direction, w = 0 (written hit or miss)        */
+} rt_aov_buffers;
+
+/* sample in 0 .. aa_x*aa_y-1 selects one AA sample per pixel, index dy*aa_x+dx exactly as the frame numbers them: every
+ * plane then holds owned_rows * width elements in the frame's own pixel order (bands: the owned rows packed top to bottom;
+ * ray directions use the global pixel coordinates).  sample == RT_AOV_ALL_SAMPLES: every plane holds
+ * owned_rows * width * aa elements, the samples of a pixel adjacent, in sample order (an antialiased matte, a per-sample
+ * denoiser).
+ * prim, position4, normal4, albedo4 carry exactly the bits that rt_trace_rays(RT_TRACE_CLOSEST_HIT) returns for the ray
+ * (cam, direction), i.e. the reference's single_ray_intersections (kernels.cl:168-241).  depth is derived from the
+ * position: with d = P - cam component-wise in FP32, depth = sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z), no contraction,
+ * correctly rounded square root.
+ * Ordering: a pass is a frame-like operation.  It runs one at a time with the context's frames and other passes (it shares
+ * their per-frame buffers), waits for the scene update before it, and scene updates wait for it.  It leaves the scheduling
+ * state ("last frame's expensive jobs first", block costs) and rt_last_kernel_ms untouched: a frame after a pass is
+ * scheduled as if the pass had not happened.  A multi-device context runs the pass on devices[0] over all rows it owns.
+ * Errors: a NULL ctx / rot / cam / buffers struct, all planes NULL and a sample out of range are RT_E_INVALID.
+ * rt_render_aov: host planes, blocking; staged through device memory the context keeps and grows on demand.
+ * rt_render_aov_device: planes in device memory on the context's device (devices[0]), enqueued on hip_stream (NULL =
+ * default stream) after the caller's earlier work; returns without synchronising, like rt_render_device.                 */
+#define RT_AOV_ALL_SAMPLES (-1)
+int rt_render_aov(rt_ctx* ctx, const float rot[12], const float cam[3], float focal, int32_t sample,
+                  const rt_aov_buffers* host_out);
+int rt_render_aov_device(rt_ctx* ctx, const float rot[12], const float cam[3], float focal, int32_t sample,
+                         const rt_aov_buffers* device_out, void* hip_stream);
+/* Diagnostic: work counters of the context's most recent AOV pass (synchronises it; zeros before the first).  out[0] samples,
+ * out[1] 64-lane waves, out[2] tiles of the scene (0 without a tiled copy), out[3] (wave, tile) pairs left by the screen
+ * masks (every tile without masks), out[4] (wave, tile) pairs whose triangles were tested, out[5] lane-level triangle tests,
+ * out[6..7] 0.                                                                                                          */
+int rt_debug_aov_stats(rt_ctx* ctx, uint64_t out[8]);
+
 /* Diagnostic, mesh kernel (n > 64): the cost of every 16x16-pixel block of the most recent frame in s_memtime ticks
  * (shader cycles) — the scheduling state "last frame's expensive blocks first" is built from it.  Row-major over
  * ceil(owned_rows/16) x ceil(width/16) blocks; writes min(count, cap) values, returns the block count, or

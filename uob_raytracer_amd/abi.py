@@ -12,6 +12,7 @@ RT_FLAG_PLAIN_ORDER = 16
 RT_FLAG_STAGED_GATHER = 32
 RT_TRACE_IN_SHADOW, RT_TRACE_CLOSEST_HIT = 0, 1
 RT_UPDATE_REORDER = 1
+RT_AOV_ALL_SAMPLES = -1
 
 
 class RtSphere(C.Structure):
@@ -46,6 +47,17 @@ class RtBandCopy(C.Structure):
 
 
 RT_COPY_2D, RT_COPY_PEER, RT_COPY_LINEAR = 0, 1, 2
+
+
+class RtAovBuffers(C.Structure):
+    """rt_aov_buffers: one nullable pointer per plane of an AOV pass."""
+    _fields_ = [("prim", C.c_void_p), ("depth", C.c_void_p), ("position4", C.c_void_p), ("normal4", C.c_void_p),
+                ("albedo4", C.c_void_p), ("direction4", C.c_void_p)]
+
+
+# plane name of RayTracer.render_aov -> (field of rt_aov_buffers, channels, element is int32)
+AOV_PLANES = {"prim": ("prim", 1, True), "depth": ("depth", 1, False), "position": ("position4", 4, False),
+              "normal": ("normal4", 4, False), "albedo": ("albedo4", 4, False), "direction": ("direction4", 4, False)}
 
 
 class RtTriangle(C.Structure):

@@ -4,7 +4,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <iostream>
+#include <string>
 
 screen* InitializeSDL(int width, int height, bool /*fullscreen*/) {
   screen* s = new screen;
@@ -57,4 +59,30 @@ void SDL_SaveImage(screen* s, const char* filename) {
   fwrite(hdr, 1, sizeof hdr, f);
   for (uint32_t y = 0; y < h; ++y) fwrite(s->buffer + (size_t)(h - 1 - y) * w, 4, w, f);
   fclose(f);
+}
+
+// A fixed hash of the primitive id (-2 sphere, -1 miss, >= 0 triangle) to an opaque colour: Knuth's multiplicative hash,
+// its top 24 bits.  (A bijection on 32 bits; two ids share a colour only if their difference times the constant falls
+// within 256 of a multiple of 2^32 — no two ids below 3 000 apart do.)
+uint32_t aov_id_colour(int32_t id) { return 0xFF000000u | (((uint32_t)(id + 2) * 2654435761u) >> 8); }
+
+void SaveAovImages(const char* prefix, int width, int height, const int32_t* prim, const float* depth, const float* normal4) {
+  screen* s = InitializeSDL(width, height, false);
+  const size_t count = (size_t)width * height;
+  auto q = [](float c) { float v = 255 * c; v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v); return (uint32_t)v; };
+  auto grey = [&](float r, float g, float b) { return (255u << 24) + (q(r) << 16) + (q(g) << 8) + q(b); };
+  float lo = INFINITY, hi = -INFINITY;
+  for (size_t i = 0; i < count; ++i)
+    if (std::isfinite(depth[i])) { lo = depth[i] < lo ? depth[i] : lo; hi = depth[i] > hi ? depth[i] : hi; }
+  for (size_t i = 0; i < count; ++i) {
+    const float g = !std::isfinite(depth[i]) ? 0.0f : (hi > lo ? (hi - depth[i]) / (hi - lo) : 1.0f);
+    s->buffer[i] = grey(g, g, g);
+  }
+  SDL_SaveImage(s, (std::string(prefix) + "_depth.bmp").c_str());
+  for (size_t i = 0; i < count; ++i)
+    s->buffer[i] = grey(0.5f * normal4[4 * i] + 0.5f, 0.5f * normal4[4 * i + 1] + 0.5f, 0.5f * normal4[4 * i + 2] + 0.5f);
+  SDL_SaveImage(s, (std::string(prefix) + "_normal.bmp").c_str());
+  for (size_t i = 0; i < count; ++i) s->buffer[i] = aov_id_colour(prim[i]);
+  SDL_SaveImage(s, (std::string(prefix) + "_id.bmp").c_str());
+  KillSDL(s);
 }

@@ -25,3 +25,9 @@ void PutPixelSDL(screen* s, int x, int y, float r, float g, float b);   // glm::
 void SDL_Renderframe(screen* s);
 void KillSDL(screen* s);
 void SDL_SaveImage(screen* s, const char* filename);
+
+// Not in the reference: the AOV planes of a view (rt_render_aov, one sample per pixel) as three images PREFIX_depth.bmp
+// (grey, nearest = white, linear between the smallest and the largest finite depth, misses black), PREFIX_normal.bmp
+// (0.5 * n + 0.5) and PREFIX_id.bmp (aov_id_colour of the primitive id), written by SDL_SaveImage.
+uint32_t aov_id_colour(int32_t id);
+void SaveAovImages(const char* prefix, int width, int height, const int32_t* prim, const float* depth, const float* normal4);

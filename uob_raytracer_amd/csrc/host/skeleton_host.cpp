@@ -117,6 +117,7 @@ int main(int argc, char* argv[]) {
   int frames = 10;
   const char* out = "screenshot.bmp";
   const char* obj = nullptr;
+  const char* aov = nullptr;
   rt_config cfg;
   rt_config_default(&cfg);
   for (int i = 1; i < argc; ++i) {
@@ -128,6 +129,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--keys" && i + 1 < argc) { istringstream in(argv[++i]); string k; while (in >> k) g_keys.push_back(k); }
     else if (a == "--out" && i + 1 < argc) out = argv[++i];
     else if (a == "--obj" && i + 1 < argc) obj = argv[++i];
+    else if (a == "--aov" && i + 1 < argc) aov = argv[++i];       // PREFIX of the last view's depth / normal / id images
     else if (a == "--move" && i + 1 < argc) {
       if (sscanf(argv[++i], "%f,%f,%f", &g_move_by[0], &g_move_by[1], &g_move_by[2]) != 3) { fprintf(stderr, "--move DX,DY,DZ\n"); return 2; }
       g_move = true;
@@ -180,6 +182,18 @@ int main(int argc, char* argv[]) {
     SDL_Renderframe(screen);
   }
   SDL_SaveImage(screen, out);                                                  // :139
+  if (aov) {                                                                   // what the last frame's pixels see (sample 0)
+    const size_t px = (size_t)SCREEN_WIDTH * SCREEN_HEIGHT;
+    vector<int32_t> prim(px);
+    vector<float> depth(px), normal(4 * px);
+    float rot[12];
+    rt_rotation_matrix(yaw, pitch, rot);
+    rt_aov_buffers planes;
+    memset(&planes, 0, sizeof planes);
+    planes.prim = prim.data(); planes.depth = depth.data(); planes.normal4 = normal.data();
+    if (rt_render_aov(g_rt, rot, camera_position, focal_length, 0, &planes) != RT_OK) die("rt_render_aov");
+    SaveAovImages(aov, SCREEN_WIDTH, SCREEN_HEIGHT, prim.data(), depth.data(), normal.data());
+  }
   printf("light_position.x %.9g yaw %.9g pitch %.9g camera %.9g %.9g\n", light_position[0], yaw, pitch,
          camera_position[0], camera_position[2]);
   rt_destroy(g_rt);

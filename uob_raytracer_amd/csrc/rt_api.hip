@@ -60,6 +60,9 @@ int launch_scene_check(const float4* v, const float4* col, int n, unsigned int* 
 void launch_scene_refit(const float4* v, const float4* nrm, const float4* col, const int* orig, int n, float4* vm, float4* nm,
                         float4* cm, float4* tile_box, hipStream_t stream);
 int query_stats_words();
+int aov_stats_words();
+void launch_aov(const FrameParams& P, bool tiled, const AovPlanes& A, int sample, unsigned long long* stats, int cus, hipStream_t stream);
+void launch_bin_primary(const FrameParams& P, hipStream_t stream);
 void launch_query(const FrameParams& P, bool tiled, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
                   float* d_out10, unsigned long long* stats, int cus, hipStream_t stream);
 
@@ -154,6 +157,15 @@ struct rt_ctx {
   float4* d_qrecords = nullptr;             // no tiled copy, beyond one LDS stage: the queries' own records (d_records is the frames')
   char* d_qio = nullptr;                    // rt_trace_rays: device copies of the caller's host arrays
   size_t qio_bytes = 0;
+  // AOV passes (rt_render_aov_device, rt_aov.hip): frame-like — they use the frames' records and screen masks, so frames,
+  // updates and later passes wait for the latest one through ev_aov; they touch none of the scheduling state above
+  hipEvent_t ev_aov = nullptr;
+  bool aov_pending = false;
+  hipStream_t aov_stream = nullptr;
+  unsigned long long* d_astats = nullptr;   // the latest pass's work counters (+ the tiled kernel's queue head)
+  int aov_tiles = 0;                        // tiles the latest pass walked (0: no tiled copy)
+  char* d_aov = nullptr;                    // rt_render_aov: device copies of the caller's host planes
+  size_t aov_bytes = 0;
 };
 
 static int validate_config(const rt_config* c) {
@@ -751,6 +763,11 @@ static hipError_t wait_scene(const rt_ctx* c, hipStream_t s) {
   return c->upd_pending ? hipStreamWaitEvent(s, c->ev_upd, 0) : hipSuccess;
 }
 
+// Whatever shares the frames' per-frame buffers (records, screen masks) or rewrites the scene waits for the latest AOV pass
+static hipError_t wait_aov(const rt_ctx* c, hipStream_t s) {
+  return (c->aov_pending && s != c->aov_stream) ? hipStreamWaitEvent(s, c->ev_aov, 0) : hipSuccess;
+}
+
 // The mesh kernel works on the reordered copy of the scene (upload_tiled_scene)
 static void use_tiled_scene(const rt_ctx* c, FrameParams* P) {
   P->verts = c->d_verts_m; P->normals = c->d_normals_m; P->colors = c->d_colors_m;
@@ -777,6 +794,7 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
   HIP_TRY(hipSetDevice(c->device));
   // one frame of a context at a time: the queue heads, the expensive-job lists and the tile masks are shared
   if (c->timed && stream != c->last_stream) HIP_TRY(hipStreamWaitEvent(stream, c->ev1, 0));
+  HIP_TRY(wait_aov(c, stream));
   HIP_TRY(wait_scene(c, stream));          // before ev0: rt_last_kernel_ms times the frame's kernels only
   HIP_TRY(hipEventRecord(c->ev0, stream));
   const bool wave_paths = !(c->cfg.flags & RT_FLAG_GENERIC_KERNEL);
@@ -840,6 +858,7 @@ static int update_begin(rt_ctx* c, hipStream_t s) {
   HIP_TRY(hipSetDevice(c->device));
   if (c->timed) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
   if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));    // ray queries still reading the scene
+  HIP_TRY(wait_aov(c, s));
   HIP_TRY(wait_scene(c, s));
   return RT_OK;
 }
@@ -1253,6 +1272,7 @@ int rt_count_work(rt_ctx* c, const float rot[12], const float cam[3], const floa
   fill_params(c, rot, cam, light, focal, &P);
   P.counters = c->d_counters;
   HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(wait_aov(c, c->stream));
   HIP_TRY(wait_scene(c, c->stream));
   HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt_work), c->stream));
   launch_generic(P, true, c->stream);
@@ -1291,6 +1311,7 @@ int rt_count_executed(rt_ctx* c, const float rot[12], const float cam[3], const 
   P.counters = c->d_counters;
   HIP_TRY(hipSetDevice(c->device));
   if (c->timed) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev1, 0));
+  HIP_TRY(wait_aov(c, c->stream));
   HIP_TRY(wait_scene(c, c->stream));
   HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt_work), c->stream));
   if (mesh) { use_tiled_scene(c, &P); launch_stage_records(P, c->stream); launch_mesh(P, true, c->tune.phase_profile, c->stream, nullptr, nullptr, nullptr); }
@@ -1353,6 +1374,7 @@ int rt_debug_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float
   };
   if (rc == RT_OK) {
     if (c->timed) ok(hipStreamWaitEvent(c->stream, c->ev1, 0), "hipStreamWaitEvent");
+    ok(wait_aov(c, c->stream), "hipStreamWaitEvent");
     ok(wait_scene(c, c->stream), "hipStreamWaitEvent");
     ok(hipMemcpyAsync(d_rays, rays6, (size_t)nray * 24, hipMemcpyHostToDevice, c->stream), "ray upload");
     if (radius_sq) ok(hipMemcpyAsync(d_r2, radius_sq, (size_t)nray * 4, hipMemcpyHostToDevice, c->stream), "ray upload");
@@ -1459,6 +1481,127 @@ int rt_debug_trace_stats(rt_ctx* c, uint64_t out[8]) {
   return RT_OK;
 }
 
+// ---- AOV passes (rt_render_aov / rt_render_aov_device, rt_aov.hip) ----------------------------------------------------
+// Checked before the context is looked at, so that the struct's own errors are reported for any context
+static int check_aov_args(const rt_ctx* c, const float* rot, const float* cam, const rt_aov_buffers* b, const char* fn) {
+  if (!b) { set_error("%s: the buffers struct is NULL", fn); return RT_E_INVALID; }
+  if (!b->prim && !b->depth && !b->position4 && !b->normal4 && !b->albedo4 && !b->direction4) {
+    set_error("%s: no plane requested (every pointer of the buffers struct is NULL)", fn); return RT_E_INVALID;
+  }
+  if (!c) { set_error("%s: ctx is NULL", fn); return RT_E_INVALID; }
+  if (!rot || !cam) { set_error("%s: rot / cam is NULL", fn); return RT_E_INVALID; }
+  return RT_OK;
+}
+
+// One pass of a single-device context on stream s into device planes of c->device.  `whole`: c is devices[0] of a
+// multi-device context and renders every row of the frame, not only its own bands.
+static int enqueue_aov(rt_ctx* c, const float rot[12], const float cam[3], float focal, int32_t sample, const AovPlanes& A,
+                       bool whole, hipStream_t s) {
+  const int aa = c->cfg.aa_x * c->cfg.aa_y;
+  if (sample != RT_AOV_ALL_SAMPLES && (sample < 0 || sample >= aa)) {
+    set_error("rt_render_aov: sample = %d outside [0, %d) and not RT_AOV_ALL_SAMPLES", sample, aa); return RT_E_INVALID;
+  }
+  for (int k = 0; k < 3; ++k)
+    if (!(fabsf(cam[k]) <= kMaxCoordinate)) { set_error("camera coordinates must be finite and <= 2^16"); return RT_E_INVALID; }
+  if (!(fabsf(focal) <= 1.0e9f)) { set_error("focal length must be finite and <= 1e9"); return RT_E_INVALID; }
+  for (int k = 0; k < 12; ++k)
+    if (!(fabsf(rot[k]) <= 4.0f)) { set_error("rotation matrix entries must be finite and <= 4"); return RT_E_INVALID; }
+  const int rows = whole ? c->cfg.height : c->owned_rows;
+  if (rows == 0) return RT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t stats_bytes = (size_t)aov_stats_words() * sizeof(unsigned long long);
+  if (!c->ev_aov) HIP_TRY(hipEventCreateWithFlags(&c->ev_aov, hipEventDisableTiming));
+  if (!c->d_astats && hipMalloc(&c->d_astats, stats_bytes) != hipSuccess) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
+  }
+  const float zero3[3] = {0.f, 0.f, 0.f};
+  FrameParams P;
+  fill_params(c, rot, cam, zero3, focal, &P);
+  if (whole) {                                 // all rows of the frame in image order
+    P.band_rows = c->cfg.height; P.band_index = 0; P.band_count = 1; P.owned_rows = rows;
+    P.band_rows_magic = P.band_rows > 1 ? (uint32_t)((0x100000000ull + (uint64_t)P.band_rows - 1) / (uint64_t)P.band_rows) : 0u;
+  }
+  const bool tiled = c->d_verts_m != nullptr;
+  const bool bins = tiled && c->d_screen_masks != nullptr && c->d_records != nullptr && !(c->tune.mask_debug & 1);
+  if (!bins) P.screen_masks = nullptr;
+  // one frame-like operation of a context at a time: the records and the screen masks are the frames'
+  if (c->timed && s != c->last_stream) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
+  HIP_TRY(wait_aov(c, s));
+  HIP_TRY(wait_scene(c, s));
+  HIP_TRY(hipMemsetAsync(c->d_astats, 0, stats_bytes, s));
+  if (tiled) {
+    use_tiled_scene(c, &P);
+    if (bins) { launch_stage_records(P, s); launch_bin_primary(P, s); }   // the masks are built from this view's records
+  } else if (generic_needs_records(c->n)) {
+    launch_stage_records(P, s);
+  }
+  launch_aov(P, tiled, A, sample, c->d_astats, c->cus, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev_aov, s));
+  c->aov_pending = true;
+  c->aov_stream = s;
+  c->aov_tiles = tiled ? mesh_tiles(c->n) : 0;
+  return RT_OK;
+}
+
+int rt_render_aov_device(rt_ctx* c, const float rot[12], const float cam[3], float focal, int32_t sample,
+                         const rt_aov_buffers* device_out, void* hip_stream) {
+  const int rc = check_aov_args(c, rot, cam, device_out, "rt_render_aov_device");
+  if (rc != RT_OK) return rc;
+  const bool whole = !c->kids.empty();
+  if (whole) c = c->kids[0];
+  DeviceGuard guard;
+  const AovPlanes A{device_out->prim, device_out->depth, (float4*)device_out->position4, (float4*)device_out->normal4,
+                    (float4*)device_out->albedo4, (float4*)device_out->direction4};
+  return enqueue_aov(c, rot, cam, focal, sample, A, whole, (hipStream_t)hip_stream);
+}
+
+int rt_render_aov(rt_ctx* c, const float rot[12], const float cam[3], float focal, int32_t sample, const rt_aov_buffers* host_out) {
+  int rc = check_aov_args(c, rot, cam, host_out, "rt_render_aov");
+  if (rc != RT_OK) return rc;
+  const bool whole = !c->kids.empty();
+  const int rows = c->owned_rows;
+  if (whole) c = c->kids[0];
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  const int aa = c->cfg.aa_x * c->cfg.aa_y;
+  const size_t count = (size_t)rows * c->cfg.width * (sample == RT_AOV_ALL_SAMPLES ? aa : 1);
+  void* const host[6] = {host_out->prim, host_out->depth, host_out->position4, host_out->normal4, host_out->albedo4, host_out->direction4};
+  const size_t elem[6] = {4, 4, 16, 16, 16, 16};
+  size_t off[6], bytes = 0;
+  for (int k = 0; k < 6; ++k) { off[k] = bytes; if (host[k]) bytes += count * elem[k]; }
+  if (count == 0) return RT_OK;
+  if (bytes > c->aov_bytes) {                 // (only this blocking entry uses the buffer: nothing can still be reading it)
+    hipFree(c->d_aov);
+    c->d_aov = nullptr; c->aov_bytes = 0;
+    if (hipMalloc(&c->d_aov, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
+    c->aov_bytes = bytes;
+  }
+  char* const d = c->d_aov;
+  auto at = [&](int k) -> void* { return host[k] ? (void*)(d + off[k]) : nullptr; };
+  const AovPlanes A{(int*)at(0), (float*)at(1), (float4*)at(2), (float4*)at(3), (float4*)at(4), (float4*)at(5)};
+  rc = enqueue_aov(c, rot, cam, focal, sample, A, whole, c->stream);
+  if (rc != RT_OK) { hipStreamSynchronize(c->stream); return rc; }
+  for (int k = 0; k < 6; ++k)
+    if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], d + off[k], count * elem[k], hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_debug_aov_stats(rt_ctx* c, uint64_t out[8]) {
+  if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
+  memset(out, 0, 8 * sizeof(uint64_t));
+  if (!c->kids.empty()) c = c->kids[0];
+  if (!c->aov_pending) return RT_OK;
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->ev_aov));
+  HIP_TRY(hipMemcpy(out, c->d_astats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  out[2] = (uint64_t)c->aov_tiles;
+  out[6] = out[7] = 0;
+  return RT_OK;
+}
+
 int rt_debug_band_copy_plan(int32_t num_devices, int32_t k, int32_t device_band_rows, int32_t width, int32_t height,
                             int32_t elem_bytes, int32_t dev_to_dev, int32_t peer_ok, int32_t same_device,
                             rt_band_copy* out, int32_t cap) {
@@ -1545,6 +1688,8 @@ void rt_destroy(rt_ctx* c) {
   if (c->ev_upd) hipEventDestroy(c->ev_upd);
   if (c->ev_query) { hipEventSynchronize(c->ev_query); hipEventDestroy(c->ev_query); }
   hipFree(c->d_qstats); hipFree(c->d_qrecords); hipFree(c->d_qio);
+  if (c->ev_aov) { hipEventSynchronize(c->ev_aov); hipEventDestroy(c->ev_aov); }
+  hipFree(c->d_astats); hipFree(c->d_aov);
   hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);
   hipFree(c->d_argb); hipFree(c->d_rgb); hipFree(c->d_counters); hipFree(c->d_records); hipFree(c->d_jobctr);
   hipFree(c->d_screen_masks); hipFree(c->d_world_masks); hipFree(c->d_world_occ);

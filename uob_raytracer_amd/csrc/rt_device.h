@@ -110,6 +110,13 @@ struct FrameParams {
   float grid_lo[3], grid_cell, grid_inv;   // world grid: origin, cell edge, 1 / cell edge
 };
 
+// The planes of an AOV pass (rt_aov.hip; include/uob_rt.h rt_aov_buffers) in device memory, nullptr = not asked for
+struct AovPlanes {
+  int* prim;
+  float* depth;
+  float4 *position, *normal, *albedo, *direction;
+};
+
 // n / d for n < 2^16 * ... (rows, jobs) with the host's magic = ceil(2^32 / d): exact while n * (magic * d - 2^32) < 2^32,
 // which holds for every row index (< 2^15) and job index (< 2^20, d <= 2^11) of a frame; magic 0 stands for d == 1
 __device__ inline uint32_t div_magic(uint32_t n, uint32_t magic) { return magic ? __umulhi(n, magic) : n; }

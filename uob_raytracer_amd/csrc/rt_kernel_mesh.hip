@@ -39,8 +39,6 @@ constexpr int kDirectSamples = 2;           // up to this many, level 2 is skipp
 // 10 samples at 2048^2: 10.2 / 5.07; at 24 and 32 samples the two forms are level (0.73 / 0.72, 8.11 / 8.45), at 64 lane =
 // point is 1.7 x slower.
 constexpr int kPointSamples = 16;
-constexpr int kScreenCell = 32;             // pixels per side of a screen cell of the primary-ray tile masks
-constexpr int kScreenCellLog = 5;
 
 // World cell of a shadow ray's start point (rt_bin_shadow bounds exactly the points that map to a cell)
 __device__ __forceinline__ int world_cell(const FrameParams& P, f3 s) {
@@ -1138,5 +1136,12 @@ void launch_mesh(const FrameParams& P, bool count, bool prof, hipStream_t stream
 }
 
 int mesh_blocks_per_cu() { return kMeshMinBlocks; }
+
+// The primary-ray tile masks alone, for a view whose records are staged (the AOV pass, rt_aov.hip)
+void launch_bin_primary(const FrameParams& P, hipStream_t stream) {
+  const int ntiles = mesh_tiles(P.n), nwords = (ntiles + 63) / 64;
+  hipMemsetAsync(P.screen_masks, 0, (size_t)P.scx * P.scy * nwords * 8, stream);
+  hipLaunchKernelGGL(rt_bin_primary, dim3((ntiles + kMeshWaves - 1) / kMeshWaves, (P.scy + 3) / 4), dim3(64 * kMeshWaves), 0, stream, P);
+}
 
 }  // namespace uobrt

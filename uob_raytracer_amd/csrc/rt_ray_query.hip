@@ -32,18 +32,6 @@ constexpr int kQTile = 64;                  // triangles per tile of the tiled c
 // Work counters of a query (rt_debug_trace_stats), then the tiled kernel's queue head
 enum { Q_RAYS, Q_WAVES, Q_TILES, Q_BUNDLE_TILES, Q_TESTED_TILES, Q_TRI_TESTS, Q_UNCULLED, Q_SLOTS = 8 };
 
-// The domain over which the exact certificates hold: finite, |start| <= 2^16, 2^-20 <= max |direction component| <= 2^16
-__device__ __forceinline__ bool in_query_domain(f3 o, f3 d) {
-  const bool fin = fabsf(o.x) <= kMaxCoordinate && fabsf(o.y) <= kMaxCoordinate && fabsf(o.z) <= kMaxCoordinate &&
-                   fabsf(d.x) <= kMaxCoordinate && fabsf(d.y) <= kMaxCoordinate && fabsf(d.z) <= kMaxCoordinate;   // (false for NaN)
-  return fin && fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z)) >= 0x1p-20f;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // One atomic add per counter and wave, at its exit (all lanes active)
 __device__ __forceinline__ void flush_stats(unsigned long long* stats, const unsigned long long (&w)[Q_SLOTS], unsigned long long lane_tests) {
   const unsigned long long tests = wave_sum(lane_tests);

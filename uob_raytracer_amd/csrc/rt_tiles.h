@@ -1,5 +1,5 @@
 // rt_tiles.h — the exact tile certificate and the closest-hit tie rule of the tiled mesh copy, shared by the mesh kernel
-// (rt_kernel_mesh.hip, bounce rays) and the ray queries (rt_ray_query.hip).  Include after rt_wave_common.h.
+// (rt_kernel_mesh.hip, bounce rays), the ray queries (rt_ray_query.hip) and the AOV pass (rt_aov.hip).  Include after rt_wave_common.h.
 #pragma once
 #include "rt_wave_common.h"
 
@@ -65,6 +65,22 @@ __device__ __forceinline__ TileHit no_hit() { return TileHit{RT_MAXFLOAT, 0.f, 0
 __device__ __forceinline__ bool closer(float t, int orig, const TileHit& h) {
   return t < h.t || (t == h.t && h.best >= 0 && orig < h.orig);
 }
+
+// ---- shared by the ray queries (rt_ray_query.hip) and the AOV pass (rt_aov.hip) -----------------------------------------
+// The domain over which the exact certificates hold: finite, |start| <= 2^16, 2^-20 <= max |direction component| <= 2^16
+__device__ __forceinline__ bool in_query_domain(f3 o, f3 d) {
+  const bool fin = fabsf(o.x) <= kMaxCoordinate && fabsf(o.y) <= kMaxCoordinate && fabsf(o.z) <= kMaxCoordinate &&
+                   fabsf(d.x) <= kMaxCoordinate && fabsf(d.y) <= kMaxCoordinate && fabsf(d.z) <= kMaxCoordinate;   // (false for NaN)
+  return fin && fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z)) >= 0x1p-20f;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+constexpr int kScreenCell = 32;             // pixels per side of a screen cell of the primary-ray tile masks
+constexpr int kScreenCellLog = 5;
 
 }  // namespace
 }  // namespace uobrt

@@ -29,10 +29,13 @@ EXPORTS = (
     "rt_selftest_rcp", "rt_selftest_normalize", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_register_output", "rt_unregister_output",
     "rt_debug_band_copy_plan", "rt_update_scene", "rt_update_scene_device", "rt_debug_tile_data",
     "rt_trace_rays", "rt_trace_rays_device", "rt_debug_trace_stats",
+    "rt_render_aov", "rt_render_aov_device", "rt_debug_aov_stats",
 )
 
 # rt_debug_trace_stats slots (include/uob_rt.h)
 TRACE_STATS_KEYS = ("rays", "waves", "tiles", "bundle_tiles", "tested_tiles", "triangle_tests", "unculled_rays", "reserved")
+# rt_debug_aov_stats slots
+AOV_STATS_KEYS = ("samples", "waves", "tiles", "mask_tiles", "tested_tiles", "triangle_tests", "reserved6", "reserved7")
 
 _lib = None
 
@@ -74,6 +77,9 @@ def lib():
         L.rt_trace_rays.argtypes = [vp, C.c_int32, fp, fp, C.c_int64, C.POINTER(C.c_int32), fp]
         L.rt_trace_rays_device.argtypes = [vp, C.c_int32, vp, vp, C.c_int64, vp, vp, vp]
         L.rt_debug_trace_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_render_aov.argtypes = [vp, fp, fp, C.c_float, C.c_int32, C.POINTER(abi.RtAovBuffers)]
+        L.rt_render_aov_device.argtypes = [vp, fp, fp, C.c_float, C.c_int32, C.POINTER(abi.RtAovBuffers), vp]
+        L.rt_debug_aov_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_debug_block_costs.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int32]
         L.rt_debug_world_masks.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.rt_debug_wave_timeline.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -387,6 +393,58 @@ class RayTracer:
                                               C.c_void_p(out_tri.data_ptr()), C.c_void_p(0 if shadow else out10.data_ptr()),
                                               C.c_void_p(raw)))
         return out_tri if shadow else (out_tri, out10)
+
+    def _aov_shape(self, name, sample):
+        if name not in abi.AOV_PLANES:
+            raise ValueError("unknown AOV plane %r (one of %s)" % (name, ", ".join(abi.AOV_PLANES)))
+        ch = abi.AOV_PLANES[name][1]
+        aa = self.cfg.aa_x * self.cfg.aa_y
+        return (self.rows, self.width) + ((aa,) if sample is None else ()) + ((4,) if ch == 4 else ())
+
+    def render_aov(self, rot, cam, focal, sample=0, planes=("prim", "depth", "position", "normal", "albedo", "direction")):
+        """AOV pass of the view (rt_render_aov), blocking: dict plane name -> numpy array [rows, W] (prim int32, depth
+        float32) / [rows, W, 4] (float32); sample=None = every AA sample, with an extra axis of aa_x*aa_y samples in front of
+        the channel axis."""
+        rot, cam, _ = self._args(rot, cam, cam)
+        planes = tuple(planes)
+        out, bufs = {}, abi.RtAovBuffers()
+        for name in planes:
+            shape = self._aov_shape(name, sample)
+            out[name] = np.zeros(shape, np.int32 if abi.AOV_PLANES[name][2] else np.float32)
+            setattr(bufs, abi.AOV_PLANES[name][0], out[name].ctypes.data)
+        _check(lib().rt_render_aov(self._h, _fp(rot), _fp(cam), C.c_float(focal),
+                                   abi.RT_AOV_ALL_SAMPLES if sample is None else int(sample), C.byref(bufs)))
+        return out
+
+    def render_aov_device(self, rot, cam, focal, sample=0, out=None, stream=None):
+        """Enqueue an AOV pass into torch tensors of the context's device (rt_render_aov_device), without synchronising.
+        out: dict plane name -> contiguous tensor shaped as render_aov's arrays (prim int32, the others float32); only the
+        planes named in it are computed.  stream: a torch stream or a raw hipStream_t (default: torch's current stream)."""
+        import torch
+        if not out:
+            raise ValueError("out must name at least one plane")
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        rot, cam, _ = self._args(rot, cam, cam)
+        bufs = abi.RtAovBuffers()
+        for name, t in out.items():
+            shape = self._aov_shape(name, sample)
+            dtype = torch.int32 if abi.AOV_PLANES[name][2] else torch.float32
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("plane %r must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
+            setattr(bufs, abi.AOV_PLANES[name][0], t.data_ptr())
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        raw = getattr(stream, "cuda_stream", stream) or 0
+        _check(lib().rt_render_aov_device(self._h, _fp(rot), _fp(cam), C.c_float(focal),
+                                          abi.RT_AOV_ALL_SAMPLES if sample is None else int(sample), C.byref(bufs),
+                                          C.c_void_p(raw)))
+        return out
+
+    def aov_stats(self):
+        """Work counters of the context's most recent AOV pass (rt_debug_aov_stats): dict of AOV_STATS_KEYS."""
+        out = (C.c_uint64 * 8)()
+        _check(lib().rt_debug_aov_stats(self._h, out))
+        return {key: int(out[i]) for i, key in enumerate(AOV_STATS_KEYS)}
 
     def trace_stats(self):
         """Work counters of the context's most recent query (rt_debug_trace_stats): dict of TRACE_STATS_KEYS."""
