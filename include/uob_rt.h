@@ -198,6 +198,44 @@ int rt_trace_rays_device(rt_ctx* ctx, int32_t what, const void* d_rays6, const v
  * tests, out[6] rays traced without culling (outside the certificates' domain; every ray without a tiled copy), out[7] 0. */
 int rt_debug_trace_stats(rt_ctx* ctx, uint64_t out[8]);
 
+/* ---- direct light at caller points (rt_shade.hip) -----------------------------------------------------
+ * How much light arrives at a surface point: one channel of the reference's direct_light (kernels.cl:313-340; its three
+ * channels are equal), the jittered area-light sum of the context's shadow_samples shadow rays with its light_spread, on the
+ * context's scene as its latest update left it.  With rt_trace_rays and RT_TRACE_IN_SHADOW this completes the queries: what
+ * does a ray hit, is a point shadowed, how much light arrives.
+ *   points6 = float32 [npoints][6]: position.xyz, normal.xyz (ray.intersect and intersect_normal, e.g. the position4 /
+ *             normal4 planes of rt_render_aov).
+ *   seeds   = nullable int32 [npoints]: the global_id that seeds the point's jitter stream, 0 .. 2^24 (the frame uses the
+ *             pixel id y * width + x); NULL = k & 0xFFFFFF.  rt_shade_points rejects a seed outside the domain with
+ *             RT_E_INVALID before any device work; in rt_shade_points_device such a seed yields an unspecified light value
+ *             (it only feeds the generator).
+ *   out_light[k] = exactly the reference's bits: seeds (id, (uint)(id * 91.0f), (uint)(id * 19.0f)), one generator step, then
+ *             per sample one step and the ray (start, dir + crush(r, light_spread)) with dir = light - P,
+ *             start = P + 0.0001f * dir, radius_sq = (dx*dx + dy*dy) + dz*dz, tested by in_shadow;
+ *             term = (16 * max(dot(dir, N), 0)) / (4 * pi_f * radius_sq) is added once per unblocked sample and 0.0f * term
+ *             for a blocked one, in FP32 without contraction, then / shadow_samples — the frame's own summation, so that
+ *             albedo.xyz * (0.5f + out_light) is the frame's colour of a diffuse primary hit.  Non-finite and degenerate
+ *             inputs (P at the light) give what that arithmetic gives; points whose rays leave the domain of the exact culls
+ *             (|coordinate| <= 2^16) are traced without culling.
+ *   out_unshadowed[k] = nullable: the number of unblocked samples, 0 .. shadow_samples (a shadow matte's numerator).  When
+ *             it is NULL a point whose term is 0 (facing away from the light) is not traced.
+ * A NULL ctx / points6 / light / out_light and npoints < 0 or > 2^31 are RT_E_INVALID; npoints == 0 is a no-op.  Ordering is
+ * rt_trace_rays': frames and shade calls do not wait for each other; the context's next query, shade call and scene update
+ * (and rt_destroy) wait for a shade call, and it waits for the query and the update before it.  A multi-device context runs
+ * it on devices[0].
+ * rt_shade_points: host arrays, blocking (staged through device memory the context keeps and grows on demand).
+ * rt_shade_points_device: device memory on the context's device, enqueued on hip_stream (NULL = default stream) after the
+ * caller's earlier work; returns without synchronising.                                                                   */
+int rt_shade_points(rt_ctx* ctx, const float* points6, const int32_t* seeds, int64_t npoints, const float light[3],
+                    float* out_light, int32_t* out_unshadowed);
+int rt_shade_points_device(rt_ctx* ctx, const void* d_points6, const void* d_seeds, int64_t npoints, const float light[3],
+                           void* d_out_light, void* d_out_unshadowed, void* hip_stream);
+/* Diagnostic: work counters of the context's most recent shade call (synchronises it; zeros before the first).  out[0] points,
+ * out[1] sample rays traced, out[2] 64-lane waves of rays, out[3] tiles of the scene (0 without a tiled copy), out[4] (wave,
+ * tile) pairs left by the bundle test (without a tiled copy: every run of 64 triangles), out[5] pairs whose triangles were
+ * tested, out[6] lane-level triangle tests, out[7] points not traced because their term is 0.                             */
+int rt_debug_shade_stats(rt_ctx* ctx, uint64_t out[8]);
+
 /* ---- AOV pass: what every pixel of a view sees (rt_aov.hip) ------------------------------------------
  * The planes describe the PRIMARY HIT of the frame that rt_render would render with the same rot, cam and focal on the
  * context's current scene (after rt_update_scene).  No light is involved.

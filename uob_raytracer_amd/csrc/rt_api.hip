@@ -65,6 +65,9 @@ void launch_aov(const FrameParams& P, bool tiled, const AovPlanes& A, int sample
 void launch_bin_primary(const FrameParams& P, hipStream_t stream);
 void launch_query(const FrameParams& P, bool tiled, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
                   float* d_out10, unsigned long long* stats, int cus, hipStream_t stream);
+int shade_stats_words();
+void launch_shade(const FrameParams& P, bool tiled, const float* d_points6, const int* d_seeds, long npoints, float* d_light,
+                  int* d_cnt, unsigned long long* stats, int cus, hipStream_t stream);
 
 }  // namespace uobrt
 
@@ -157,6 +160,14 @@ struct rt_ctx {
   float4* d_qrecords = nullptr;             // no tiled copy, beyond one LDS stage: the queries' own records (d_records is the frames')
   char* d_qio = nullptr;                    // rt_trace_rays: device copies of the caller's host arrays
   size_t qio_bytes = 0;
+  // shade calls (rt_shade_points_device, rt_shade.hip): ordered like the queries — they read only the scene, frames do not wait
+  // for them; the next query, shade call and scene update do, through ev_shade (and a shade call waits for the latest query)
+  hipEvent_t ev_shade = nullptr;
+  bool shade_pending = false;
+  unsigned long long* d_sstats = nullptr;   // the latest call's work counters (+ the kernel's queue head)
+  int shade_tiles = 0;                      // tiles of the latest call's scene (0: no tiled copy)
+  char* d_sio = nullptr;                    // rt_shade_points: device copies of the caller's host arrays
+  size_t sio_bytes = 0;
   // AOV passes (rt_render_aov_device, rt_aov.hip): frame-like — they use the frames' records and screen masks, so frames,
   // updates and later passes wait for the latest one through ev_aov; they touch none of the scheduling state above
   hipEvent_t ev_aov = nullptr;
@@ -858,6 +869,7 @@ static int update_begin(rt_ctx* c, hipStream_t s) {
   HIP_TRY(hipSetDevice(c->device));
   if (c->timed) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
   if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));    // ray queries still reading the scene
+  if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));    // shade calls likewise
   HIP_TRY(wait_aov(c, s));
   HIP_TRY(wait_scene(c, s));
   return RT_OK;
@@ -1421,6 +1433,7 @@ static int enqueue_query(rt_ctx* c, int32_t what, const float* d_rays, const flo
   P.records = records ? c->d_qrecords : nullptr;
   HIP_TRY(wait_scene(c, s));
   if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));
+  if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));
   HIP_TRY(hipMemsetAsync(c->d_qstats, 0, stats_bytes, s));
   if (records) launch_stage_records(P, s);
   launch_query(P, tiled, what, d_rays, d_r2, nray, d_tri, what == RT_TRACE_CLOSEST_HIT ? d_out10 : nullptr, c->d_qstats, c->cus, s);
@@ -1478,6 +1491,97 @@ int rt_debug_trace_stats(rt_ctx* c, uint64_t out[8]) {
   HIP_TRY(hipEventSynchronize(c->ev_query));
   HIP_TRY(hipMemcpy(out, c->d_qstats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
   out[2] = (uint64_t)c->query_tiles;
+  return RT_OK;
+}
+
+// ---- shade calls (rt_shade_points / rt_shade_points_device, rt_shade.hip) -----------------------------------------------
+// Checked before the context is looked at, like the queries' arguments
+static int check_shade_args(const rt_ctx* c, const void* points6, int64_t npoints, const float* light, const void* out_light,
+                            const char* fn) {
+  if (!c || !points6 || !light || !out_light) { set_error("%s: NULL argument", fn); return RT_E_INVALID; }
+  if (npoints < 0 || npoints > (int64_t(1) << 31)) { set_error("%s: npoints = %lld outside [0, 2^31]", fn, (long long)npoints); return RT_E_INVALID; }
+  return RT_OK;
+}
+
+// One shade call of a single-device context on stream s (device buffers of c->device); npoints > 0, arguments checked
+static int enqueue_shade(rt_ctx* c, const float* d_points6, const int* d_seeds, long npoints, const float light[3], float* d_light,
+                         int* d_cnt, hipStream_t s) {
+  HIP_TRY(hipSetDevice(c->device));
+  const bool tiled = c->d_verts_m != nullptr;
+  const size_t stats_bytes = (size_t)shade_stats_words() * sizeof(unsigned long long);
+  if (!c->ev_shade) HIP_TRY(hipEventCreateWithFlags(&c->ev_shade, hipEventDisableTiming));
+  if (!c->d_sstats && hipMalloc(&c->d_sstats, stats_bytes) != hipSuccess) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
+  }
+  const float zero3[3] = {0.f, 0.f, 0.f}, ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  FrameParams P;
+  fill_params(c, ident, zero3, light, 1.0f, &P);
+  if (tiled) use_tiled_scene(c, &P);
+  HIP_TRY(wait_scene(c, s));
+  if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));
+  if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));
+  HIP_TRY(hipMemsetAsync(c->d_sstats, 0, stats_bytes, s));
+  launch_shade(P, tiled, d_points6, d_seeds, npoints, d_light, d_cnt, c->d_sstats, c->cus, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev_shade, s));
+  c->shade_pending = true;
+  c->shade_tiles = tiled ? mesh_tiles(c->n) : 0;
+  return RT_OK;
+}
+
+int rt_shade_points_device(rt_ctx* c, const void* d_points6, const void* d_seeds, int64_t npoints, const float light[3],
+                           void* d_out_light, void* d_out_unshadowed, void* hip_stream) {
+  const int rc = check_shade_args(c, d_points6, npoints, light, d_out_light, "rt_shade_points_device");
+  if (rc != RT_OK || npoints == 0) return rc;
+  if (!c->kids.empty()) c = c->kids[0];
+  DeviceGuard guard;
+  return enqueue_shade(c, (const float*)d_points6, (const int*)d_seeds, (long)npoints, light, (float*)d_out_light,
+                       (int*)d_out_unshadowed, (hipStream_t)hip_stream);
+}
+
+int rt_shade_points(rt_ctx* c, const float* points6, const int32_t* seeds, int64_t npoints, const float light[3], float* out_light,
+                    int32_t* out_unshadowed) {
+  int rc = check_shade_args(c, points6, npoints, light, out_light, "rt_shade_points");
+  if (rc != RT_OK) return rc;
+  if (seeds)                                  // the domain of global_id: beyond 2^24 the reference's float products lose the id
+    for (int64_t k = 0; k < npoints; ++k)
+      if (seeds[k] < 0 || seeds[k] > (1 << 24)) {
+        set_error("rt_shade_points: seeds[%lld] = %d outside [0, 2^24]", (long long)k, seeds[k]); return RT_E_INVALID;
+      }
+  if (npoints == 0) return RT_OK;
+  if (!c->kids.empty()) c = c->kids[0];
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)npoints;
+  const size_t o_seed = n * 24, o_light = o_seed + (seeds ? n * 4 : 0), o_cnt = o_light + n * 4, bytes = o_cnt + (out_unshadowed ? n * 4 : 0);
+  if (bytes > c->sio_bytes) {                 // (only this blocking entry uses the buffer: nothing can still be reading it)
+    hipFree(c->d_sio);
+    c->d_sio = nullptr; c->sio_bytes = 0;
+    if (hipMalloc(&c->d_sio, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
+    c->sio_bytes = bytes;
+  }
+  char* const d = c->d_sio;
+  HIP_TRY(hipMemcpyAsync(d, points6, n * 24, hipMemcpyHostToDevice, c->stream));
+  if (seeds) HIP_TRY(hipMemcpyAsync(d + o_seed, seeds, n * 4, hipMemcpyHostToDevice, c->stream));
+  rc = enqueue_shade(c, (const float*)d, seeds ? (const int*)(d + o_seed) : nullptr, (long)npoints, light, (float*)(d + o_light),
+                     out_unshadowed ? (int*)(d + o_cnt) : nullptr, c->stream);
+  if (rc != RT_OK) { hipStreamSynchronize(c->stream); return rc; }
+  HIP_TRY(hipMemcpyAsync(out_light, d + o_light, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (out_unshadowed) HIP_TRY(hipMemcpyAsync(out_unshadowed, d + o_cnt, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_debug_shade_stats(rt_ctx* c, uint64_t out[8]) {
+  if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
+  memset(out, 0, 8 * sizeof(uint64_t));
+  if (!c->kids.empty()) c = c->kids[0];
+  if (!c->shade_pending) return RT_OK;
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->ev_shade));
+  HIP_TRY(hipMemcpy(out, c->d_sstats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  out[3] = (uint64_t)c->shade_tiles;
   return RT_OK;
 }
 
@@ -1688,6 +1792,8 @@ void rt_destroy(rt_ctx* c) {
   if (c->ev_upd) hipEventDestroy(c->ev_upd);
   if (c->ev_query) { hipEventSynchronize(c->ev_query); hipEventDestroy(c->ev_query); }
   hipFree(c->d_qstats); hipFree(c->d_qrecords); hipFree(c->d_qio);
+  if (c->ev_shade) { hipEventSynchronize(c->ev_shade); hipEventDestroy(c->ev_shade); }
+  hipFree(c->d_sstats); hipFree(c->d_sio);
   if (c->ev_aov) { hipEventSynchronize(c->ev_aov); hipEventDestroy(c->ev_aov); }
   hipFree(c->d_astats); hipFree(c->d_aov);
   hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);

@@ -5,14 +5,11 @@
 // Contexts without a tiled copy (n <= 64, RT_FLAG_GENERIC_KERNEL): rt_query_flat, one lane per ray over the whole scene
 // in original order, the scene staged in LDS once per workgroup (or, beyond one LDS stage, the query's own records).
 // Tiled contexts (n > 64): rt_query_tiled, persistent waves, 64 consecutive rays per wave:
-//   1. lane = tile, 64 tiles per pass: the wave's rays bounded as one bundle (bounce_bundle) against each tile's box,
-//      normal cone and sliver measure (tile_clear_for_bundle, rt_tiles.h) -> the candidate tiles of the pass;
-//   2. per candidate tile, the same certificate for each lane's own ray (es = ed = 0), ballot: no lane -> next tile;
-//   3. the tile's records v0|material, e1|original index, e2, c = cof(e1, e2) are built into the wave's LDS from the tiled
-//      copy, lane = triangle bounds the bundle (task_bound; on curved meshes the tiles' normal cones are wide, and this is
-//      where most of the work goes away) and lane = ray tests the survivors with the reference's
-//      arithmetic: closest hit carried across tiles with the original-order tie rule (closer), shadow any-hit with an
-//      early exit per lane and per wave;
+//   1.-3. tile_walk (rt_tiles.h, shared with rt_shade.hip): the bundle bound per tile, the per-lane tile certificate, the
+//      tile's records in the wave's LDS with lane = triangle bounding the bundle (task_bound; on curved meshes the tiles'
+//      normal cones are wide, and this is where most of the work goes away) and lane = ray testing the survivors with the
+//      reference's arithmetic: closest hit carried across tiles with the original-order tie rule (closer), shadow any-hit
+//      with an early exit per lane and per wave;
 //   4. the hit is finished from the tiled arrays (set_hit arithmetic), then the spheres (closest_spheres / shadow_spheres).
 // Every skip is a certificate that the reference's test cannot accept, so skipping changes no bit.  The certificates are
 // verified for |start| <= 2^16 and 2^-20 <= max |direction component| <= 2^16 (finite); a ray outside that domain
@@ -28,7 +25,6 @@ namespace uobrt {
 namespace {
 
 constexpr int kQueryWaves = 4;              // waves per workgroup of rt_query_tiled (independent: no barriers between them)
-constexpr int kQTile = 64;                  // triangles per tile of the tiled copy (rt_kernel_mesh.hip kTile)
 // Work counters of a query (rt_debug_trace_stats), then the tiled kernel's queue head
 enum { Q_RAYS, Q_WAVES, Q_TILES, Q_BUNDLE_TILES, Q_TESTED_TILES, Q_TRI_TESTS, Q_UNCULLED, Q_SLOTS = 8 };
 
@@ -98,17 +94,14 @@ __global__ __launch_bounds__(256) void rt_query_flat(const FrameParams P, const 
 
 // Tiled contexts (P = the tiled copy: verts / normals / colors / orig / tile_box of use_tiled_scene).  Persistent waves pull
 // 64-ray groups from the queue head behind the counters; see the top of the file for the four steps.
+// (amdgpu_waves_per_eu(5): with the walk in a shared function the closest-hit instantiation is allocated 102 vector registers
+// instead of 93, i.e. 4 waves per SIMD instead of 5; held to 5 it takes 96, without spills)
 template <bool SHADOW>
-__global__ __launch_bounds__(64 * kQueryWaves) void rt_query_tiled(const FrameParams P, const float* __restrict__ rays,
-                                                                    const float* __restrict__ r2, long nray, int* __restrict__ out_tri,
-                                                                    float* __restrict__ out10, unsigned long long* __restrict__ stats) {
+__global__ __launch_bounds__(64 * kQueryWaves) __attribute__((amdgpu_waves_per_eu(5)))
+void rt_query_tiled(const FrameParams P, const float* __restrict__ rays, const float* __restrict__ r2, long nray,
+                    int* __restrict__ out_tri, float* __restrict__ out10, unsigned long long* __restrict__ stats) {
   __shared__ float4 s_tile[kQueryWaves][4 * kQTile];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float4* const tv0 = s_tile[wave];             // v0 | material
-  float4* const te1 = tv0 + kQTile;             // e1 | original index
-  float4* const te2 = tv0 + 2 * kQTile;         // e2
-  float4* const tc = tv0 + 3 * kQTile;          // cof(e1, e2)
-  const int n = P.n, ntiles = (n + kQTile - 1) / kQTile;
   const long ngroups = (nray + 63) >> 6;
   unsigned int* const head = reinterpret_cast<unsigned int*>(stats + Q_SLOTS);
   unsigned long long w[Q_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -128,82 +121,10 @@ __global__ __launch_bounds__(64 * kQueryWaves) void rt_query_tiled(const FramePa
       d = mk(rays[6 * k + 3], rays[6 * k + 4], rays[6 * k + 5]);
       if (SHADOW) rsq = r2[k];
     }
-    const bool indom = act && in_query_domain(o, d);
-    const bool brute = act && !indom;             // every tile, every triangle
-    const unsigned long long brm = ballot(brute);
-    w[Q_RAYS] += __popcll(ballot(act)); w[Q_WAVES] += 1; w[Q_UNCULLED] += __popcll(brm);
-    // the wave's bundle (only while no lane is outside the domain: such a lane needs every tile anyway)
-    const BounceBundle bnd = bounce_bundle(indom, o, d);
-    const bool bundle_ok = brm == 0ull && bnd.mode == 1;
-    const float d2 = 1.0001f * bsqrt(wave_max_pos(indom ? dot3(d, d) : 0.0f)) * 1.0001f;   // >= |d|_2 of every ray of the bundle
-    const float dl = 1.0001f * bsqrt(dot3(d, d)) * 1.0001f;                               // >= |d|_2 of this lane's ray
-    const f3 nd = -d;
     TileHit h = no_hit();
     bool blocked = false;
-    bool done = false;                            // SHADOW: every lane of the wave has found its blocker
-    for (int base = 0; base < ntiles && !done; base += 64) {
-      const int t = base + lane;
-      bool need = t < ntiles;
-      if (need && bundle_ok) need = !tile_clear_for_bundle(P.tile_box + (size_t)3 * t, bnd.s0, bnd.D0, bnd.es, bnd.ed, d2);
-      const unsigned long long cand = ballot(need);
-      w[Q_BUNDLE_TILES] += __popcll(cand);
-      for (unsigned long long m = uniform64(cand); m != 0ull; m &= m - 1ull) {
-        const int tt = base + __builtin_ctzll(m);
-        bool mine = act && !(SHADOW && blocked);
-        if (mine && !brute) mine = !tile_clear_for_bundle(P.tile_box + (size_t)3 * tt, o, d, 0.0f, 0.0f, dl);
-        if (ballot(mine) == 0ull) continue;
-        wave_lds_sync();                          // the previous tile's records are no longer read
-        {
-          const int gi = tt * kQTile + lane;
-          if (gi < n) {
-            const f3 v0 = xyz(P.verts[3 * gi]), e1 = xyz(P.verts[3 * gi + 1]) - v0, e2 = xyz(P.verts[3 * gi + 2]) - v0;
-            const f3 cf = cof(e1, e2);
-            tv0[lane] = make_float4(v0.x, v0.y, v0.z, P.colors[gi].w);
-            te1[lane] = make_float4(e1.x, e1.y, e1.z, __int_as_float(P.orig[gi]));
-            te2[lane] = make_float4(e2.x, e2.y, e2.z, 0.f);
-            tc[lane] = make_float4(cf.x, cf.y, cf.z, 0.f);
-          } else {
-            tv0[lane] = make_float4(0.f, 0.f, 0.f, -1.0f);
-            te1[lane] = te2[lane] = tc[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
-          }
-        }
-        wave_lds_sync();
-        const int nc = (n - tt * kQTile) < kQTile ? (n - tt * kQTile) : kQTile;
-        unsigned long long K = nc == 64 ? ~0ull : ((1ull << nc) - 1ull);
-        if (SHADOW) K &= ~ballot(tv0[lane].w == -1.0f);                 // glass casts no shadow (kernels.cl:250)
-        if (bundle_ok)
-          K &= ~ballot(task_bound(tri_lane(tv0, te1, te2, tc, lane), bnd.s0, bnd.D0, bnd.es, bnd.ed, 2e-6f * bnd.dl, 0.0f, bnd.dl).clear);
-        if (K == 0ull) continue;
-        w[Q_TESTED_TILES] += 1;
-        if (mine) {
-          // (uniform64: a loop inside a divergent `if` otherwise keeps its wave-uniform mask in vector registers)
-          for (unsigned long long mm = uniform64(K); mm != 0ull; mm &= mm - 1ull) {
-            const int i = __builtin_ctzll(mm);
-            ++tests;
-            const float4 e14 = te1[i];
-            const f3 v0 = xyz(tv0[i]), e1 = xyz(e14), e2 = xyz(te2[i]), c = xyz(tc[i]);
-            const f3 b = o - v0;
-            const float detA_recip = rcp_exact(detc(nd, c));
-            const float tq = detc(b, c) * detA_recip;
-            if (SHADOW) {                                               // kernels.cl:258-274
-              const f3 dv = tq * d;
-              const float dist = dv.x * dv.x + dv.y * dv.y + dv.z * dv.z;
-              if (tq >= 0 && dist < rsq) {
-                const float u = detc(nd, cof(b, e2)) * detA_recip;
-                const float v = detc(nd, cof(e1, b)) * detA_recip;
-                if (u >= 0 && v >= 0 && (u + v) <= 1) { blocked = true; break; }
-              }
-            } else {                                                    // kernels.cl:176-206
-              const float u = detc(nd, cof(b, e2)) * detA_recip;
-              const float v = detc(nd, cof(e1, b)) * detA_recip;
-              const int oi = __float_as_int(e14.w);
-              if (u >= 0 && v >= 0 && (u + v) <= 1 && tq >= 0 && closer(tq, oi, h)) h = TileHit{tq, u, v, tt * kQTile + i, oi};
-            }
-          }
-        }
-        if (SHADOW && ballot(act && !blocked) == 0ull) { done = true; break; }
-      }
-    }
+    w[Q_RAYS] += __popcll(ballot(act)); w[Q_WAVES] += 1;
+    tile_walk<SHADOW>(P, s_tile[wave], lane, act, o, d, rsq, h, blocked, w[Q_UNCULLED], w[Q_BUNDLE_TILES], w[Q_TESTED_TILES], tests);
     if (act) {
       if (SHADOW) {
         out_tri[k] = (blocked || shadow_spheres<false>(P, o, d, rsq, wk)) ? 1 : 0;

@@ -1,5 +1,5 @@
 // rt_tiles.h — the exact tile certificate and the closest-hit tie rule of the tiled mesh copy, shared by the mesh kernel
-// (rt_kernel_mesh.hip, bounce rays), the ray queries (rt_ray_query.hip) and the AOV pass (rt_aov.hip).  Include after rt_wave_common.h.
+// (rt_kernel_mesh.hip, bounce rays), the ray queries (rt_ray_query.hip), rt_shade_points (rt_shade.hip) and the AOV pass (rt_aov.hip).  Include after rt_wave_common.h.
 #pragma once
 #include "rt_wave_common.h"
 
@@ -79,7 +79,110 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
   return v;
 }
 
-constexpr int kScreenCell = 32;             // pixels per side of a screen cell of the primary-ray tile masks
+// ---- the tiled walk of caller rays, shared by the ray queries (rt_ray_query.hip) and rt_shade_points (rt_shade.hip) ----
+constexpr int kQTile = 64;                  // triangles per tile of the tiled copy (rt_kernel_mesh.hip kTile)
+
+// One lane = one ray (start o, direction d; SHADOW: radius_sq rsq) of a wave's 64, `act` = the lane has one; call with all
+// 64 lanes.  P = the tiled copy (use_tiled_scene), tile = 4 * kQTile float4 of LDS that belong to this wave.
+//   1. lane = tile, 64 tiles per pass: the wave's rays bounded as one bundle (bounce_bundle) against each tile's box,
+//      normal cone and sliver measure (tile_clear_for_bundle) -> the candidate tiles of the pass;
+//   2. per candidate tile, the same certificate for each lane's own ray (es = ed = 0), ballot: no lane -> next tile;
+//   3. the tile's records v0|material, e1|original index, e2, c = cof(e1, e2) are built into the wave's LDS from the tiled
+//      copy, lane = triangle bounds the bundle (task_bound) and lane = ray tests the survivors with the reference's
+//      arithmetic: closest hit carried across tiles in h with the original-order tie rule (closer), or (SHADOW) any-hit
+//      into `blocked` with an early exit per lane and per wave.
+// A ray outside in_query_domain takes every tile and every triangle.  The spheres are the caller's.
+// BOXES = false: P is a scene WITHOUT a tiled copy (n <= 64, RT_FLAG_GENERIC_KERNEL) — its triangles in their own order cut into
+// runs of 64, no tile data: steps 1 and 2 pass every run, step 3 is the same.
+// Counters (added to): rays outside the domain, (wave, tile) pairs left by the bundle test, pairs whose triangles were tested
+// (all three wave-uniform), and this LANE's triangle tests (the caller sums them over the wave).
+template <bool SHADOW, bool BOXES = true>
+__device__ __forceinline__ void tile_walk(const FrameParams& P, float4* tile, int lane, bool act, f3 o, f3 d, float rsq,
+                                          TileHit& h, bool& blocked, unsigned long long& n_unculled,
+                                          unsigned long long& n_bundle_tiles, unsigned long long& n_tested_tiles,
+                                          unsigned long long& lane_tests) {
+  float4* const tv0 = tile;                     // v0 | material
+  float4* const te1 = tv0 + kQTile;             // e1 | original index
+  float4* const te2 = tv0 + 2 * kQTile;         // e2
+  float4* const tc = tv0 + 3 * kQTile;          // cof(e1, e2)
+  const int n = P.n, ntiles = (n + kQTile - 1) / kQTile;
+  const bool indom = act && in_query_domain(o, d);
+  const bool brute = act && !indom;             // every tile, every triangle
+  const unsigned long long brm = ballot(brute);
+  n_unculled += __popcll(brm);
+  // the wave's bundle (only while no lane is outside the domain: such a lane needs every tile anyway)
+  const BounceBundle bnd = bounce_bundle(indom, o, d);
+  const bool bundle_ok = brm == 0ull && bnd.mode == 1;
+  const float d2 = 1.0001f * bsqrt(wave_max_pos(indom ? dot3(d, d) : 0.0f)) * 1.0001f;   // >= |d|_2 of every ray of the bundle
+  const float dl = 1.0001f * bsqrt(dot3(d, d)) * 1.0001f;                               // >= |d|_2 of this lane's ray
+  const f3 nd = -d;
+  bool done = false;                            // SHADOW: every lane of the wave has found its blocker
+  for (int base = 0; base < ntiles && !done; base += 64) {
+    const int t = base + lane;
+    bool need = t < ntiles;
+    if (BOXES && need && bundle_ok) need = !tile_clear_for_bundle(P.tile_box + (size_t)3 * t, bnd.s0, bnd.D0, bnd.es, bnd.ed, d2);
+    const unsigned long long cand = ballot(need);
+    n_bundle_tiles += __popcll(cand);
+    for (unsigned long long m = uniform64(cand); m != 0ull; m &= m - 1ull) {
+      const int tt = base + __builtin_ctzll(m);
+      bool mine = act && !(SHADOW && blocked);
+      if (BOXES && mine && !brute) mine = !tile_clear_for_bundle(P.tile_box + (size_t)3 * tt, o, d, 0.0f, 0.0f, dl);
+      if (ballot(mine) == 0ull) continue;
+      wave_lds_sync();                          // the previous tile's records are no longer read
+      {
+        const int gi = tt * kQTile + lane;
+        if (gi < n) {
+          const f3 v0 = xyz(P.verts[3 * gi]), e1 = xyz(P.verts[3 * gi + 1]) - v0, e2 = xyz(P.verts[3 * gi + 2]) - v0;
+          const f3 cf = cof(e1, e2);
+          tv0[lane] = make_float4(v0.x, v0.y, v0.z, P.colors[gi].w);
+          te1[lane] = make_float4(e1.x, e1.y, e1.z, __int_as_float(BOXES ? P.orig[gi] : gi));
+          te2[lane] = make_float4(e2.x, e2.y, e2.z, 0.f);
+          tc[lane] = make_float4(cf.x, cf.y, cf.z, 0.f);
+        } else {
+          tv0[lane] = make_float4(0.f, 0.f, 0.f, -1.0f);
+          te1[lane] = te2[lane] = tc[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+      wave_lds_sync();
+      const int nc = (n - tt * kQTile) < kQTile ? (n - tt * kQTile) : kQTile;
+      unsigned long long K = nc == 64 ? ~0ull : ((1ull << nc) - 1ull);
+      if (SHADOW) K &= ~ballot(tv0[lane].w == -1.0f);                 // glass casts no shadow (kernels.cl:250)
+      if (bundle_ok)
+        K &= ~ballot(task_bound(tri_lane(tv0, te1, te2, tc, lane), bnd.s0, bnd.D0, bnd.es, bnd.ed, 2e-6f * bnd.dl, 0.0f, bnd.dl).clear);
+      if (K == 0ull) continue;
+      n_tested_tiles += 1;
+      if (mine) {
+        // (uniform64: a loop inside a divergent `if` otherwise keeps its wave-uniform mask in vector registers)
+        for (unsigned long long mm = uniform64(K); mm != 0ull; mm &= mm - 1ull) {
+          const int i = __builtin_ctzll(mm);
+          ++lane_tests;
+          const float4 e14 = te1[i];
+          const f3 v0 = xyz(tv0[i]), e1 = xyz(e14), e2 = xyz(te2[i]), c = xyz(tc[i]);
+          const f3 b = o - v0;
+          const float detA_recip = rcp_exact(detc(nd, c));
+          const float tq = detc(b, c) * detA_recip;
+          if (SHADOW) {                                               // kernels.cl:258-274
+            const f3 dv = tq * d;
+            const float dist = dv.x * dv.x + dv.y * dv.y + dv.z * dv.z;
+            if (tq >= 0 && dist < rsq) {
+              const float u = detc(nd, cof(b, e2)) * detA_recip;
+              const float v = detc(nd, cof(e1, b)) * detA_recip;
+              if (u >= 0 && v >= 0 && (u + v) <= 1) { blocked = true; break; }
+            }
+          } else {                                                    // kernels.cl:176-206
+            const float u = detc(nd, cof(b, e2)) * detA_recip;
+            const float v = detc(nd, cof(e1, b)) * detA_recip;
+            const int oi = __float_as_int(e14.w);
+            if (u >= 0 && v >= 0 && (u + v) <= 1 && tq >= 0 && closer(tq, oi, h)) h = TileHit{tq, u, v, tt * kQTile + i, oi};
+          }
+        }
+      }
+      if (SHADOW && ballot(act && !blocked) == 0ull) { done = true; break; }
+    }
+  }
+}
+
+constexpr int kScreenCell = 32;            // pixels per side of a screen cell of the primary-ray tile masks
 constexpr int kScreenCellLog = 5;
 
 }  // namespace

@@ -30,12 +30,16 @@ EXPORTS = (
     "rt_debug_band_copy_plan", "rt_update_scene", "rt_update_scene_device", "rt_debug_tile_data",
     "rt_trace_rays", "rt_trace_rays_device", "rt_debug_trace_stats",
     "rt_render_aov", "rt_render_aov_device", "rt_debug_aov_stats",
+    "rt_shade_points", "rt_shade_points_device", "rt_debug_shade_stats",
 )
 
 # rt_debug_trace_stats slots (include/uob_rt.h)
 TRACE_STATS_KEYS = ("rays", "waves", "tiles", "bundle_tiles", "tested_tiles", "triangle_tests", "unculled_rays", "reserved")
 # rt_debug_aov_stats slots
 AOV_STATS_KEYS = ("samples", "waves", "tiles", "mask_tiles", "tested_tiles", "triangle_tests", "reserved6", "reserved7")
+
+# rt_debug_shade_stats slots
+SHADE_STATS_KEYS = ("points", "sample_rays", "waves", "tiles", "bundle_tiles", "tested_tiles", "triangle_tests", "skipped_points")
 
 _lib = None
 
@@ -80,6 +84,9 @@ def lib():
         L.rt_render_aov.argtypes = [vp, fp, fp, C.c_float, C.c_int32, C.POINTER(abi.RtAovBuffers)]
         L.rt_render_aov_device.argtypes = [vp, fp, fp, C.c_float, C.c_int32, C.POINTER(abi.RtAovBuffers), vp]
         L.rt_debug_aov_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_shade_points.argtypes = [vp, fp, C.POINTER(C.c_int32), C.c_int64, fp, fp, C.POINTER(C.c_int32)]
+        L.rt_shade_points_device.argtypes = [vp, vp, vp, C.c_int64, fp, vp, vp, vp]
+        L.rt_debug_shade_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_debug_block_costs.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int32]
         L.rt_debug_world_masks.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.rt_debug_wave_timeline.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -445,6 +452,103 @@ class RayTracer:
         out = (C.c_uint64 * 8)()
         _check(lib().rt_debug_aov_stats(self._h, out))
         return {key: int(out[i]) for i, key in enumerate(AOV_STATS_KEYS)}
+
+    def shade_points(self, points, normals, light, seeds=None, want_counts=False):
+        """Soft-shadowed direct light at caller points (rt_shade_points), blocking: points, normals [k,3] (intersect and
+        intersect_normal, e.g. the AOV position / normal planes), seeds int32 [k] = the global_id of each point's jitter
+        stream (None: k & 0xFFFFFF; the frame uses the pixel id) -> light float32 [k], one channel of the reference's
+        direct_light; with want_counts also the unblocked samples int32 [k] (0 .. shadow_samples)."""
+        p = np.asarray(points, np.float32).reshape(-1, 3)
+        nr = np.asarray(normals, np.float32).reshape(-1, 3)
+        if p.shape != nr.shape:
+            raise ValueError("points and normals must have the same shape [k, 3]")
+        k = p.shape[0]
+        p6 = np.ascontiguousarray(np.concatenate([p, nr], 1), np.float32)
+        li = np.ascontiguousarray(light, np.float32)[:3].copy()
+        sp = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, np.int32).reshape(-1)
+            if seeds.shape[0] != k:
+                raise ValueError("seeds must have one entry per point")
+            sp = seeds.ctypes.data_as(C.POINTER(C.c_int32))
+        out = np.zeros(k, np.float32)
+        cnt = np.zeros(k, np.int32) if want_counts else None
+        _check(lib().rt_shade_points(self._h, _fp(p6), sp, k, _fp(li), _fp(out),
+                                     cnt.ctypes.data_as(C.POINTER(C.c_int32)) if want_counts else None))
+        return (out, cnt) if want_counts else out
+
+    def shade_points_device(self, points6, light, seeds=None, out_light=None, out_counts=None, want_counts=False, stream=None):
+        """Enqueue rt_shade_points_device on torch tensors of the context's device, without synchronising.  points6: float32
+        [k,6] (position, normal); seeds: int32 [k] or None; out_light: float32 [k]; out_counts: int32 [k] (allocated when
+        want_counts).  stream: a torch stream or a raw hipStream_t (default: torch's current stream).  Returns out_light, or
+        (out_light, out_counts) when counts are asked for."""
+        import torch
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+
+        def _need(name, t, dtype, shape):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch tensor" % name)
+            if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
+                                 % (name, dtype, shape, dev, t.dtype, tuple(t.shape), t.device))
+
+        if not isinstance(points6, torch.Tensor) or points6.dim() != 2:
+            raise ValueError("points6 must be a torch tensor of shape [k, 6]")
+        k = points6.shape[0]
+        _need("points6", points6, torch.float32, (k, 6))
+        if seeds is not None:
+            _need("seeds", seeds, torch.int32, (k,))
+        if out_light is None:
+            out_light = torch.empty(k, dtype=torch.float32, device=dev)
+        _need("out_light", out_light, torch.float32, (k,))
+        if out_counts is None and want_counts:
+            out_counts = torch.empty(k, dtype=torch.int32, device=dev)
+        if out_counts is not None:
+            _need("out_counts", out_counts, torch.int32, (k,))
+        li = np.ascontiguousarray(light, np.float32)[:3].copy()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        raw = getattr(stream, "cuda_stream", stream) or 0
+        if k:
+            _check(lib().rt_shade_points_device(self._h, C.c_void_p(points6.data_ptr()),
+                                                C.c_void_p(seeds.data_ptr() if seeds is not None else 0), k, _fp(li),
+                                                C.c_void_p(out_light.data_ptr()),
+                                                C.c_void_p(out_counts.data_ptr() if out_counts is not None else 0),
+                                                C.c_void_p(raw)))
+        return out_light if out_counts is None else (out_light, out_counts)
+
+    def render_direct_light(self, rot, cam, light, focal, sample=0):
+        """The direct light of every pixel's primary hit, on the device: an AOV pass (position, normal, prim of AA sample
+        `sample`) and a shade call seeded with the global pixel id, as the frame seeds it -> torch float32 [rows, W], 0 where
+        the pixel sees nothing.  For a diffuse hit, albedo.xyz * (0.5 + light) is that sample's colour in the frame.
+        Runs on torch's current stream; does not synchronise.  sample is one AA sample index (not RT_AOV_ALL_SAMPLES: the
+        result is one value per pixel); a context of row bands gets its owned rows, seeded with the global ids; frames of
+        more than 2^24 pixels are refused (the ids leave the seed domain and the frame's own ids are formed in FP32)."""
+        import torch
+        aa = self.cfg.aa_x * self.cfg.aa_y
+        if sample is None or isinstance(sample, bool) or int(sample) != sample or not 0 <= int(sample) < aa:
+            raise ValueError("sample must be one AA sample index in [0, %d)" % aa)
+        if self.cfg.width * self.cfg.height > abi.RT_SHADE_SEED_MAX:
+            raise ValueError("render_direct_light: %d x %d pixels exceed the seed domain of 2^24 ids" % (self.cfg.width, self.cfg.height))
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        shape = (self.rows, self.width)
+        planes = {"prim": torch.empty(shape, dtype=torch.int32, device=dev),
+                  "position": torch.empty(shape + (4,), dtype=torch.float32, device=dev),
+                  "normal": torch.empty(shape + (4,), dtype=torch.float32, device=dev)}
+        self.render_aov_device(rot, cam, focal, sample=sample, out=planes)
+        cfg = self.cfg
+        br, bc = (cfg.band_rows if cfg.band_rows > 0 else cfg.height), max(cfg.band_count, 1)
+        ys = torch.tensor([y for y in range(cfg.height) if (y // br) % bc == cfg.band_index], dtype=torch.int32, device=dev)
+        seeds = (ys[:, None] * self.width + torch.arange(self.width, dtype=torch.int32, device=dev)[None, :]).reshape(-1).contiguous()
+        p6 = torch.cat([planes["position"][..., :3], planes["normal"][..., :3]], -1).reshape(-1, 6).contiguous()
+        out = self.shade_points_device(p6, light, seeds=seeds)
+        return torch.where(planes["prim"].reshape(-1) != -1, out, torch.zeros_like(out)).reshape(shape)
+
+    def shade_stats(self):
+        """Work counters of the context's most recent shade call (rt_debug_shade_stats): dict of SHADE_STATS_KEYS."""
+        out = (C.c_uint64 * 8)()
+        _check(lib().rt_debug_shade_stats(self._h, out))
+        return {key: int(out[i]) for i, key in enumerate(SHADE_STATS_KEYS)}
 
     def trace_stats(self):
         """Work counters of the context's most recent query (rt_debug_trace_stats): dict of TRACE_STATS_KEYS."""
