@@ -236,6 +236,54 @@ int rt_shade_points_device(rt_ctx* ctx, const void* d_points6, const void* d_see
  * tested, out[6] lane-level triangle tests, out[7] points not traced because their term is 0.                             */
 int rt_debug_shade_stats(rt_ctx* ctx, uint64_t out[8]);
 
+/* ---- the frame's full colour for caller rays (rt_radiance.hip) ----------------------------------------
+ * What rt_render computes for one AA sample of a pixel — closest hit, the reflect / refract bounce loop, soft-shadowed
+ * direct light, the colour rule — for rays the caller supplies, on the context's scene as its latest update left it: any
+ * camera the pinhole cannot express (panoramas, cube-map probes, fisheye and stereo rigs, lens samples for depth of field),
+ * or the colour along a picking ray.  With the `direction` plane of rt_render_aov as the rays and the pixel ids as the seeds,
+ * the per-pixel sum in sample order / aa is rt_render's out_rgb_f32, bit for bit, on every pixel.
+ *   rays6   = float32 [nray][6]: start.xyz, direction.xyz (rt_trace_rays' layout).  The direction is used as given, not
+ *             normalised.  A ray starts in air: medium AIR, colour w = 1, intersect_triangle = -1 (kernels.cl:400-405).
+ *   seeds   = nullable int32 [nray]: the global_id of the ray's jitter stream, 0 .. 2^24 (the frame uses the pixel id
+ *             y * width + x); NULL = k & 0xFFFFFF.  rt_radiance_rays rejects a seed outside the domain with RT_E_INVALID
+ *             before any device work; in rt_radiance_rays_device such a seed yields an unspecified colour.
+ *   out_rgba4 = float32 [nray][4], 16-byte aligned.  xyz is the colour:
+ *             the first hit is single_ray_intersections (kernels.cl:168-241), the bits of rt_trace_rays(RT_TRACE_CLOSEST_HIT);
+ *             miss: (0, 0, 0);
+ *             diffuse hit (albedo w > 0; exactly: not w <= 0): albedo.xyz * (0.5f + L);
+ *             mirror or glass hit (w <= 0): secondary_light (kernels.cl:342-365) with the context's max_bounces — while
+ *             b < max_bounces and the hit's w <= 0: reflect_ray (w == 0) or refract_ray (w < 0; n = n1 / n2 in FP32, the
+ *             medium carried from bounce to bounce), start = P + 0.0001f * dir with the UNnormalised new direction, then the
+ *             direction normalised, closest hit again; at the first hit with w > 0 the colour is
+ *             (0.9f * (0.5f + L)) * albedo.xyz, and (0, 0, 0) if the loop ends on a miss or runs out;
+ *             L is exactly rt_shade_points' out_light for (that hit's position, its normal, the ray's seed, light), with the
+ *             context's shadow_samples and light_spread.  FP32 without contraction, operation order of the reference.
+ *             w is 1.0f when the first hit exists and 0.0f on a miss: coverage, for compositing over a background.
+ *   out_prim  = nullable int32 [nray]: the first hit, -1 / -2 / the ORIGINAL triangle index (as rt_trace_rays' out_tri).
+ * NaN and non-finite rays give what the arithmetic gives: they hit nothing, so the result is zero.  Rays outside the domain
+ * of the exact culls (finite, |start| <= 2^16, 2^-20 <= max |direction component| <= 2^16) are traced without culling; that
+ * holds for the bounce rays and the sample rays of a call as well.
+ * A NULL ctx / rays6 / light / out_rgba4 and nray < 0 or > 2^31 are RT_E_INVALID, before any device work; nray == 0 is a
+ * no-op.  Ordering is rt_shade_points': a radiance call touches none of the per-frame buffers, frames do not wait for it and
+ * it does not wait for frames; it waits for the scene update, query, shade call and radiance call before it, and the
+ * context's next query, shade call, radiance call and scene update (and rt_destroy) wait for it.  A multi-device context
+ * runs it on devices[0].
+ * rt_radiance_rays: host arrays, blocking (staged through device memory the context keeps and grows on demand).
+ * rt_radiance_rays_device: device memory on the context's device, enqueued on hip_stream (NULL = default stream) after the
+ * caller's earlier work; returns without synchronising, and no stage of it waits for the host: how many rays reach a diffuse
+ * surface stays on the device.  The scratch between its stages (48 bytes per ray) belongs to the context and grows on
+ * demand; only a call with more rays than any before it allocates.                                                       */
+int rt_radiance_rays(rt_ctx* ctx, const float* rays6, const int32_t* seeds, int64_t nray, const float light[3],
+                     float* out_rgba4, int32_t* out_prim);
+int rt_radiance_rays_device(rt_ctx* ctx, const void* d_rays6, const void* d_seeds, int64_t nray, const float light[3],
+                            void* d_out_rgba4, void* d_out_prim, void* hip_stream);
+/* Diagnostic: work counters of the context's most recent radiance call (synchronises it; zeros before the first).  out[0]
+ * rays, out[1] bounce rays traced, out[2] rays that reached a diffuse surface (shaded points), out[3] shadow sample rays
+ * traced, out[4] (wave, tile) pairs whose triangles were tested by closest-hit walks, out[5] lane-level triangle tests of
+ * closest-hit walks, out[6] lane-level triangle tests of shadow walks, out[7] rays of any kind traced without culling
+ * (outside the certificates' domain).                                                                                     */
+int rt_debug_radiance_stats(rt_ctx* ctx, uint64_t out[8]);
+
 /* ---- AOV pass: what every pixel of a view sees (rt_aov.hip) ------------------------------------------
  * The planes describe the PRIMARY HIT of the frame that rt_render would render with the same rot, cam and focal on the
  * context's current scene (after rt_update_scene).  No light is involved.

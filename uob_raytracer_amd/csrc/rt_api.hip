@@ -68,6 +68,10 @@ void launch_query(const FrameParams& P, bool tiled, int what, const float* d_ray
 int shade_stats_words();
 void launch_shade(const FrameParams& P, bool tiled, const float* d_points6, const int* d_seeds, long npoints, float* d_light,
                   int* d_cnt, unsigned long long* stats, int cus, hipStream_t stream);
+int radiance_stats_words();
+size_t radiance_record_bytes(long nray);
+void launch_radiance(const FrameParams& P, bool tiled, const float* d_rays6, const int* d_seeds, long nray, float4* d_rgba,
+                     int* d_prim, float4* d_records, unsigned long long* stats, int cus, hipStream_t stream);
 
 }  // namespace uobrt
 
@@ -168,6 +172,15 @@ struct rt_ctx {
   int shade_tiles = 0;                      // tiles of the latest call's scene (0: no tiled copy)
   char* d_sio = nullptr;                    // rt_shade_points: device copies of the caller's host arrays
   size_t sio_bytes = 0;
+  // radiance calls (rt_radiance_rays_device, rt_radiance.hip): ordered like the shade calls, through ev_rad — they read only
+  // the scene; the next query, shade call, radiance call and scene update wait for the latest one
+  hipEvent_t ev_rad = nullptr;
+  bool rad_pending = false;
+  unsigned long long* d_rstats = nullptr;   // the latest call's work counters (+ the two kernels' queue heads)
+  char* d_rrec = nullptr;                   // the records its first stage leaves for its second (both entries)
+  size_t rrec_bytes = 0;
+  char* d_rio = nullptr;                    // rt_radiance_rays: device copies of the caller's host arrays
+  size_t rio_bytes = 0;
   // AOV passes (rt_render_aov_device, rt_aov.hip): frame-like — they use the frames' records and screen masks, so frames,
   // updates and later passes wait for the latest one through ev_aov; they touch none of the scheduling state above
   hipEvent_t ev_aov = nullptr;
@@ -870,6 +883,7 @@ static int update_begin(rt_ctx* c, hipStream_t s) {
   if (c->timed) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
   if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));    // ray queries still reading the scene
   if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));    // shade calls likewise
+  if (c->rad_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_rad, 0));        // and radiance calls
   HIP_TRY(wait_aov(c, s));
   HIP_TRY(wait_scene(c, s));
   return RT_OK;
@@ -1434,6 +1448,7 @@ static int enqueue_query(rt_ctx* c, int32_t what, const float* d_rays, const flo
   HIP_TRY(wait_scene(c, s));
   if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));
   if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));
+  if (c->rad_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_rad, 0));
   HIP_TRY(hipMemsetAsync(c->d_qstats, 0, stats_bytes, s));
   if (records) launch_stage_records(P, s);
   launch_query(P, tiled, what, d_rays, d_r2, nray, d_tri, what == RT_TRACE_CLOSEST_HIT ? d_out10 : nullptr, c->d_qstats, c->cus, s);
@@ -1520,6 +1535,7 @@ static int enqueue_shade(rt_ctx* c, const float* d_points6, const int* d_seeds, 
   HIP_TRY(wait_scene(c, s));
   if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));
   if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));
+  if (c->rad_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_rad, 0));
   HIP_TRY(hipMemsetAsync(c->d_sstats, 0, stats_bytes, s));
   launch_shade(P, tiled, d_points6, d_seeds, npoints, d_light, d_cnt, c->d_sstats, c->cus, s);
   HIP_TRY(hipGetLastError());
@@ -1582,6 +1598,106 @@ int rt_debug_shade_stats(rt_ctx* c, uint64_t out[8]) {
   HIP_TRY(hipEventSynchronize(c->ev_shade));
   HIP_TRY(hipMemcpy(out, c->d_sstats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
   out[3] = (uint64_t)c->shade_tiles;
+  return RT_OK;
+}
+
+// ---- radiance calls (rt_radiance_rays / rt_radiance_rays_device, rt_radiance.hip) --------------------------------------
+// Checked before the context is looked at, like the shade calls' arguments
+static int check_radiance_args(const rt_ctx* c, const void* rays6, int64_t nray, const float* light, const void* out_rgba4,
+                               const char* fn) {
+  if (!c || !rays6 || !light || !out_rgba4) { set_error("%s: NULL argument", fn); return RT_E_INVALID; }
+  if (nray < 0 || nray > (int64_t(1) << 31)) { set_error("%s: nray = %lld outside [0, 2^31]", fn, (long long)nray); return RT_E_INVALID; }
+  return RT_OK;
+}
+
+// One radiance call of a single-device context on stream s (device buffers of c->device); nray > 0, arguments checked
+static int enqueue_radiance(rt_ctx* c, const float* d_rays6, const int* d_seeds, long nray, const float light[3], float* d_rgba4,
+                            int* d_prim, hipStream_t s) {
+  HIP_TRY(hipSetDevice(c->device));
+  const bool tiled = c->d_verts_m != nullptr;
+  const size_t stats_bytes = (size_t)radiance_stats_words() * sizeof(unsigned long long);
+  if (!c->ev_rad) HIP_TRY(hipEventCreateWithFlags(&c->ev_rad, hipEventDisableTiming));
+  if (!c->d_rstats && hipMalloc(&c->d_rstats, stats_bytes) != hipSuccess) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
+  }
+  const size_t rec_bytes = radiance_record_bytes(nray);
+  if (rec_bytes > c->rrec_bytes) {            // (a larger call than any before: hipFree waits for the call still using the old one)
+    hipFree(c->d_rrec);
+    c->d_rrec = nullptr; c->rrec_bytes = 0;
+    if (hipMalloc(&c->d_rrec, rec_bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
+    c->rrec_bytes = rec_bytes;
+  }
+  const float zero3[3] = {0.f, 0.f, 0.f}, ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  FrameParams P;
+  fill_params(c, ident, zero3, light, 1.0f, &P);
+  if (tiled) use_tiled_scene(c, &P);
+  HIP_TRY(wait_scene(c, s));
+  if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));
+  if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));
+  if (c->rad_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_rad, 0));
+  HIP_TRY(hipMemsetAsync(c->d_rstats, 0, stats_bytes, s));
+  launch_radiance(P, tiled, d_rays6, d_seeds, nray, (float4*)d_rgba4, d_prim, (float4*)c->d_rrec, c->d_rstats, c->cus, s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev_rad, s));
+  c->rad_pending = true;
+  return RT_OK;
+}
+
+int rt_radiance_rays_device(rt_ctx* c, const void* d_rays6, const void* d_seeds, int64_t nray, const float light[3],
+                            void* d_out_rgba4, void* d_out_prim, void* hip_stream) {
+  const int rc = check_radiance_args(c, d_rays6, nray, light, d_out_rgba4, "rt_radiance_rays_device");
+  if (rc != RT_OK) return rc;
+  if (((uintptr_t)d_out_rgba4 & 15) != 0) { set_error("rt_radiance_rays_device: d_out_rgba4 is not 16-byte aligned"); return RT_E_INVALID; }
+  if (nray == 0) return rc;
+  if (!c->kids.empty()) c = c->kids[0];
+  DeviceGuard guard;
+  return enqueue_radiance(c, (const float*)d_rays6, (const int*)d_seeds, (long)nray, light, (float*)d_out_rgba4, (int*)d_out_prim,
+                          (hipStream_t)hip_stream);
+}
+
+int rt_radiance_rays(rt_ctx* c, const float* rays6, const int32_t* seeds, int64_t nray, const float light[3], float* out_rgba4,
+                     int32_t* out_prim) {
+  int rc = check_radiance_args(c, rays6, nray, light, out_rgba4, "rt_radiance_rays");
+  if (rc != RT_OK) return rc;
+  if (seeds)                                  // the domain of global_id, as for rt_shade_points
+    for (int64_t k = 0; k < nray; ++k)
+      if (seeds[k] < 0 || seeds[k] > (1 << 24)) {
+        set_error("rt_radiance_rays: seeds[%lld] = %d outside [0, 2^24]", (long long)k, seeds[k]); return RT_E_INVALID;
+      }
+  if (nray == 0) return RT_OK;
+  if (!c->kids.empty()) c = c->kids[0];
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)nray;
+  // (the colours first: the kernels store them as float4)
+  const size_t o_rays = n * 16, o_seed = o_rays + n * 24, o_prim = o_seed + (seeds ? n * 4 : 0), bytes = o_prim + (out_prim ? n * 4 : 0);
+  if (bytes > c->rio_bytes) {                 // (only this blocking entry uses the buffer: nothing can still be reading it)
+    hipFree(c->d_rio);
+    c->d_rio = nullptr; c->rio_bytes = 0;
+    if (hipMalloc(&c->d_rio, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
+    c->rio_bytes = bytes;
+  }
+  char* const d = c->d_rio;
+  HIP_TRY(hipMemcpyAsync(d + o_rays, rays6, n * 24, hipMemcpyHostToDevice, c->stream));
+  if (seeds) HIP_TRY(hipMemcpyAsync(d + o_seed, seeds, n * 4, hipMemcpyHostToDevice, c->stream));
+  rc = enqueue_radiance(c, (const float*)(d + o_rays), seeds ? (const int*)(d + o_seed) : nullptr, (long)nray, light, (float*)d,
+                        out_prim ? (int*)(d + o_prim) : nullptr, c->stream);
+  if (rc != RT_OK) { hipStreamSynchronize(c->stream); return rc; }
+  HIP_TRY(hipMemcpyAsync(out_rgba4, d, n * 16, hipMemcpyDeviceToHost, c->stream));
+  if (out_prim) HIP_TRY(hipMemcpyAsync(out_prim, d + o_prim, n * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_debug_radiance_stats(rt_ctx* c, uint64_t out[8]) {
+  if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
+  memset(out, 0, 8 * sizeof(uint64_t));
+  if (!c->kids.empty()) c = c->kids[0];
+  if (!c->rad_pending) return RT_OK;
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(c->ev_rad));
+  HIP_TRY(hipMemcpy(out, c->d_rstats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return RT_OK;
 }
 
@@ -1794,6 +1910,8 @@ void rt_destroy(rt_ctx* c) {
   hipFree(c->d_qstats); hipFree(c->d_qrecords); hipFree(c->d_qio);
   if (c->ev_shade) { hipEventSynchronize(c->ev_shade); hipEventDestroy(c->ev_shade); }
   hipFree(c->d_sstats); hipFree(c->d_sio);
+  if (c->ev_rad) { hipEventSynchronize(c->ev_rad); hipEventDestroy(c->ev_rad); }
+  hipFree(c->d_rstats); hipFree(c->d_rrec); hipFree(c->d_rio);
   if (c->ev_aov) { hipEventSynchronize(c->ev_aov); hipEventDestroy(c->ev_aov); }
   hipFree(c->d_astats); hipFree(c->d_aov);
   hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);

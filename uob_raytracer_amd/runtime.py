@@ -31,6 +31,7 @@ EXPORTS = (
     "rt_trace_rays", "rt_trace_rays_device", "rt_debug_trace_stats",
     "rt_render_aov", "rt_render_aov_device", "rt_debug_aov_stats",
     "rt_shade_points", "rt_shade_points_device", "rt_debug_shade_stats",
+    "rt_radiance_rays", "rt_radiance_rays_device", "rt_debug_radiance_stats",
 )
 
 # rt_debug_trace_stats slots (include/uob_rt.h)
@@ -40,6 +41,10 @@ AOV_STATS_KEYS = ("samples", "waves", "tiles", "mask_tiles", "tested_tiles", "tr
 
 # rt_debug_shade_stats slots
 SHADE_STATS_KEYS = ("points", "sample_rays", "waves", "tiles", "bundle_tiles", "tested_tiles", "triangle_tests", "skipped_points")
+
+# rt_debug_radiance_stats slots
+RADIANCE_STATS_KEYS = ("rays", "bounce_rays", "shaded_points", "sample_rays", "closest_tested_tiles", "closest_triangle_tests",
+                       "shadow_triangle_tests", "unculled_rays")
 
 _lib = None
 
@@ -87,6 +92,9 @@ def lib():
         L.rt_shade_points.argtypes = [vp, fp, C.POINTER(C.c_int32), C.c_int64, fp, fp, C.POINTER(C.c_int32)]
         L.rt_shade_points_device.argtypes = [vp, vp, vp, C.c_int64, fp, vp, vp, vp]
         L.rt_debug_shade_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_radiance_rays.argtypes = [vp, fp, C.POINTER(C.c_int32), C.c_int64, fp, fp, C.POINTER(C.c_int32)]
+        L.rt_radiance_rays_device.argtypes = [vp, vp, vp, C.c_int64, fp, vp, vp, vp]
+        L.rt_debug_radiance_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_debug_block_costs.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int32]
         L.rt_debug_world_masks.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.rt_debug_wave_timeline.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -549,6 +557,97 @@ class RayTracer:
         out = (C.c_uint64 * 8)()
         _check(lib().rt_debug_shade_stats(self._h, out))
         return {key: int(out[i]) for i, key in enumerate(SHADE_STATS_KEYS)}
+
+    def radiance_rays(self, rays, light, seeds=None, want_prim=False):
+        """The frame's full colour along caller rays (rt_radiance_rays), blocking: rays [k,6] = start, direction (used as
+        given), seeds int32 [k] = the global_id of each ray's jitter stream (None: k & 0xFFFFFF; the frame uses the pixel
+        id) -> rgba float32 [k,4]: xyz the colour rt_render gives that ray (bounces and soft shadows included), w = 1 where
+        the ray hits anything, else 0; with want_prim also the first hit int32 [k] (-1 / -2 / original triangle index)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        k = rays.shape[0]
+        li = np.ascontiguousarray(light, np.float32)[:3].copy()
+        sp = None
+        if seeds is not None:
+            seeds = np.ascontiguousarray(seeds, np.int32).reshape(-1)
+            if seeds.shape[0] != k:
+                raise ValueError("seeds must have one entry per ray")
+            sp = seeds.ctypes.data_as(C.POINTER(C.c_int32))
+        out = np.zeros((k, 4), np.float32)
+        prim = np.zeros(k, np.int32) if want_prim else None
+        _check(lib().rt_radiance_rays(self._h, _fp(rays), sp, k, _fp(li), _fp(out),
+                                      prim.ctypes.data_as(C.POINTER(C.c_int32)) if want_prim else None))
+        return (out, prim) if want_prim else out
+
+    def radiance_rays_device(self, rays6, light, seeds=None, out=None, out_prim=None, stream=None):
+        """Enqueue rt_radiance_rays_device on torch tensors of the context's device, without synchronising.  rays6: float32
+        [k,6] (start, direction); seeds: int32 [k] or None; out: float32 [k,4] (allocated when None); out_prim: int32 [k] or
+        None (not computed).  stream: a torch stream or a raw hipStream_t (default: torch's current stream).  Returns out,
+        or (out, out_prim) when out_prim is given."""
+        import torch
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+
+        def _need(name, t, dtype, shape):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch tensor" % name)
+            if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
+                                 % (name, dtype, shape, dev, t.dtype, tuple(t.shape), t.device))
+
+        if not isinstance(rays6, torch.Tensor) or rays6.dim() != 2:
+            raise ValueError("rays6 must be a torch tensor of shape [k, 6]")
+        k = rays6.shape[0]
+        _need("rays6", rays6, torch.float32, (k, 6))
+        if seeds is not None:
+            _need("seeds", seeds, torch.int32, (k,))
+        if out is None:
+            out = torch.empty((k, 4), dtype=torch.float32, device=dev)
+        _need("out", out, torch.float32, (k, 4))
+        if out_prim is not None:
+            _need("out_prim", out_prim, torch.int32, (k,))
+        li = np.ascontiguousarray(light, np.float32)[:3].copy()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        raw = getattr(stream, "cuda_stream", stream) or 0
+        if k:
+            _check(lib().rt_radiance_rays_device(self._h, C.c_void_p(rays6.data_ptr()),
+                                                 C.c_void_p(seeds.data_ptr() if seeds is not None else 0), k, _fp(li),
+                                                 C.c_void_p(out.data_ptr()),
+                                                 C.c_void_p(out_prim.data_ptr() if out_prim is not None else 0),
+                                                 C.c_void_p(raw)))
+        return out if out_prim is None else (out, out_prim)
+
+    def radiance_stats(self):
+        """Work counters of the context's most recent radiance call (rt_debug_radiance_stats): dict of RADIANCE_STATS_KEYS."""
+        out = (C.c_uint64 * 8)()
+        _check(lib().rt_debug_radiance_stats(self._h, out))
+        return {key: int(out[i]) for i, key in enumerate(RADIANCE_STATS_KEYS)}
+
+    def render_panorama(self, width, height, cam, light, yaw=0.0):
+        """An equirectangular 360 x 180 degree view from `cam`, on the device (rt_radiance_rays_device) -> torch float32
+        [height, width, 4], rgb the frame's colour and w the coverage.  Pixel (x, y) looks along
+            (sin(phi) * cos(theta), sin(theta), cos(phi) * cos(theta)),
+            phi = yaw + 2 * pi * (x + 0.5) / width - pi,   theta = pi * (y + 0.5) / height - pi / 2,
+        evaluated in float32 with torch on the device, left to right as written (x + 0.5 and y + 0.5 from float32 aranges;
+        2 * pi, pi and pi / 2 are the float32 values of math.pi's multiples; yaw a float32 scalar); the ray starts at cam
+        and its seed is (y * width + x) & 0xFFFFFF.  Runs on torch's current stream; does not synchronise."""
+        import math
+        import torch
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError("width and height must be positive")
+        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        f32 = dict(dtype=torch.float32, device=dev)
+        xs = (torch.arange(width, **f32) + 0.5) * torch.tensor(2.0 * math.pi, **f32) / torch.tensor(float(width), **f32)
+        phi = torch.tensor(float(yaw), **f32) + xs - torch.tensor(math.pi, **f32)
+        theta = (torch.arange(height, **f32) + 0.5) * torch.tensor(math.pi, **f32) / torch.tensor(float(height), **f32) \
+            - torch.tensor(math.pi / 2.0, **f32)
+        ct = torch.cos(theta)[:, None]
+        d = torch.stack([torch.sin(phi)[None, :] * ct, torch.sin(theta)[:, None].expand(height, width),
+                         torch.cos(phi)[None, :] * ct], -1)
+        start = torch.tensor(np.ascontiguousarray(cam, np.float32)[:3].copy(), device=dev).expand(height, width, 3)
+        rays = torch.cat([start, d], -1).reshape(-1, 6).contiguous()
+        seeds = (torch.arange(width * height, dtype=torch.int64, device=dev) & abi.RT_SHADE_SEED_MASK).to(torch.int32)
+        return self.radiance_rays_device(rays, light, seeds=seeds).reshape(height, width, 4)
 
     def trace_stats(self):
         """Work counters of the context's most recent query (rt_debug_trace_stats): dict of TRACE_STATS_KEYS."""
