@@ -108,7 +108,7 @@ def test_mesh_leaves_the_old_scene_box(scene, oracle, tmp_path):
 
 
 def tile_data_np(v4, orig):
-    """upload_tiled_scene's per-tile data (rt_api.hip tile_data_host) restated in numpy float64 for a given order."""
+    """upload_tiled_scene's per-tile data (rt_tile_sort.hip tile_data_host) restated in numpy float64 for a given order."""
     n = len(orig)
     V = v4.reshape(n, 3, 4)[:, :, :3][orig]
     out = np.zeros(((n + 63) // 64, 12), np.float32)

@@ -17,6 +17,7 @@
 // Every skip is one of those certificates ("the reference's test cannot accept"), so skipping changes no bit.
 // A plane that was not asked for (nullptr) costs a wave-uniform branch.
 // Compiled with -ffp-contract=off: see rt_math.h for the numerics contract.
+#include "rt_host.h"
 #include "rt_tiles.h"
 
 // rt_wave_common.h lets the compiler fuse the BOUNDS it defines; what follows is the reference's arithmetic again

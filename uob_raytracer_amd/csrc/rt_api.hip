@@ -13,9 +13,9 @@
 // over the direct xGMI link to that device (rt_render_device).  A gather to one root over point-to-point links
 // IS N-1 independent peer copies; they occupy no compute unit, so they run beside the next frame's persistent
 // grid.  (The one-process-per-GPU flow of bench.py gathers with RCCL through torch.distributed instead.)
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
+//
+// Here: contexts, frames, delivery across devices, scene updates, output registration and diagnostics.  The calls beside
+// the frame (ray queries, shade and radiance calls, AOV passes) are rt_calls.hip; the context itself is rt_host.h.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -23,10 +23,9 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <utility>
 #include <vector>
 
-#include "rt_device.h"
+#include "rt_host.h"
 
 namespace uobrt {
 
@@ -41,156 +40,11 @@ void set_error(const char* fmt, ...) {
   g_last_error = buf;
 }
 
-void launch_generic(const FrameParams& P, bool count, hipStream_t stream);
-bool generic_needs_records(int n);
-void launch_stage_records(const FrameParams& P, hipStream_t stream);
-void launch_trace_rays(const FrameParams& P, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
-                       float* d_out10, hipStream_t stream);
-void launch_mesh(const FrameParams& P, bool count, bool prof, hipStream_t stream, hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join);
-bool mesh_kernel_supports(const FrameParams& P);
-int mesh_tiles(int n);
-int mesh_occ_words(int grid);
-int mesh_screen_cells(int pixels);
-void launch_wave(const FrameParams& P, bool cull, bool count, hipStream_t stream);
-void launch_wave_prof(const FrameParams& P, hipStream_t stream);
-bool wave_kernel_supports(const FrameParams& P);
-int wave_blocks_per_cu(bool leave_room);
-int mesh_blocks_per_cu();
-int launch_scene_check(const float4* v, const float4* col, int n, unsigned int* out, hipStream_t stream);
-void launch_scene_refit(const float4* v, const float4* nrm, const float4* col, const int* orig, int n, float4* vm, float4* nm,
-                        float4* cm, float4* tile_box, hipStream_t stream);
-int query_stats_words();
-int aov_stats_words();
-void launch_aov(const FrameParams& P, bool tiled, const AovPlanes& A, int sample, unsigned long long* stats, int cus, hipStream_t stream);
-void launch_bin_primary(const FrameParams& P, hipStream_t stream);
-void launch_query(const FrameParams& P, bool tiled, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
-                  float* d_out10, unsigned long long* stats, int cus, hipStream_t stream);
-int shade_stats_words();
-void launch_shade(const FrameParams& P, bool tiled, const float* d_points6, const int* d_seeds, long npoints, float* d_light,
-                  int* d_cnt, unsigned long long* stats, int cus, hipStream_t stream);
-int radiance_stats_words();
-size_t radiance_record_bytes(long nray);
-void launch_radiance(const FrameParams& P, bool tiled, const float* d_rays6, const int* d_seeds, long nray, float4* d_rgba,
-                     int* d_prim, float4* d_records, unsigned long long* stats, int cus, hipStream_t stream);
-
 }  // namespace uobrt
 
 using namespace uobrt;
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return RT_E_DEVICE;                                                               \
-    }                                                                                   \
-  } while (0)
-
 constexpr int kWorldGrid = 32;       // world cells per axis of the mesh kernel's shadow-ray tile masks
-
-// Tuning knobs, read from the environment ONCE per context (rt_init); 0 / false = the built-in choice
-struct Tuning {
-  int job_tasks = 0;          // UOB_RT_JOB_TASKS: 64-ray tasks per job of the wave kernel
-  int heavy_factor4 = 8;      // UOB_RT_HEAVY_FACTOR4: a job is expensive above this / 4 times the average cost
-  bool plain_order = false;   // RT_FLAG_PLAIN_ORDER or UOB_RT_PLAIN_ORDER
-  bool full_grid = false;     // UOB_RT_FULL_GRID: a rank of a multi-GPU job fills every wave slot too
-  float l1_inflate = 3.5f;    // UOB_RT_L1_INFLATE: width of the point set level 1 bounds, in units of the task's own spread (1 .. 64)
-  bool heavy_dilate = true;   // UOB_RT_HEAVY_DILATE=0: expensive jobs are listed without their row neighbours
-  bool no_specialise = false; // UOB_RT_NO_SPECIALISE: the generic wave-kernel instantiation also where a specialised one exists
-  int grid_per_cu = 0;        // UOB_RT_GRID_PER_CU: workgroups per CU of the wave kernel's persistent grid (experiments)
-  bool phase_profile = false; // UOB_RT_PHASE_PROFILE: rt_count_executed returns s_memtime shares per phase
-  bool timeline = false;      // UOB_RT_TIMELINE: the wave kernel records when its waves start and end (rt_debug_wave_timeline)
-  int mask_debug = 0;         // UOB_RT_MASK_DEBUG: mesh kernel, switch single tile-mask stages off (fault isolation)
-  bool tile_morton = false;   // UOB_RT_TILE_ORDER=morton: the mesh kernel's tiles in plain Morton order (tiled_order)
-};
-
-struct rt_ctx {
-  rt_config cfg;
-  Tuning tune;
-  int device = 0;
-  int n = 0, n_shadow = 0;
-  int owned_rows = 0;
-  float4 *d_verts = nullptr, *d_normals = nullptr, *d_colors = nullptr;
-  uint32_t* d_argb = nullptr;      // internal framebuffer (stripe) for rt_render
-  float4* d_rgb = nullptr;         // lazily allocated float tap
-  unsigned long long* d_counters = nullptr;
-  unsigned int* d_jobctr = nullptr; // wave kernel's job queue heads
-  int cus = 256;                    // compute units of the device
-  // wave kernel: last frame's expensive jobs go first (rt_device.h FrameParams::heavy_*); two lists, used in turn
-  unsigned int *d_heavy[2] = {nullptr, nullptr}, *d_heavy_flags = nullptr;
-  int heavy_cap = 0, heavy_phase = 0;
-  size_t heavy_jobs_max = 0;       // entries of each of the two per-job flag arrays in d_heavy_flags
-  // rt_register_output: a host range the device writes frames into directly
-  char* reg_host = nullptr; char* reg_dev = nullptr; size_t reg_bytes = 0;
-  bool reg_owner = false;        // this context called hipHostRegister (a child of a multi-device context only holds its device's alias)
-  bool timeline_valid = false;   // the last frame left one (start, end, jobs) record per wave in d_timeline
-  uint64_t* d_timeline = nullptr;
-  size_t timeline_waves = 0;
-  uint32_t heavy_gen = 0;
-  float4* d_records = nullptr;     // staged records in HBM for meshes beyond one LDS stage
-  // mesh kernel (n > 64): the scene once more, reordered so that every 64-triangle tile is spatially compact (large
-  // triangles first, then Morton order of the centroids), the original index of each triangle, and the tiles' boxes
-  float4 *d_verts_m = nullptr, *d_normals_m = nullptr, *d_colors_m = nullptr, *d_tile_box = nullptr;
-  int* d_orig = nullptr;
-  DevSphere* d_spheres = nullptr;  // the sphere table in device memory (the wave-mapped kernels stage it into LDS)
-  unsigned int *d_mesh_cost = nullptr, *d_mesh_order = nullptr;   // per 16x16-pixel block: last frame's cost, this frame's order
-  bool mesh_order_valid = false;
-  // mesh kernel: per-frame candidate-tile masks (rt_kernel_mesh.hip) and the scene's bounding box for its world grid
-  unsigned long long *d_screen_masks = nullptr, *d_world_masks = nullptr;
-  unsigned int* d_world_occ = nullptr;
-  int nwords = 0, scx = 0, scy = 0;
-  float box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
-  hipStream_t stream = nullptr;
-  hipStream_t aux_stream = nullptr;             // mesh kernel: the primary-ray masks are built beside the shadow-ray masks
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
-  hipStream_t last_stream = nullptr;
-  // several devices: one child context per entry of cfg.devices (then this context owns no device memory)
-  std::vector<rt_ctx*> kids;
-  hipEvent_t ev_go = nullptr;       // parent: "the caller's stream has reached this frame"
-  hipEvent_t ev_done = nullptr;     // child: "this device's bands have been delivered"
-  bool peer_ok = true;              // child: its device can copy 2-D into the destination device directly
-  // rt_update_scene_device: the latest update, enqueued on the caller's stream; later frames (any stream) wait for it
-  hipEvent_t ev_upd = nullptr;
-  bool upd_pending = false;
-  unsigned int* d_check = nullptr;  // rt_scene_check's result block (rt_scene_update.hip)
-  // ray queries (rt_trace_rays_device, rt_ray_query.hip): they read only the scene, so frames need not wait for them; later
-  // queries (they share the counters and staging below) and scene updates do, through ev_query
-  hipEvent_t ev_query = nullptr;
-  bool query_pending = false;
-  unsigned long long* d_qstats = nullptr;   // the latest query's work counters (+ the tiled kernel's queue head)
-  int query_tiles = 0;                      // tiles of the latest query's scene (0: no tiled copy)
-  float4* d_qrecords = nullptr;             // no tiled copy, beyond one LDS stage: the queries' own records (d_records is the frames')
-  char* d_qio = nullptr;                    // rt_trace_rays: device copies of the caller's host arrays
-  size_t qio_bytes = 0;
-  // shade calls (rt_shade_points_device, rt_shade.hip): ordered like the queries — they read only the scene, frames do not wait
-  // for them; the next query, shade call and scene update do, through ev_shade (and a shade call waits for the latest query)
-  hipEvent_t ev_shade = nullptr;
-  bool shade_pending = false;
-  unsigned long long* d_sstats = nullptr;   // the latest call's work counters (+ the kernel's queue head)
-  int shade_tiles = 0;                      // tiles of the latest call's scene (0: no tiled copy)
-  char* d_sio = nullptr;                    // rt_shade_points: device copies of the caller's host arrays
-  size_t sio_bytes = 0;
-  // radiance calls (rt_radiance_rays_device, rt_radiance.hip): ordered like the shade calls, through ev_rad — they read only
-  // the scene; the next query, shade call, radiance call and scene update wait for the latest one
-  hipEvent_t ev_rad = nullptr;
-  bool rad_pending = false;
-  unsigned long long* d_rstats = nullptr;   // the latest call's work counters (+ the two kernels' queue heads)
-  char* d_rrec = nullptr;                   // the records its first stage leaves for its second (both entries)
-  size_t rrec_bytes = 0;
-  char* d_rio = nullptr;                    // rt_radiance_rays: device copies of the caller's host arrays
-  size_t rio_bytes = 0;
-  // AOV passes (rt_render_aov_device, rt_aov.hip): frame-like — they use the frames' records and screen masks, so frames,
-  // updates and later passes wait for the latest one through ev_aov; they touch none of the scheduling state above
-  hipEvent_t ev_aov = nullptr;
-  bool aov_pending = false;
-  hipStream_t aov_stream = nullptr;
-  unsigned long long* d_astats = nullptr;   // the latest pass's work counters (+ the tiled kernel's queue head)
-  int aov_tiles = 0;                        // tiles the latest pass walked (0: no tiled copy)
-  char* d_aov = nullptr;                    // rt_render_aov: device copies of the caller's host planes
-  size_t aov_bytes = 0;
-};
 
 static int validate_config(const rt_config* c) {
   if (!c) { set_error("rt_config is NULL"); return RT_E_INVALID; }
@@ -255,170 +109,10 @@ static int validate_vertices(const float* vertices4, int n) {
   return RT_OK;
 }
 
-static void vertex_box(const float* vertices4, int n, float lo[3], float hi[3]) {
-  for (int k = 0; k < 3; ++k) { lo[k] = 3.0e38f; hi[k] = -3.0e38f; }
-  for (size_t v = 0; v < (size_t)n * 3; ++v)
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = fminf(lo[k], vertices4[4 * v + k]);
-      hi[k] = fmaxf(hi[k], vertices4[4 * v + k]);
-    }
-}
-
 static int count_shadow_casters(const float* colors4, int n) {
   int cnt = 0;
   for (int i = 0; i < n; ++i) cnt += (colors4[4 * i + 3] != -1.0f);
   return cnt;
-}
-
-// Keeps the calling thread's current device unchanged across an API call (the caller may be a torch process)
-struct DeviceGuard {
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) hipSetDevice(prev); }
-};
-
-// 10 bits -> every third bit
-static uint32_t spread3(uint32_t v) {
-  v &= 1023u;
-  v = (v | (v << 16)) & 0x030000FFu;
-  v = (v | (v << 8)) & 0x0300F00Fu;
-  v = (v | (v << 4)) & 0x030C30C3u;
-  v = (v | (v << 2)) & 0x09249249u;
-  return v;
-}
-
-// The mesh kernel's copy of the scene (rt_kernel_mesh.hip): the triangle ORDER is a free choice there — shadow tests are
-// any-hit, and the closest-hit search resolves equal t by the ORIGINAL index (the reference's loop order, kernels.cl:120)
-// — so the triangles are sorted into spatially compact tiles of 64: a task's rays then meet few tiles.  Triangles whose
-// extent exceeds a quarter of the scene's (walls) come first, the rest in Morton order of their centroids.
-// Three parts, shared by rt_init and rt_update_scene(RT_UPDATE_REORDER): the order (tiled_order), the per-tile data for an
-// order (tile_data_host; rt_scene_update.hip's refit computes the same floats on the device) and the upload (upload_tiled).
-// Returns orig: orig[j] = original index of the triangle at tiled position j.
-static std::vector<int> tiled_order(const float* v4, int n, bool morton) {
-  float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-  for (size_t v = 0; v < (size_t)n * 3; ++v)
-    for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], v4[4 * v + k]); hi[k] = fmaxf(hi[k], v4[4 * v + k]); }
-  float ext = 0.0f;
-  for (int k = 0; k < 3; ++k) ext = fmaxf(ext, hi[k] - lo[k]);
-  const float inv = ext > 0.0f ? 1023.0f / ext : 0.0f;
-  std::vector<std::pair<uint32_t, int>> key((size_t)n);
-  for (int i = 0; i < n; ++i) {
-    const float* a = v4 + (size_t)12 * i;
-    float tl[3], th[3];
-    for (int k = 0; k < 3; ++k) { tl[k] = fminf(fminf(a[k], a[4 + k]), a[8 + k]); th[k] = fmaxf(fmaxf(a[k], a[4 + k]), a[8 + k]); }
-    const float te = fmaxf(fmaxf(th[0] - tl[0], th[1] - tl[1]), th[2] - tl[2]);
-    uint32_t code = 0u;
-    if (!(te > 0.25f * ext)) {
-      uint32_t q[3];
-      for (int k = 0; k < 3; ++k) {
-        const float f = (0.5f * (tl[k] + th[k]) - lo[k]) * inv;
-        q[k] = f >= 0.0f ? (f < 1023.0f ? (uint32_t)f : 1023u) : 0u;
-      }
-      code = 0x40000000u | spread3(q[0]) | (spread3(q[1]) << 1) | (spread3(q[2]) << 2);
-    }
-    key[(size_t)i] = std::make_pair(code, i);
-  }
-  std::stable_sort(key.begin(), key.end(), [](const std::pair<uint32_t, int>& x, const std::pair<uint32_t, int>& y) { return x.first < y.first; });
-  // UOB_RT_TILE_ORDER=kd (default, Tuning::tile_morton): the small triangles are not left in Morton order (runs of 64 along a space-filling curve
-  // jump between octants: a quarter of this round's test mesh's tiles had a normal-cone chord above 0.8) but split top-down at
-  // the median of the longest axis of their centroids' box, every cut on a tile boundary, until a range is one tile: compact
-  // boxes, compact normal cones.  =morton keeps round 2's order (A/B).  The order is a free choice (see above).
-  {
-    int nb = 0;
-    while (nb < n && key[(size_t)nb].first == 0u) ++nb;                  // the large triangles, in original order
-    if (!morton && n - nb > 64) {
-      std::vector<float> cen((size_t)n * 3);
-      for (int i = 0; i < n; ++i)
-        for (int k = 0; k < 3; ++k) cen[(size_t)3 * i + k] = (v4[(size_t)12 * i + k] + v4[(size_t)12 * i + 4 + k] + v4[(size_t)12 * i + 8 + k]) * (1.0f / 3.0f);
-      std::vector<int> idx((size_t)(n - nb));
-      for (int j = nb; j < n; ++j) idx[(size_t)(j - nb)] = key[(size_t)j].second;
-      // ranges [b, e) of idx; position p of idx is position nb + p of the tiled order: cuts where (nb + p) % 64 == 0
-      std::vector<std::pair<int, int>> stack;
-      stack.push_back(std::make_pair(0, n - nb));
-      while (!stack.empty()) {
-        const int b = stack.back().first, e = stack.back().second;
-        stack.pop_back();
-        if ((nb + b) / 64 == (nb + e - 1) / 64) continue;               // one tile
-        float clo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, chi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-        for (int p = b; p < e; ++p)
-          for (int k = 0; k < 3; ++k) { clo[k] = fminf(clo[k], cen[(size_t)3 * idx[(size_t)p] + k]); chi[k] = fmaxf(chi[k], cen[(size_t)3 * idx[(size_t)p] + k]); }
-        int ax = 0;
-        if (chi[1] - clo[1] > chi[ax] - clo[ax]) ax = 1;
-        if (chi[2] - clo[2] > chi[ax] - clo[ax]) ax = 2;
-        // the tile boundary nearest to the middle of the range
-        const int first_cut = ((nb + b) / 64 + 1) * 64 - nb, last_cut = ((nb + e - 1) / 64) * 64 - nb;
-        int m = ((nb + (b + e) / 2 + 32) / 64) * 64 - nb;
-        m = m < first_cut ? first_cut : (m > last_cut ? last_cut : m);
-        std::nth_element(idx.begin() + b, idx.begin() + m, idx.begin() + e,
-                         [&](int x, int y) { return cen[(size_t)3 * x + ax] < cen[(size_t)3 * y + ax] || (cen[(size_t)3 * x + ax] == cen[(size_t)3 * y + ax] && x < y); });
-        stack.push_back(std::make_pair(b, m));
-        stack.push_back(std::make_pair(m, e));
-      }
-      for (int j = nb; j < n; ++j) key[(size_t)j].second = idx[(size_t)(j - nb)];
-    }
-  }
-  std::vector<int> orig((size_t)n);
-  for (int j = 0; j < n; ++j) orig[(size_t)j] = key[(size_t)j].second;
-  return orig;
-}
-
-// The tiles' data for the order orig, 12 floats per tile (rt_device.h FrameParams::tile_box), from the ORIGINAL-order vertices
-static std::vector<float> tile_data_host(const float* v4, const int* orig, int n) {
-  const int ntiles = mesh_tiles(n);
-  std::vector<float> box((size_t)ntiles * 12);
-  for (int t = 0; t < ntiles; ++t) { for (int k = 0; k < 3; ++k) { box[(size_t)12 * t + k] = 3.0e38f; box[(size_t)12 * t + 4 + k] = -3.0e38f; } box[(size_t)12 * t + 3] = box[(size_t)12 * t + 7] = 0.0f; }
-  for (int j = 0; j < n; ++j) {
-    const int i = orig[j];
-    float* b = &box[(size_t)12 * (j / 64)];
-    for (int v = 0; v < 3; ++v)
-      for (int k = 0; k < 3; ++k) { b[k] = fminf(b[k], v4[(size_t)12 * i + 4 * v + k]); b[4 + k] = fmaxf(b[4 + k], v4[(size_t)12 * i + 4 * v + k]); }
-  }
-  // Per tile, for the bounce rays' tile pre-test (rt_kernel_mesh.hip tile_clear_for_bundle), in double from the float vertices:
-  //   lo.w  eta   = max over the tile's triangles of max(|e1|, |e2|, |e2 - e1|) / |e1 x e2|   (inverse altitudes)
-  //   hi.w  emax  = max edge length
-  //   third float4: unit axis of the triangles' normals (signs aligned) | chi = max |n_T - axis|_2 (chord of the normal cone)
-  // A tile with a degenerate triangle gets chi = 4: never certified clear, always visited.  (rt_scene_update.hip
-  // rt_scene_refit is the same arithmetic, one lane per triangle: change both together.)
-  for (int t = 0; t < ntiles; ++t) {
-    const int j0 = t * 64, j1 = (j0 + 64 < n) ? j0 + 64 : n;
-    double ax[3] = {0, 0, 0}, eta = 0.0, emax = 0.0;
-    bool degenerate = false;
-    std::vector<double> nn((size_t)(j1 - j0) * 3);
-    for (int j = j0; j < j1; ++j) {
-      const float* a = v4 + (size_t)12 * orig[j];
-      const double e1[3] = {(double)a[4] - a[0], (double)a[5] - a[1], (double)a[6] - a[2]};
-      const double e2[3] = {(double)a[8] - a[0], (double)a[9] - a[1], (double)a[10] - a[2]};
-      double cr[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-      const double l1 = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), l2 = sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
-      const double lc = sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]);
-      if (!(lc > 1e-30) || !(l1 > 0) || !(l2 > 0) || !(lc >= 1e-9 * l1 * l2)) { degenerate = true; break; }
-      const double l3 = sqrt((e2[0] - e1[0]) * (e2[0] - e1[0]) + (e2[1] - e1[1]) * (e2[1] - e1[1]) + (e2[2] - e1[2]) * (e2[2] - e1[2]));
-      const double le = fmax(fmax(l1, l2), l3);
-      eta = fmax(eta, le / lc);
-      emax = fmax(emax, le);
-      double* q = &nn[(size_t)(j - j0) * 3];
-      for (int k = 0; k < 3; ++k) q[k] = cr[k] / lc;
-      if (j > j0 && q[0] * nn[0] + q[1] * nn[1] + q[2] * nn[2] < 0) for (int k = 0; k < 3; ++k) q[k] = -q[k];   // align with the first
-      for (int k = 0; k < 3; ++k) ax[k] += q[k];
-    }
-    float* b = &box[(size_t)12 * t];
-    const double la = sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
-    double chi = 4.0;
-    if (!degenerate && la > 1e-12) {
-      for (int k = 0; k < 3; ++k) ax[k] /= la;
-      chi = 0.0;
-      for (int j = j0; j < j1; ++j) {
-        const double* q = &nn[(size_t)(j - j0) * 3];
-        const double dx = q[0] - ax[0], dy = q[1] - ax[1], dz = q[2] - ax[2];
-        chi = fmax(chi, sqrt(dx * dx + dy * dy + dz * dz));
-      }
-    } else {
-      ax[0] = 1.0; ax[1] = ax[2] = 0.0; eta = 1e30; emax = 1e30;
-    }
-    b[3] = (float)(eta * 1.0001); b[7] = (float)(emax * 1.0001);
-    b[8] = (float)ax[0]; b[9] = (float)ax[1]; b[10] = (float)ax[2]; b[11] = (float)(chi * 1.0001 + 1e-6);
-  }
-  return box;
 }
 
 // The tiled copy into the context's buffers (allocated on first use), on c->stream; blocking
@@ -666,7 +360,7 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
 
 }  // extern "C"
 
-static void fill_params(const rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal,
+void uobrt::fill_params(const rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal,
                         FrameParams* P) {
   memset(P, 0, sizeof *P);
   memcpy(P->rot, rot, 12 * sizeof(float));
@@ -688,7 +382,7 @@ static void fill_params(const rt_ctx* c, const float rot[12], const float cam[3]
     P->rzf[0] = rot[2] * P->focal0; P->rzf[1] = rot[6] * P->focal0; P->rzf[2] = rot[10] * P->focal0;
     P->hbox = g.light_spread / 2.f;
     P->light_inf = fmaxf(fmaxf(fabsf(light[0]), fabsf(light[1])), fabsf(light[2]));
-    P->band_rows_magic = g.band_rows > 1 ? (uint32_t)((0x100000000ull + (uint64_t)g.band_rows - 1) / (uint64_t)g.band_rows) : 0u;
+    P->band_rows_magic = div_magic_for(g.band_rows);
   }
   {
     const int aa = g.aa_x * g.aa_y;
@@ -733,15 +427,10 @@ static void fill_params(const rt_ctx* c, const float rot[12], const float cam[3]
     int job_pixels = 0;
     for (;;) {
       job_pixels = big_chunks ? jt / big_chunks : jt * pt;
-      if (big_chunks) {
-        P->nseg = (g.width + job_pixels - 1) / job_pixels;
-        P->njobs = P->nseg * c->owned_rows;
-        P->nseg_magic = P->nseg > 1 ? (uint32_t)((0x100000000ull + (uint64_t)P->nseg - 1) / (uint64_t)P->nseg) : 0u;
-        break;                                                   // 16-pixel jobs: within div_magic's bound for every accepted frame
-      }
       P->nseg = (g.width + job_pixels - 1) / job_pixels;
       P->njobs = P->nseg * c->owned_rows;
-      P->nseg_magic = P->nseg > 1 ? (uint32_t)((0x100000000ull + (uint64_t)P->nseg - 1) / (uint64_t)P->nseg) : 0u;
+      P->nseg_magic = div_magic_for(P->nseg);
+      if (big_chunks) break;                                     // 16-pixel jobs: within div_magic's bound for every accepted frame
       const uint64_t err = P->nseg_magic ? (uint64_t)P->nseg_magic * (uint64_t)P->nseg - 0x100000000ull : 0ull;
       if ((uint64_t)(P->njobs > 0 ? P->njobs - 1 : 0) * err < 0x100000000ull || 2 * jt * pt > 64) break;
       jt *= 2;
@@ -782,21 +471,19 @@ static void fill_params(const rt_ctx* c, const float rot[12], const float cam[3]
   }
 }
 
-// Frames and diagnostics read the scene that the context's latest rt_update_scene_device left, on whichever stream they run
-static hipError_t wait_scene(const rt_ctx* c, hipStream_t s) {
-  return c->upd_pending ? hipStreamWaitEvent(s, c->ev_upd, 0) : hipSuccess;
-}
-
-// Whatever shares the frames' per-frame buffers (records, screen masks) or rewrites the scene waits for the latest AOV pass
-static hipError_t wait_aov(const rt_ctx* c, hipStream_t s) {
-  return (c->aov_pending && s != c->aov_stream) ? hipStreamWaitEvent(s, c->ev_aov, 0) : hipSuccess;
-}
-
 // The mesh kernel works on the reordered copy of the scene (upload_tiled_scene)
-static void use_tiled_scene(const rt_ctx* c, FrameParams* P) {
+void uobrt::use_tiled_scene(const rt_ctx* c, FrameParams* P) {
   P->verts = c->d_verts_m; P->normals = c->d_normals_m; P->colors = c->d_colors_m;
   P->orig = c->d_orig; P->tile_box = c->d_tile_box;
   P->mesh_blocks = c->cus * mesh_blocks_per_cu();
+}
+
+// FrameParams of the scene only, for what looks at no view: identity view, the given light, and the tiled copy when `tiled`
+// (the readers of rt_calls.hip pass "the context keeps one"; the brute-force rt_debug_trace_rays reads the original order)
+void uobrt::scene_params(const rt_ctx* c, const float light[3], bool tiled, FrameParams* P) {
+  const float zero3[3] = {0.f, 0.f, 0.f}, ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  fill_params(c, ident, zero3, light, 1.0f, P);
+  if (tiled) use_tiled_scene(c, P);
 }
 
 // One frame of a single-device context into d_argb (packed rows, or global rows when out_global) on `stream`
@@ -877,13 +564,12 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
 // caller asks for the tiles to be sorted again (RT_UPDATE_REORDER: the rt_init path on the host).
 
 // An update enqueued on `s` first waits for everything that may still read the buffers it overwrites: the context's
-// previous frame (ev1, on whichever stream it ran), its latest ray query (ev_query) and its previous update
+// previous frame (ev1, on whichever stream it ran), the calls that still read the scene, its latest AOV pass and its
+// previous update
 static int update_begin(rt_ctx* c, hipStream_t s) {
   HIP_TRY(hipSetDevice(c->device));
   if (c->timed) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
-  if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));    // ray queries still reading the scene
-  if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));    // shade calls likewise
-  if (c->rad_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_rad, 0));        // and radiance calls
+  if (wait_scene_readers(c, s) != RT_OK) return RT_E_DEVICE;
   HIP_TRY(wait_aov(c, s));
   HIP_TRY(wait_scene(c, s));
   return RT_OK;
@@ -1038,7 +724,7 @@ int rt_update_scene_device(rt_ctx* c, const void* d_vertices4, const void* d_nor
 
 int rt_debug_tile_data(rt_ctx* c, int32_t* orig, float* tiles, int32_t cap_tiles) {
   if (!c || cap_tiles < 0 || (cap_tiles > 0 && (!orig || !tiles))) { set_error("NULL argument"); return RT_E_INVALID; }
-  if (!c->kids.empty()) c = c->kids[0];
+  c = lead_ctx(c);
   if (!c->d_tile_box) { set_error("rt_debug_tile_data: this context keeps no tiled copy of the scene"); return RT_E_UNSUPPORTED; }
   const int ntiles = mesh_tiles(c->n);
   if (cap_tiles == 0) return ntiles;
@@ -1351,7 +1037,7 @@ int rt_count_executed(rt_ctx* c, const float rot[12], const float cam[3], const 
 
 int rt_debug_wave_timeline(rt_ctx* c, uint64_t out[8]) {
   if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
-  if (!c->kids.empty()) c = c->kids[0];
+  c = lead_ctx(c);
   if (!c->tune.timeline || !c->timeline_valid) {
     set_error("rt_debug_wave_timeline: needs UOB_RT_TIMELINE=1 at rt_init and a frame rendered by the wave kernel");
     return RT_E_UNSUPPORTED;
@@ -1381,13 +1067,13 @@ int rt_debug_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float
   if (what != RT_TRACE_IN_SHADOW && what != RT_TRACE_CLOSEST_HIT) { set_error("rt_debug_trace_rays: unknown mode %d", what); return RT_E_INVALID; }
   if (what == RT_TRACE_IN_SHADOW && !radius_sq) { set_error("rt_debug_trace_rays: radius_sq missing"); return RT_E_INVALID; }
   if (what == RT_TRACE_CLOSEST_HIT && !out10) { set_error("rt_debug_trace_rays: out10 missing"); return RT_E_INVALID; }
-  if (!c->kids.empty()) c = c->kids[0];
+  c = lead_ctx(c);
   if (nray == 0) return RT_OK;
   DeviceGuard guard;
   HIP_TRY(hipSetDevice(c->device));
-  const float zero3[3] = {0.f, 0.f, 0.f}, ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  const float zero3[3] = {0.f, 0.f, 0.f};
   FrameParams P;
-  fill_params(c, ident, zero3, zero3, 1.0f, &P);
+  scene_params(c, zero3, false, &P);
   float *d_rays = nullptr, *d_r2 = nullptr, *d_out = nullptr;
   int* d_tri = nullptr;
   int rc = RT_OK;
@@ -1418,410 +1104,6 @@ int rt_debug_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float
   return rc;
 }
 
-// ---- ray queries (rt_trace_rays / rt_trace_rays_device, rt_ray_query.hip) ---------------------------------------------
-static int check_query_args(const rt_ctx* c, int32_t what, const void* rays6, const void* radius_sq, int64_t nray,
-                            const void* out_tri, const char* fn) {
-  if (!c || !rays6 || !out_tri) { set_error("%s: NULL argument", fn); return RT_E_INVALID; }
-  if (what != RT_TRACE_IN_SHADOW && what != RT_TRACE_CLOSEST_HIT) { set_error("%s: unknown mode %d", fn, what); return RT_E_INVALID; }
-  if (nray < 0 || nray > (int64_t(1) << 36)) { set_error("%s: nray = %lld outside [0, 2^36]", fn, (long long)nray); return RT_E_INVALID; }
-  if (what == RT_TRACE_IN_SHADOW && !radius_sq) { set_error("%s: radius_sq missing", fn); return RT_E_INVALID; }
-  return RT_OK;
-}
-
-// One query of a single-device context on stream s (device buffers of c->device); nray > 0, arguments checked
-static int enqueue_query(rt_ctx* c, int32_t what, const float* d_rays, const float* d_r2, long nray, int* d_tri, float* d_out10,
-                         hipStream_t s) {
-  HIP_TRY(hipSetDevice(c->device));
-  const bool tiled = c->d_verts_m != nullptr;
-  const bool records = !tiled && generic_needs_records(c->n);
-  const size_t stats_bytes = (size_t)query_stats_words() * sizeof(unsigned long long);
-  if (!c->ev_query) HIP_TRY(hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
-  if ((!c->d_qstats && hipMalloc(&c->d_qstats, stats_bytes) != hipSuccess) ||
-      (records && !c->d_qrecords && hipMalloc(&c->d_qrecords, (size_t)c->n * kRecordsPerTriangle * sizeof(float4)) != hipSuccess)) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
-  }
-  const float zero3[3] = {0.f, 0.f, 0.f}, ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  FrameParams P;
-  fill_params(c, ident, zero3, zero3, 1.0f, &P);
-  if (tiled) use_tiled_scene(c, &P);
-  P.records = records ? c->d_qrecords : nullptr;
-  HIP_TRY(wait_scene(c, s));
-  if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));
-  if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));
-  if (c->rad_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_rad, 0));
-  HIP_TRY(hipMemsetAsync(c->d_qstats, 0, stats_bytes, s));
-  if (records) launch_stage_records(P, s);
-  launch_query(P, tiled, what, d_rays, d_r2, nray, d_tri, what == RT_TRACE_CLOSEST_HIT ? d_out10 : nullptr, c->d_qstats, c->cus, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_query, s));
-  c->query_pending = true;
-  c->query_tiles = tiled ? mesh_tiles(c->n) : 0;
-  return RT_OK;
-}
-
-int rt_trace_rays_device(rt_ctx* c, int32_t what, const void* d_rays6, const void* d_radius_sq, int64_t nray, void* d_out_tri,
-                         void* d_out10, void* hip_stream) {
-  const int rc = check_query_args(c, what, d_rays6, d_radius_sq, nray, d_out_tri, "rt_trace_rays_device");
-  if (rc != RT_OK || nray == 0) return rc;
-  if (!c->kids.empty()) c = c->kids[0];
-  DeviceGuard guard;
-  return enqueue_query(c, what, (const float*)d_rays6, (const float*)d_radius_sq, (long)nray, (int*)d_out_tri, (float*)d_out10,
-                       (hipStream_t)hip_stream);
-}
-
-int rt_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float* radius_sq, int64_t nray, int32_t* out_tri, float* out10) {
-  int rc = check_query_args(c, what, rays6, radius_sq, nray, out_tri, "rt_trace_rays");
-  if (rc != RT_OK || nray == 0) return rc;
-  if (!c->kids.empty()) c = c->kids[0];
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  const bool shadow = what == RT_TRACE_IN_SHADOW, want10 = !shadow && out10;
-  const size_t n = (size_t)nray;
-  const size_t o_r2 = n * 24, o_tri = o_r2 + (shadow ? n * 4 : 0), o_out = o_tri + n * 4, bytes = o_out + (want10 ? n * 40 : 0);
-  if (bytes > c->qio_bytes) {                 // (only this blocking entry uses the buffer: nothing can still be reading it)
-    hipFree(c->d_qio);
-    c->d_qio = nullptr; c->qio_bytes = 0;
-    if (hipMalloc(&c->d_qio, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
-    c->qio_bytes = bytes;
-  }
-  char* const d = c->d_qio;
-  HIP_TRY(hipMemcpyAsync(d, rays6, n * 24, hipMemcpyHostToDevice, c->stream));
-  if (shadow) HIP_TRY(hipMemcpyAsync(d + o_r2, radius_sq, n * 4, hipMemcpyHostToDevice, c->stream));
-  rc = enqueue_query(c, what, (const float*)d, shadow ? (const float*)(d + o_r2) : nullptr, (long)nray, (int*)(d + o_tri),
-                     want10 ? (float*)(d + o_out) : nullptr, c->stream);
-  if (rc != RT_OK) { hipStreamSynchronize(c->stream); return rc; }
-  HIP_TRY(hipMemcpyAsync(out_tri, d + o_tri, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (want10) HIP_TRY(hipMemcpyAsync(out10, d + o_out, n * 40, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return RT_OK;
-}
-
-int rt_debug_trace_stats(rt_ctx* c, uint64_t out[8]) {
-  if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
-  memset(out, 0, 8 * sizeof(uint64_t));
-  if (!c->kids.empty()) c = c->kids[0];
-  if (!c->query_pending) return RT_OK;
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipEventSynchronize(c->ev_query));
-  HIP_TRY(hipMemcpy(out, c->d_qstats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  out[2] = (uint64_t)c->query_tiles;
-  return RT_OK;
-}
-
-// ---- shade calls (rt_shade_points / rt_shade_points_device, rt_shade.hip) -----------------------------------------------
-// Checked before the context is looked at, like the queries' arguments
-static int check_shade_args(const rt_ctx* c, const void* points6, int64_t npoints, const float* light, const void* out_light,
-                            const char* fn) {
-  if (!c || !points6 || !light || !out_light) { set_error("%s: NULL argument", fn); return RT_E_INVALID; }
-  if (npoints < 0 || npoints > (int64_t(1) << 31)) { set_error("%s: npoints = %lld outside [0, 2^31]", fn, (long long)npoints); return RT_E_INVALID; }
-  return RT_OK;
-}
-
-// One shade call of a single-device context on stream s (device buffers of c->device); npoints > 0, arguments checked
-static int enqueue_shade(rt_ctx* c, const float* d_points6, const int* d_seeds, long npoints, const float light[3], float* d_light,
-                         int* d_cnt, hipStream_t s) {
-  HIP_TRY(hipSetDevice(c->device));
-  const bool tiled = c->d_verts_m != nullptr;
-  const size_t stats_bytes = (size_t)shade_stats_words() * sizeof(unsigned long long);
-  if (!c->ev_shade) HIP_TRY(hipEventCreateWithFlags(&c->ev_shade, hipEventDisableTiming));
-  if (!c->d_sstats && hipMalloc(&c->d_sstats, stats_bytes) != hipSuccess) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
-  }
-  const float zero3[3] = {0.f, 0.f, 0.f}, ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  FrameParams P;
-  fill_params(c, ident, zero3, light, 1.0f, &P);
-  if (tiled) use_tiled_scene(c, &P);
-  HIP_TRY(wait_scene(c, s));
-  if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));
-  if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));
-  if (c->rad_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_rad, 0));
-  HIP_TRY(hipMemsetAsync(c->d_sstats, 0, stats_bytes, s));
-  launch_shade(P, tiled, d_points6, d_seeds, npoints, d_light, d_cnt, c->d_sstats, c->cus, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_shade, s));
-  c->shade_pending = true;
-  c->shade_tiles = tiled ? mesh_tiles(c->n) : 0;
-  return RT_OK;
-}
-
-int rt_shade_points_device(rt_ctx* c, const void* d_points6, const void* d_seeds, int64_t npoints, const float light[3],
-                           void* d_out_light, void* d_out_unshadowed, void* hip_stream) {
-  const int rc = check_shade_args(c, d_points6, npoints, light, d_out_light, "rt_shade_points_device");
-  if (rc != RT_OK || npoints == 0) return rc;
-  if (!c->kids.empty()) c = c->kids[0];
-  DeviceGuard guard;
-  return enqueue_shade(c, (const float*)d_points6, (const int*)d_seeds, (long)npoints, light, (float*)d_out_light,
-                       (int*)d_out_unshadowed, (hipStream_t)hip_stream);
-}
-
-int rt_shade_points(rt_ctx* c, const float* points6, const int32_t* seeds, int64_t npoints, const float light[3], float* out_light,
-                    int32_t* out_unshadowed) {
-  int rc = check_shade_args(c, points6, npoints, light, out_light, "rt_shade_points");
-  if (rc != RT_OK) return rc;
-  if (seeds)                                  // the domain of global_id: beyond 2^24 the reference's float products lose the id
-    for (int64_t k = 0; k < npoints; ++k)
-      if (seeds[k] < 0 || seeds[k] > (1 << 24)) {
-        set_error("rt_shade_points: seeds[%lld] = %d outside [0, 2^24]", (long long)k, seeds[k]); return RT_E_INVALID;
-      }
-  if (npoints == 0) return RT_OK;
-  if (!c->kids.empty()) c = c->kids[0];
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t n = (size_t)npoints;
-  const size_t o_seed = n * 24, o_light = o_seed + (seeds ? n * 4 : 0), o_cnt = o_light + n * 4, bytes = o_cnt + (out_unshadowed ? n * 4 : 0);
-  if (bytes > c->sio_bytes) {                 // (only this blocking entry uses the buffer: nothing can still be reading it)
-    hipFree(c->d_sio);
-    c->d_sio = nullptr; c->sio_bytes = 0;
-    if (hipMalloc(&c->d_sio, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
-    c->sio_bytes = bytes;
-  }
-  char* const d = c->d_sio;
-  HIP_TRY(hipMemcpyAsync(d, points6, n * 24, hipMemcpyHostToDevice, c->stream));
-  if (seeds) HIP_TRY(hipMemcpyAsync(d + o_seed, seeds, n * 4, hipMemcpyHostToDevice, c->stream));
-  rc = enqueue_shade(c, (const float*)d, seeds ? (const int*)(d + o_seed) : nullptr, (long)npoints, light, (float*)(d + o_light),
-                     out_unshadowed ? (int*)(d + o_cnt) : nullptr, c->stream);
-  if (rc != RT_OK) { hipStreamSynchronize(c->stream); return rc; }
-  HIP_TRY(hipMemcpyAsync(out_light, d + o_light, n * 4, hipMemcpyDeviceToHost, c->stream));
-  if (out_unshadowed) HIP_TRY(hipMemcpyAsync(out_unshadowed, d + o_cnt, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return RT_OK;
-}
-
-int rt_debug_shade_stats(rt_ctx* c, uint64_t out[8]) {
-  if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
-  memset(out, 0, 8 * sizeof(uint64_t));
-  if (!c->kids.empty()) c = c->kids[0];
-  if (!c->shade_pending) return RT_OK;
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipEventSynchronize(c->ev_shade));
-  HIP_TRY(hipMemcpy(out, c->d_sstats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  out[3] = (uint64_t)c->shade_tiles;
-  return RT_OK;
-}
-
-// ---- radiance calls (rt_radiance_rays / rt_radiance_rays_device, rt_radiance.hip) --------------------------------------
-// Checked before the context is looked at, like the shade calls' arguments
-static int check_radiance_args(const rt_ctx* c, const void* rays6, int64_t nray, const float* light, const void* out_rgba4,
-                               const char* fn) {
-  if (!c || !rays6 || !light || !out_rgba4) { set_error("%s: NULL argument", fn); return RT_E_INVALID; }
-  if (nray < 0 || nray > (int64_t(1) << 31)) { set_error("%s: nray = %lld outside [0, 2^31]", fn, (long long)nray); return RT_E_INVALID; }
-  return RT_OK;
-}
-
-// One radiance call of a single-device context on stream s (device buffers of c->device); nray > 0, arguments checked
-static int enqueue_radiance(rt_ctx* c, const float* d_rays6, const int* d_seeds, long nray, const float light[3], float* d_rgba4,
-                            int* d_prim, hipStream_t s) {
-  HIP_TRY(hipSetDevice(c->device));
-  const bool tiled = c->d_verts_m != nullptr;
-  const size_t stats_bytes = (size_t)radiance_stats_words() * sizeof(unsigned long long);
-  if (!c->ev_rad) HIP_TRY(hipEventCreateWithFlags(&c->ev_rad, hipEventDisableTiming));
-  if (!c->d_rstats && hipMalloc(&c->d_rstats, stats_bytes) != hipSuccess) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
-  }
-  const size_t rec_bytes = radiance_record_bytes(nray);
-  if (rec_bytes > c->rrec_bytes) {            // (a larger call than any before: hipFree waits for the call still using the old one)
-    hipFree(c->d_rrec);
-    c->d_rrec = nullptr; c->rrec_bytes = 0;
-    if (hipMalloc(&c->d_rrec, rec_bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
-    c->rrec_bytes = rec_bytes;
-  }
-  const float zero3[3] = {0.f, 0.f, 0.f}, ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  FrameParams P;
-  fill_params(c, ident, zero3, light, 1.0f, &P);
-  if (tiled) use_tiled_scene(c, &P);
-  HIP_TRY(wait_scene(c, s));
-  if (c->query_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_query, 0));
-  if (c->shade_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_shade, 0));
-  if (c->rad_pending) HIP_TRY(hipStreamWaitEvent(s, c->ev_rad, 0));
-  HIP_TRY(hipMemsetAsync(c->d_rstats, 0, stats_bytes, s));
-  launch_radiance(P, tiled, d_rays6, d_seeds, nray, (float4*)d_rgba4, d_prim, (float4*)c->d_rrec, c->d_rstats, c->cus, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_rad, s));
-  c->rad_pending = true;
-  return RT_OK;
-}
-
-int rt_radiance_rays_device(rt_ctx* c, const void* d_rays6, const void* d_seeds, int64_t nray, const float light[3],
-                            void* d_out_rgba4, void* d_out_prim, void* hip_stream) {
-  const int rc = check_radiance_args(c, d_rays6, nray, light, d_out_rgba4, "rt_radiance_rays_device");
-  if (rc != RT_OK) return rc;
-  if (((uintptr_t)d_out_rgba4 & 15) != 0) { set_error("rt_radiance_rays_device: d_out_rgba4 is not 16-byte aligned"); return RT_E_INVALID; }
-  if (nray == 0) return rc;
-  if (!c->kids.empty()) c = c->kids[0];
-  DeviceGuard guard;
-  return enqueue_radiance(c, (const float*)d_rays6, (const int*)d_seeds, (long)nray, light, (float*)d_out_rgba4, (int*)d_out_prim,
-                          (hipStream_t)hip_stream);
-}
-
-int rt_radiance_rays(rt_ctx* c, const float* rays6, const int32_t* seeds, int64_t nray, const float light[3], float* out_rgba4,
-                     int32_t* out_prim) {
-  int rc = check_radiance_args(c, rays6, nray, light, out_rgba4, "rt_radiance_rays");
-  if (rc != RT_OK) return rc;
-  if (seeds)                                  // the domain of global_id, as for rt_shade_points
-    for (int64_t k = 0; k < nray; ++k)
-      if (seeds[k] < 0 || seeds[k] > (1 << 24)) {
-        set_error("rt_radiance_rays: seeds[%lld] = %d outside [0, 2^24]", (long long)k, seeds[k]); return RT_E_INVALID;
-      }
-  if (nray == 0) return RT_OK;
-  if (!c->kids.empty()) c = c->kids[0];
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t n = (size_t)nray;
-  // (the colours first: the kernels store them as float4)
-  const size_t o_rays = n * 16, o_seed = o_rays + n * 24, o_prim = o_seed + (seeds ? n * 4 : 0), bytes = o_prim + (out_prim ? n * 4 : 0);
-  if (bytes > c->rio_bytes) {                 // (only this blocking entry uses the buffer: nothing can still be reading it)
-    hipFree(c->d_rio);
-    c->d_rio = nullptr; c->rio_bytes = 0;
-    if (hipMalloc(&c->d_rio, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
-    c->rio_bytes = bytes;
-  }
-  char* const d = c->d_rio;
-  HIP_TRY(hipMemcpyAsync(d + o_rays, rays6, n * 24, hipMemcpyHostToDevice, c->stream));
-  if (seeds) HIP_TRY(hipMemcpyAsync(d + o_seed, seeds, n * 4, hipMemcpyHostToDevice, c->stream));
-  rc = enqueue_radiance(c, (const float*)(d + o_rays), seeds ? (const int*)(d + o_seed) : nullptr, (long)nray, light, (float*)d,
-                        out_prim ? (int*)(d + o_prim) : nullptr, c->stream);
-  if (rc != RT_OK) { hipStreamSynchronize(c->stream); return rc; }
-  HIP_TRY(hipMemcpyAsync(out_rgba4, d, n * 16, hipMemcpyDeviceToHost, c->stream));
-  if (out_prim) HIP_TRY(hipMemcpyAsync(out_prim, d + o_prim, n * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return RT_OK;
-}
-
-int rt_debug_radiance_stats(rt_ctx* c, uint64_t out[8]) {
-  if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
-  memset(out, 0, 8 * sizeof(uint64_t));
-  if (!c->kids.empty()) c = c->kids[0];
-  if (!c->rad_pending) return RT_OK;
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipEventSynchronize(c->ev_rad));
-  HIP_TRY(hipMemcpy(out, c->d_rstats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return RT_OK;
-}
-
-// ---- AOV passes (rt_render_aov / rt_render_aov_device, rt_aov.hip) ----------------------------------------------------
-// Checked before the context is looked at, so that the struct's own errors are reported for any context
-static int check_aov_args(const rt_ctx* c, const float* rot, const float* cam, const rt_aov_buffers* b, const char* fn) {
-  if (!b) { set_error("%s: the buffers struct is NULL", fn); return RT_E_INVALID; }
-  if (!b->prim && !b->depth && !b->position4 && !b->normal4 && !b->albedo4 && !b->direction4) {
-    set_error("%s: no plane requested (every pointer of the buffers struct is NULL)", fn); return RT_E_INVALID;
-  }
-  if (!c) { set_error("%s: ctx is NULL", fn); return RT_E_INVALID; }
-  if (!rot || !cam) { set_error("%s: rot / cam is NULL", fn); return RT_E_INVALID; }
-  return RT_OK;
-}
-
-// One pass of a single-device context on stream s into device planes of c->device.  `whole`: c is devices[0] of a
-// multi-device context and renders every row of the frame, not only its own bands.
-static int enqueue_aov(rt_ctx* c, const float rot[12], const float cam[3], float focal, int32_t sample, const AovPlanes& A,
-                       bool whole, hipStream_t s) {
-  const int aa = c->cfg.aa_x * c->cfg.aa_y;
-  if (sample != RT_AOV_ALL_SAMPLES && (sample < 0 || sample >= aa)) {
-    set_error("rt_render_aov: sample = %d outside [0, %d) and not RT_AOV_ALL_SAMPLES", sample, aa); return RT_E_INVALID;
-  }
-  for (int k = 0; k < 3; ++k)
-    if (!(fabsf(cam[k]) <= kMaxCoordinate)) { set_error("camera coordinates must be finite and <= 2^16"); return RT_E_INVALID; }
-  if (!(fabsf(focal) <= 1.0e9f)) { set_error("focal length must be finite and <= 1e9"); return RT_E_INVALID; }
-  for (int k = 0; k < 12; ++k)
-    if (!(fabsf(rot[k]) <= 4.0f)) { set_error("rotation matrix entries must be finite and <= 4"); return RT_E_INVALID; }
-  const int rows = whole ? c->cfg.height : c->owned_rows;
-  if (rows == 0) return RT_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t stats_bytes = (size_t)aov_stats_words() * sizeof(unsigned long long);
-  if (!c->ev_aov) HIP_TRY(hipEventCreateWithFlags(&c->ev_aov, hipEventDisableTiming));
-  if (!c->d_astats && hipMalloc(&c->d_astats, stats_bytes) != hipSuccess) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
-  }
-  const float zero3[3] = {0.f, 0.f, 0.f};
-  FrameParams P;
-  fill_params(c, rot, cam, zero3, focal, &P);
-  if (whole) {                                 // all rows of the frame in image order
-    P.band_rows = c->cfg.height; P.band_index = 0; P.band_count = 1; P.owned_rows = rows;
-    P.band_rows_magic = P.band_rows > 1 ? (uint32_t)((0x100000000ull + (uint64_t)P.band_rows - 1) / (uint64_t)P.band_rows) : 0u;
-  }
-  const bool tiled = c->d_verts_m != nullptr;
-  const bool bins = tiled && c->d_screen_masks != nullptr && c->d_records != nullptr && !(c->tune.mask_debug & 1);
-  if (!bins) P.screen_masks = nullptr;
-  // one frame-like operation of a context at a time: the records and the screen masks are the frames'
-  if (c->timed && s != c->last_stream) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
-  HIP_TRY(wait_aov(c, s));
-  HIP_TRY(wait_scene(c, s));
-  HIP_TRY(hipMemsetAsync(c->d_astats, 0, stats_bytes, s));
-  if (tiled) {
-    use_tiled_scene(c, &P);
-    if (bins) { launch_stage_records(P, s); launch_bin_primary(P, s); }   // the masks are built from this view's records
-  } else if (generic_needs_records(c->n)) {
-    launch_stage_records(P, s);
-  }
-  launch_aov(P, tiled, A, sample, c->d_astats, c->cus, s);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_aov, s));
-  c->aov_pending = true;
-  c->aov_stream = s;
-  c->aov_tiles = tiled ? mesh_tiles(c->n) : 0;
-  return RT_OK;
-}
-
-int rt_render_aov_device(rt_ctx* c, const float rot[12], const float cam[3], float focal, int32_t sample,
-                         const rt_aov_buffers* device_out, void* hip_stream) {
-  const int rc = check_aov_args(c, rot, cam, device_out, "rt_render_aov_device");
-  if (rc != RT_OK) return rc;
-  const bool whole = !c->kids.empty();
-  if (whole) c = c->kids[0];
-  DeviceGuard guard;
-  const AovPlanes A{device_out->prim, device_out->depth, (float4*)device_out->position4, (float4*)device_out->normal4,
-                    (float4*)device_out->albedo4, (float4*)device_out->direction4};
-  return enqueue_aov(c, rot, cam, focal, sample, A, whole, (hipStream_t)hip_stream);
-}
-
-int rt_render_aov(rt_ctx* c, const float rot[12], const float cam[3], float focal, int32_t sample, const rt_aov_buffers* host_out) {
-  int rc = check_aov_args(c, rot, cam, host_out, "rt_render_aov");
-  if (rc != RT_OK) return rc;
-  const bool whole = !c->kids.empty();
-  const int rows = c->owned_rows;
-  if (whole) c = c->kids[0];
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  const int aa = c->cfg.aa_x * c->cfg.aa_y;
-  const size_t count = (size_t)rows * c->cfg.width * (sample == RT_AOV_ALL_SAMPLES ? aa : 1);
-  void* const host[6] = {host_out->prim, host_out->depth, host_out->position4, host_out->normal4, host_out->albedo4, host_out->direction4};
-  const size_t elem[6] = {4, 4, 16, 16, 16, 16};
-  size_t off[6], bytes = 0;
-  for (int k = 0; k < 6; ++k) { off[k] = bytes; if (host[k]) bytes += count * elem[k]; }
-  if (count == 0) return RT_OK;
-  if (bytes > c->aov_bytes) {                 // (only this blocking entry uses the buffer: nothing can still be reading it)
-    hipFree(c->d_aov);
-    c->d_aov = nullptr; c->aov_bytes = 0;
-    if (hipMalloc(&c->d_aov, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
-    c->aov_bytes = bytes;
-  }
-  char* const d = c->d_aov;
-  auto at = [&](int k) -> void* { return host[k] ? (void*)(d + off[k]) : nullptr; };
-  const AovPlanes A{(int*)at(0), (float*)at(1), (float4*)at(2), (float4*)at(3), (float4*)at(4), (float4*)at(5)};
-  rc = enqueue_aov(c, rot, cam, focal, sample, A, whole, c->stream);
-  if (rc != RT_OK) { hipStreamSynchronize(c->stream); return rc; }
-  for (int k = 0; k < 6; ++k)
-    if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], d + off[k], count * elem[k], hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return RT_OK;
-}
-
-int rt_debug_aov_stats(rt_ctx* c, uint64_t out[8]) {
-  if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
-  memset(out, 0, 8 * sizeof(uint64_t));
-  if (!c->kids.empty()) c = c->kids[0];
-  if (!c->aov_pending) return RT_OK;
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipEventSynchronize(c->ev_aov));
-  HIP_TRY(hipMemcpy(out, c->d_astats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  out[2] = (uint64_t)c->aov_tiles;
-  out[6] = out[7] = 0;
-  return RT_OK;
-}
-
 int rt_debug_band_copy_plan(int32_t num_devices, int32_t k, int32_t device_band_rows, int32_t width, int32_t height,
                             int32_t elem_bytes, int32_t dev_to_dev, int32_t peer_ok, int32_t same_device,
                             rt_band_copy* out, int32_t cap) {
@@ -1839,7 +1121,7 @@ int rt_debug_band_copy_plan(int32_t num_devices, int32_t k, int32_t device_band_
 
 int rt_debug_block_costs(rt_ctx* c, uint32_t* out, int32_t cap) {
   if (!c || (!out && cap > 0) || cap < 0) { set_error("NULL argument"); return RT_E_INVALID; }
-  if (!c->kids.empty()) c = c->kids[0];
+  c = lead_ctx(c);
   if (!c->d_mesh_cost || !c->mesh_order_valid) { set_error("rt_debug_block_costs: this context records no block costs"); return RT_E_UNSUPPORTED; }
   DeviceGuard guard;
   HIP_TRY(hipSetDevice(c->device));
@@ -1860,7 +1142,7 @@ int rt_debug_block_costs(rt_ctx* c, uint32_t* out, int32_t cap) {
 
 int rt_debug_world_masks(rt_ctx* c, uint64_t* out, int64_t cap, int32_t* grid, int32_t* words) {
   if (!c || (!out && cap > 0) || cap < 0 || !grid || !words) { set_error("NULL argument"); return RT_E_INVALID; }
-  if (!c->kids.empty()) c = c->kids[0];
+  c = lead_ctx(c);
   if (!c->d_world_masks || c->nwords <= 0) { set_error("rt_debug_world_masks: this context builds no tile masks"); return RT_E_UNSUPPORTED; }
   DeviceGuard guard;
   HIP_TRY(hipSetDevice(c->device));
@@ -1906,14 +1188,11 @@ void rt_destroy(rt_ctx* c) {
   if (c->ev_go) hipEventDestroy(c->ev_go);
   if (c->ev_done) hipEventDestroy(c->ev_done);
   if (c->ev_upd) hipEventDestroy(c->ev_upd);
-  if (c->ev_query) { hipEventSynchronize(c->ev_query); hipEventDestroy(c->ev_query); }
-  hipFree(c->d_qstats); hipFree(c->d_qrecords); hipFree(c->d_qio);
-  if (c->ev_shade) { hipEventSynchronize(c->ev_shade); hipEventDestroy(c->ev_shade); }
-  hipFree(c->d_sstats); hipFree(c->d_sio);
-  if (c->ev_rad) { hipEventSynchronize(c->ev_rad); hipEventDestroy(c->ev_rad); }
-  hipFree(c->d_rstats); hipFree(c->d_rrec); hipFree(c->d_rio);
-  if (c->ev_aov) { hipEventSynchronize(c->ev_aov); hipEventDestroy(c->ev_aov); }
-  hipFree(c->d_astats); hipFree(c->d_aov);
+  for (SideCall* k : {&c->query, &c->shade, &c->rad, &c->aov}) {     // no call of any family may still be running
+    if (k->ev) { hipEventSynchronize(k->ev); hipEventDestroy(k->ev); }
+    hipFree(k->d_stats); hipFree(k->io.p);
+  }
+  hipFree(c->d_qrecords); hipFree(c->rrec.p);
   hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);
   hipFree(c->d_argb); hipFree(c->d_rgb); hipFree(c->d_counters); hipFree(c->d_records); hipFree(c->d_jobctr);
   hipFree(c->d_screen_masks); hipFree(c->d_world_masks); hipFree(c->d_world_occ);

@@ -1,0 +1,351 @@
+// rt_calls.hip — the calls beside the frame, over the C ABI (include/uob_rt.h): ray queries (rt_trace_rays, rt_ray_query.hip),
+// shade calls (rt_shade_points, rt_shade.hip), radiance calls (rt_radiance_rays, rt_radiance.hip) and AOV passes
+// (rt_render_aov, rt_aov.hip).  Each family has an enqueue on the caller's stream (the *_device entry), a blocking entry for
+// host arrays that stages them through the family's device buffer, and a stats export.  What the families share is written
+// once: the steps around a call (call_prepare / reader_begin / call_end), the blocking entry (run_blocking) and the stats
+// reader (read_stats).  Which operation waits for which is DESIGN.md 4.9 (rt_host.h wait_scene_readers, wait_aov, wait_scene).
+#include <cmath>
+#include <cstring>
+
+#include "rt_host.h"
+
+using namespace uobrt;
+
+// Make sure the buffer holds `bytes`.  Regrowing frees the old buffer first: hipFree synchronises with the device, so
+// whatever still uses the old buffer has finished before it goes.
+static int ensure_bytes(DevBuffer* b, size_t bytes) {
+  if (bytes <= b->bytes) return RT_OK;
+  hipFree(b->p);
+  b->p = nullptr; b->bytes = 0;
+  if (hipMalloc(&b->p, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
+  b->bytes = bytes;
+  return RT_OK;
+}
+
+// ---- around a call -------------------------------------------------------------------------------------------------------
+// Before anything of a call is enqueued: the device, and the family's event and counters on first use
+static int call_prepare(rt_ctx* c, SideCall* k, size_t stats_bytes) {
+  HIP_TRY(hipSetDevice(c->device));
+  if (!k->ev) HIP_TRY(hipEventCreateWithFlags(&k->ev, hipEventDisableTiming));
+  if (!k->d_stats && hipMalloc(&k->d_stats, stats_bytes) != hipSuccess) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
+  }
+  return RT_OK;
+}
+
+// A reader of the scene on stream s: prepared, behind the latest update and the latest call of every reader family,
+// counters zeroed
+static int reader_begin(rt_ctx* c, SideCall* k, int stats_words, hipStream_t s) {
+  const size_t stats_bytes = (size_t)stats_words * sizeof(unsigned long long);
+  const int rc = call_prepare(c, k, stats_bytes);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(wait_scene(c, s));
+  if (wait_scene_readers(c, s) != RT_OK) return RT_E_DEVICE;
+  HIP_TRY(hipMemsetAsync(k->d_stats, 0, stats_bytes, s));
+  return RT_OK;
+}
+
+// Behind the call's kernels: launch errors, the family's event, and what its stats export reports besides the counters
+static int call_end(rt_ctx* c, SideCall* k, hipStream_t s) {
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(k->ev, s));
+  k->pending = true;
+  k->tiles = c->d_verts_m ? mesh_tiles(c->n) : 0;
+  return RT_OK;
+}
+
+// ---- blocking entries -------------------------------------------------------------------------------------------------------
+// One host array of a blocking entry: uploaded before the call (in) or downloaded after it; host == nullptr: not asked for,
+// takes no room.  run_blocking fills dev, the array's place in the family's staging buffer, in the order of the list.
+struct IoSlot {
+  void* host;
+  size_t bytes;
+  bool in;
+  char* dev;
+};
+
+// The blocking entry of a family, c a single-device context: lay the slots out, make room, upload the inputs on c->stream,
+// enqueue (the callable sees the slots' dev pointers), download the outputs, synchronise
+template <class Enqueue>
+static int run_blocking(rt_ctx* c, SideCall* k, IoSlot* slot, int nslot, Enqueue enqueue) {
+  HIP_TRY(hipSetDevice(c->device));
+  size_t bytes = 0;
+  for (int i = 0; i < nslot; ++i) if (slot[i].host) bytes += slot[i].bytes;
+  int rc = ensure_bytes(&k->io, bytes);          // (only this blocking entry uses the buffer: nothing can still be reading it)
+  if (rc != RT_OK) return rc;
+  char* d = k->io.p;
+  for (int i = 0; i < nslot; ++i) { slot[i].dev = slot[i].host ? d : nullptr; if (slot[i].host) d += slot[i].bytes; }
+  for (int i = 0; i < nslot; ++i)
+    if (slot[i].host && slot[i].in) HIP_TRY(hipMemcpyAsync(slot[i].dev, slot[i].host, slot[i].bytes, hipMemcpyHostToDevice, c->stream));
+  rc = enqueue();
+  if (rc != RT_OK) { hipStreamSynchronize(c->stream); return rc; }
+  for (int i = 0; i < nslot; ++i)
+    if (slot[i].host && !slot[i].in) HIP_TRY(hipMemcpyAsync(slot[i].host, slot[i].dev, slot[i].bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// The domain of global_id: beyond 2^24 the reference's float products lose the id
+static int check_seeds(const int32_t* seeds, int64_t n, const char* fn) {
+  if (seeds)
+    for (int64_t k = 0; k < n; ++k)
+      if (seeds[k] < 0 || seeds[k] > (1 << 24)) {
+        set_error("%s: seeds[%lld] = %d outside [0, 2^24]", fn, (long long)k, seeds[k]); return RT_E_INVALID;
+      }
+  return RT_OK;
+}
+
+// The counters of a family's latest call, once it has finished; tile_slot: where the tile count goes (-1: nowhere)
+static int read_stats(rt_ctx* c, SideCall rt_ctx::*family, int tile_slot, uint64_t out[8]) {
+  if (!c || !out) { set_error("NULL argument"); return RT_E_INVALID; }
+  memset(out, 0, 8 * sizeof(uint64_t));
+  c = lead_ctx(c);
+  const SideCall& k = c->*family;
+  if (!k.pending) return RT_OK;
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventSynchronize(k.ev));
+  HIP_TRY(hipMemcpy(out, k.d_stats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (tile_slot >= 0) out[tile_slot] = (uint64_t)k.tiles;
+  return RT_OK;
+}
+
+// ---- ray queries (rt_trace_rays / rt_trace_rays_device, rt_ray_query.hip) ---------------------------------------------
+static int check_query_args(const rt_ctx* c, int32_t what, const void* rays6, const void* radius_sq, int64_t nray,
+                            const void* out_tri, const char* fn) {
+  if (!c || !rays6 || !out_tri) { set_error("%s: NULL argument", fn); return RT_E_INVALID; }
+  if (what != RT_TRACE_IN_SHADOW && what != RT_TRACE_CLOSEST_HIT) { set_error("%s: unknown mode %d", fn, what); return RT_E_INVALID; }
+  if (nray < 0 || nray > (int64_t(1) << 36)) { set_error("%s: nray = %lld outside [0, 2^36]", fn, (long long)nray); return RT_E_INVALID; }
+  if (what == RT_TRACE_IN_SHADOW && !radius_sq) { set_error("%s: radius_sq missing", fn); return RT_E_INVALID; }
+  return RT_OK;
+}
+
+// One query of a single-device context on stream s (device buffers of c->device); nray > 0, arguments checked
+static int enqueue_query(rt_ctx* c, int32_t what, const float* d_rays, const float* d_r2, long nray, int* d_tri, float* d_out10,
+                         hipStream_t s) {
+  const bool tiled = c->d_verts_m != nullptr;
+  const bool records = !tiled && generic_needs_records(c->n);
+  const int rc = reader_begin(c, &c->query, query_stats_words(), s);
+  if (rc != RT_OK) return rc;
+  if (records && !c->d_qrecords && hipMalloc(&c->d_qrecords, (size_t)c->n * kRecordsPerTriangle * sizeof(float4)) != hipSuccess) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
+  }
+  const float zero3[3] = {0.f, 0.f, 0.f};
+  FrameParams P;
+  scene_params(c, zero3, tiled, &P);
+  P.records = records ? c->d_qrecords : nullptr;
+  if (records) launch_stage_records(P, s);
+  launch_query(P, tiled, what, d_rays, d_r2, nray, d_tri, what == RT_TRACE_CLOSEST_HIT ? d_out10 : nullptr, c->query.d_stats, c->cus, s);
+  return call_end(c, &c->query, s);
+}
+
+// ---- shade calls (rt_shade_points / rt_shade_points_device, rt_shade.hip) -----------------------------------------------
+// The arguments of a shade or radiance call (`count` names n in the message); checked before the context is looked at, like
+// the queries' arguments
+static int check_lit_args(const rt_ctx* c, const void* in6, int64_t n, const float* light, const void* out, const char* fn,
+                          const char* count) {
+  if (!c || !in6 || !light || !out) { set_error("%s: NULL argument", fn); return RT_E_INVALID; }
+  if (n < 0 || n > (int64_t(1) << 31)) { set_error("%s: %s = %lld outside [0, 2^31]", fn, count, (long long)n); return RT_E_INVALID; }
+  return RT_OK;
+}
+
+// One shade call of a single-device context on stream s (device buffers of c->device); npoints > 0, arguments checked
+static int enqueue_shade(rt_ctx* c, const float* d_points6, const int* d_seeds, long npoints, const float light[3], float* d_light,
+                         int* d_cnt, hipStream_t s) {
+  const bool tiled = c->d_verts_m != nullptr;
+  const int rc = reader_begin(c, &c->shade, shade_stats_words(), s);
+  if (rc != RT_OK) return rc;
+  FrameParams P;
+  scene_params(c, light, tiled, &P);
+  launch_shade(P, tiled, d_points6, d_seeds, npoints, d_light, d_cnt, c->shade.d_stats, c->cus, s);
+  return call_end(c, &c->shade, s);
+}
+
+// ---- radiance calls (rt_radiance_rays / rt_radiance_rays_device, rt_radiance.hip) --------------------------------------
+// One radiance call of a single-device context on stream s (device buffers of c->device); nray > 0, arguments checked
+static int enqueue_radiance(rt_ctx* c, const float* d_rays6, const int* d_seeds, long nray, const float light[3], float* d_rgba4,
+                            int* d_prim, hipStream_t s) {
+  const bool tiled = c->d_verts_m != nullptr;
+  int rc = reader_begin(c, &c->rad, radiance_stats_words(), s);
+  if (rc != RT_OK) return rc;
+  rc = ensure_bytes(&c->rrec, radiance_record_bytes(nray));   // (a larger call than any before: hipFree waits for the call still using the old one)
+  if (rc != RT_OK) return rc;
+  FrameParams P;
+  scene_params(c, light, tiled, &P);
+  launch_radiance(P, tiled, d_rays6, d_seeds, nray, (float4*)d_rgba4, d_prim, (float4*)c->rrec.p, c->rad.d_stats, c->cus, s);
+  return call_end(c, &c->rad, s);
+}
+
+// ---- AOV passes (rt_render_aov / rt_render_aov_device, rt_aov.hip) ----------------------------------------------------
+// Checked before the context is looked at, so that the struct's own errors are reported for any context
+static int check_aov_args(const rt_ctx* c, const float* rot, const float* cam, const rt_aov_buffers* b, const char* fn) {
+  if (!b) { set_error("%s: the buffers struct is NULL", fn); return RT_E_INVALID; }
+  if (!b->prim && !b->depth && !b->position4 && !b->normal4 && !b->albedo4 && !b->direction4) {
+    set_error("%s: no plane requested (every pointer of the buffers struct is NULL)", fn); return RT_E_INVALID;
+  }
+  if (!c) { set_error("%s: ctx is NULL", fn); return RT_E_INVALID; }
+  if (!rot || !cam) { set_error("%s: rot / cam is NULL", fn); return RT_E_INVALID; }
+  return RT_OK;
+}
+
+// One pass of a single-device context on stream s into device planes of c->device.  `whole`: c is devices[0] of a
+// multi-device context and renders every row of the frame, not only its own bands.
+static int enqueue_aov(rt_ctx* c, const float rot[12], const float cam[3], float focal, int32_t sample, const AovPlanes& A,
+                       bool whole, hipStream_t s) {
+  const int aa = c->cfg.aa_x * c->cfg.aa_y;
+  if (sample != RT_AOV_ALL_SAMPLES && (sample < 0 || sample >= aa)) {
+    set_error("rt_render_aov: sample = %d outside [0, %d) and not RT_AOV_ALL_SAMPLES", sample, aa); return RT_E_INVALID;
+  }
+  for (int k = 0; k < 3; ++k)
+    if (!(fabsf(cam[k]) <= kMaxCoordinate)) { set_error("camera coordinates must be finite and <= 2^16"); return RT_E_INVALID; }
+  if (!(fabsf(focal) <= 1.0e9f)) { set_error("focal length must be finite and <= 1e9"); return RT_E_INVALID; }
+  for (int k = 0; k < 12; ++k)
+    if (!(fabsf(rot[k]) <= 4.0f)) { set_error("rotation matrix entries must be finite and <= 4"); return RT_E_INVALID; }
+  const int rows = whole ? c->cfg.height : c->owned_rows;
+  if (rows == 0) return RT_OK;
+  const size_t stats_bytes = (size_t)aov_stats_words() * sizeof(unsigned long long);
+  const int rc = call_prepare(c, &c->aov, stats_bytes);
+  if (rc != RT_OK) return rc;
+  const float zero3[3] = {0.f, 0.f, 0.f};
+  FrameParams P;
+  fill_params(c, rot, cam, zero3, focal, &P);
+  if (whole) {                                 // all rows of the frame in image order
+    P.band_rows = c->cfg.height; P.band_index = 0; P.band_count = 1; P.owned_rows = rows;
+    P.band_rows_magic = div_magic_for(P.band_rows);
+  }
+  const bool tiled = c->d_verts_m != nullptr;
+  const bool bins = tiled && c->d_screen_masks != nullptr && c->d_records != nullptr && !(c->tune.mask_debug & 1);
+  if (!bins) P.screen_masks = nullptr;
+  // one frame-like operation of a context at a time: the records and the screen masks are the frames'
+  if (c->timed && s != c->last_stream) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
+  HIP_TRY(wait_aov(c, s));
+  HIP_TRY(wait_scene(c, s));
+  HIP_TRY(hipMemsetAsync(c->aov.d_stats, 0, stats_bytes, s));
+  if (tiled) {
+    use_tiled_scene(c, &P);
+    if (bins) { launch_stage_records(P, s); launch_bin_primary(P, s); }   // the masks are built from this view's records
+  } else if (generic_needs_records(c->n)) {
+    launch_stage_records(P, s);
+  }
+  launch_aov(P, tiled, A, sample, c->aov.d_stats, c->cus, s);
+  c->aov_stream = s;                           // (wait_aov: a later operation on this stream is behind the pass anyway)
+  return call_end(c, &c->aov, s);
+}
+
+extern "C" {
+
+int rt_trace_rays_device(rt_ctx* c, int32_t what, const void* d_rays6, const void* d_radius_sq, int64_t nray, void* d_out_tri,
+                         void* d_out10, void* hip_stream) {
+  const int rc = check_query_args(c, what, d_rays6, d_radius_sq, nray, d_out_tri, "rt_trace_rays_device");
+  if (rc != RT_OK || nray == 0) return rc;
+  DeviceGuard guard;
+  return enqueue_query(lead_ctx(c), what, (const float*)d_rays6, (const float*)d_radius_sq, (long)nray, (int*)d_out_tri,
+                       (float*)d_out10, (hipStream_t)hip_stream);
+}
+
+int rt_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float* radius_sq, int64_t nray, int32_t* out_tri, float* out10) {
+  const int rc = check_query_args(c, what, rays6, radius_sq, nray, out_tri, "rt_trace_rays");
+  if (rc != RT_OK || nray == 0) return rc;
+  c = lead_ctx(c);
+  DeviceGuard guard;
+  const bool shadow = what == RT_TRACE_IN_SHADOW;
+  const size_t n = (size_t)nray;
+  IoSlot io[4] = {{(void*)rays6, n * 24, true}, {shadow ? (void*)radius_sq : nullptr, n * 4, true}, {out_tri, n * 4, false},
+                  {shadow ? nullptr : out10, n * 40, false}};
+  return run_blocking(c, &c->query, io, 4, [&] {
+    return enqueue_query(c, what, (const float*)io[0].dev, (const float*)io[1].dev, (long)nray, (int*)io[2].dev, (float*)io[3].dev, c->stream);
+  });
+}
+
+int rt_debug_trace_stats(rt_ctx* c, uint64_t out[8]) { return read_stats(c, &rt_ctx::query, 2, out); }
+
+int rt_shade_points_device(rt_ctx* c, const void* d_points6, const void* d_seeds, int64_t npoints, const float light[3],
+                           void* d_out_light, void* d_out_unshadowed, void* hip_stream) {
+  const int rc = check_lit_args(c, d_points6, npoints, light, d_out_light, "rt_shade_points_device", "npoints");
+  if (rc != RT_OK || npoints == 0) return rc;
+  DeviceGuard guard;
+  return enqueue_shade(lead_ctx(c), (const float*)d_points6, (const int*)d_seeds, (long)npoints, light, (float*)d_out_light,
+                       (int*)d_out_unshadowed, (hipStream_t)hip_stream);
+}
+
+int rt_shade_points(rt_ctx* c, const float* points6, const int32_t* seeds, int64_t npoints, const float light[3], float* out_light,
+                    int32_t* out_unshadowed) {
+  int rc = check_lit_args(c, points6, npoints, light, out_light, "rt_shade_points", "npoints");
+  if (rc == RT_OK) rc = check_seeds(seeds, npoints, "rt_shade_points");
+  if (rc != RT_OK || npoints == 0) return rc;
+  c = lead_ctx(c);
+  DeviceGuard guard;
+  const size_t n = (size_t)npoints;
+  IoSlot io[4] = {{(void*)points6, n * 24, true}, {(void*)seeds, n * 4, true}, {out_light, n * 4, false}, {out_unshadowed, n * 4, false}};
+  return run_blocking(c, &c->shade, io, 4, [&] {
+    return enqueue_shade(c, (const float*)io[0].dev, (const int*)io[1].dev, (long)npoints, light, (float*)io[2].dev, (int*)io[3].dev, c->stream);
+  });
+}
+
+int rt_debug_shade_stats(rt_ctx* c, uint64_t out[8]) { return read_stats(c, &rt_ctx::shade, 3, out); }
+
+int rt_radiance_rays_device(rt_ctx* c, const void* d_rays6, const void* d_seeds, int64_t nray, const float light[3],
+                            void* d_out_rgba4, void* d_out_prim, void* hip_stream) {
+  const int rc = check_lit_args(c, d_rays6, nray, light, d_out_rgba4, "rt_radiance_rays_device", "nray");
+  if (rc != RT_OK) return rc;
+  if (((uintptr_t)d_out_rgba4 & 15) != 0) { set_error("rt_radiance_rays_device: d_out_rgba4 is not 16-byte aligned"); return RT_E_INVALID; }
+  if (nray == 0) return rc;
+  DeviceGuard guard;
+  return enqueue_radiance(lead_ctx(c), (const float*)d_rays6, (const int*)d_seeds, (long)nray, light, (float*)d_out_rgba4,
+                          (int*)d_out_prim, (hipStream_t)hip_stream);
+}
+
+int rt_radiance_rays(rt_ctx* c, const float* rays6, const int32_t* seeds, int64_t nray, const float light[3], float* out_rgba4,
+                     int32_t* out_prim) {
+  int rc = check_lit_args(c, rays6, nray, light, out_rgba4, "rt_radiance_rays", "nray");
+  if (rc == RT_OK) rc = check_seeds(seeds, nray, "rt_radiance_rays");   // the domain of global_id, as for rt_shade_points
+  if (rc != RT_OK || nray == 0) return rc;
+  c = lead_ctx(c);
+  DeviceGuard guard;
+  const size_t n = (size_t)nray;
+  // (the colours first: the kernels store them as float4, and the start of the staging buffer is aligned for that)
+  IoSlot io[4] = {{out_rgba4, n * 16, false}, {(void*)rays6, n * 24, true}, {(void*)seeds, n * 4, true}, {out_prim, n * 4, false}};
+  return run_blocking(c, &c->rad, io, 4, [&] {
+    return enqueue_radiance(c, (const float*)io[1].dev, (const int*)io[2].dev, (long)nray, light, (float*)io[0].dev, (int*)io[3].dev, c->stream);
+  });
+}
+
+int rt_debug_radiance_stats(rt_ctx* c, uint64_t out[8]) { return read_stats(c, &rt_ctx::rad, -1, out); }
+
+int rt_render_aov_device(rt_ctx* c, const float rot[12], const float cam[3], float focal, int32_t sample,
+                         const rt_aov_buffers* device_out, void* hip_stream) {
+  const int rc = check_aov_args(c, rot, cam, device_out, "rt_render_aov_device");
+  if (rc != RT_OK) return rc;
+  const bool whole = !c->kids.empty();
+  DeviceGuard guard;
+  const AovPlanes A{device_out->prim, device_out->depth, (float4*)device_out->position4, (float4*)device_out->normal4,
+                    (float4*)device_out->albedo4, (float4*)device_out->direction4};
+  return enqueue_aov(lead_ctx(c), rot, cam, focal, sample, A, whole, (hipStream_t)hip_stream);
+}
+
+int rt_render_aov(rt_ctx* c, const float rot[12], const float cam[3], float focal, int32_t sample, const rt_aov_buffers* host_out) {
+  const int rc = check_aov_args(c, rot, cam, host_out, "rt_render_aov");
+  if (rc != RT_OK) return rc;
+  const bool whole = !c->kids.empty();
+  const int rows = c->owned_rows;
+  c = lead_ctx(c);
+  DeviceGuard guard;
+  const int aa = c->cfg.aa_x * c->cfg.aa_y;
+  const size_t count = (size_t)rows * c->cfg.width * (sample == RT_AOV_ALL_SAMPLES ? aa : 1);
+  if (count == 0) return RT_OK;
+  IoSlot io[6] = {{host_out->prim, count * 4, false},       {host_out->depth, count * 4, false},
+                  {host_out->position4, count * 16, false}, {host_out->normal4, count * 16, false},
+                  {host_out->albedo4, count * 16, false},   {host_out->direction4, count * 16, false}};
+  return run_blocking(c, &c->aov, io, 6, [&] {
+    const AovPlanes A{(int*)io[0].dev, (float*)io[1].dev, (float4*)io[2].dev, (float4*)io[3].dev, (float4*)io[4].dev, (float4*)io[5].dev};
+    return enqueue_aov(c, rot, cam, focal, sample, A, whole, c->stream);
+  });
+}
+
+int rt_debug_aov_stats(rt_ctx* c, uint64_t out[8]) {
+  const int rc = read_stats(c, &rt_ctx::aov, 2, out);
+  if (rc == RT_OK) out[6] = out[7] = 0;       // (the kernel's queue head lives behind the counters)
+  return rc;
+}
+
+}  // extern "C"

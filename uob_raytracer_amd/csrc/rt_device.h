@@ -1,4 +1,4 @@
-// rt_device.h — structures shared by the host API (rt_api.hip) and the gfx950 kernels.
+// rt_device.h — structures shared by the host API (rt_api.hip, rt_calls.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -98,7 +98,7 @@ struct FrameParams {
   unsigned int* mesh_queue_len;     // its length (a very expensive block is entered as four cooperative sub-block jobs)
   int32_t mesh_blocks;              // workgroups the device holds at once
   const int* orig;        // mesh kernel: original index of every (reordered) triangle; nullptr = the order is the original
-  const float4* tile_box; // mesh kernel: per 64-triangle tile, 3 float4: box lo.xyz | eta, box hi.xyz | sigma, normal-cone axis | chi (rt_api.hip)
+  const float4* tile_box; // mesh kernel: per 64-triangle tile, 3 float4: box lo.xyz | eta, box hi.xyz | sigma, normal-cone axis | chi (rt_tile_sort.hip)
   // mesh kernel: per-frame candidate-tile masks (rt_kernel_mesh.hip), nullptr = visit every tile
   unsigned long long* screen_masks;   // [scy][scx][nwords]: tiles a primary ray through that 64x64-pixel cell may hit
   unsigned long long* world_masks;    // [G][G][G][nwords]: tiles that may shadow a surface point inside that world cell

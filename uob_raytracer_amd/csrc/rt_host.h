@@ -1,0 +1,203 @@
+// rt_host.h — what the host side of the library shares: the context, the error text, and the prototypes of the host
+// functions that the kernel files define.  Included by the API files (rt_api.hip, rt_calls.hip, rt_tile_sort.hip) AND by
+// the kernel files that define launch_* and friends, so the compiler checks every prototype against its definition.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "rt_device.h"
+
+#define HIP_TRY(expr)                                                                   \
+  do {                                                                                  \
+    hipError_t e_ = (expr);                                                             \
+    if (e_ != hipSuccess) {                                                             \
+      uobrt::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+      return RT_E_DEVICE;                                                               \
+    }                                                                                   \
+  } while (0)
+
+namespace uobrt {
+
+void set_error(const char* fmt, ...);      // the text behind rt_last_error (rt_api.hip)
+
+// rt_kernel_generic.hip
+void launch_generic(const FrameParams& P, bool count, hipStream_t stream);
+bool generic_needs_records(int n);
+void launch_stage_records(const FrameParams& P, hipStream_t stream);
+void launch_trace_rays(const FrameParams& P, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
+                       float* d_out10, hipStream_t stream);
+// rt_kernel_wave.hip
+void launch_wave(const FrameParams& P, bool cull, bool count, hipStream_t stream);
+void launch_wave_prof(const FrameParams& P, hipStream_t stream);
+bool wave_kernel_supports(const FrameParams& P);
+int wave_blocks_per_cu(bool leave_room);
+// rt_kernel_mesh.hip
+void launch_mesh(const FrameParams& P, bool count, bool prof, hipStream_t stream, hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join);
+void launch_bin_primary(const FrameParams& P, hipStream_t stream);
+bool mesh_kernel_supports(const FrameParams& P);
+int mesh_tiles(int n);
+int mesh_occ_words(int grid);
+int mesh_screen_cells(int pixels);
+int mesh_blocks_per_cu();
+// rt_scene_update.hip
+int launch_scene_check(const float4* v, const float4* col, int n, unsigned int* out, hipStream_t stream);
+void launch_scene_refit(const float4* v, const float4* nrm, const float4* col, const int* orig, int n, float4* vm, float4* nm,
+                        float4* cm, float4* tile_box, hipStream_t stream);
+// rt_ray_query.hip
+int query_stats_words();
+void launch_query(const FrameParams& P, bool tiled, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
+                  float* d_out10, unsigned long long* stats, int cus, hipStream_t stream);
+// rt_shade.hip
+int shade_stats_words();
+void launch_shade(const FrameParams& P, bool tiled, const float* d_points6, const int* d_seeds, long npoints, float* d_light,
+                  int* d_cnt, unsigned long long* stats, int cus, hipStream_t stream);
+// rt_radiance.hip
+int radiance_stats_words();
+size_t radiance_record_bytes(long nray);
+void launch_radiance(const FrameParams& P, bool tiled, const float* d_rays6, const int* d_seeds, long nray, float4* d_rgba,
+                     int* d_prim, float4* d_records, unsigned long long* stats, int cus, hipStream_t stream);
+// rt_aov.hip
+int aov_stats_words();
+void launch_aov(const FrameParams& P, bool tiled, const AovPlanes& A, int sample, unsigned long long* stats, int cus, hipStream_t stream);
+// rt_tile_sort.hip: the vertices' box, and the mesh kernel's tiled order and per-tile data (host arithmetic)
+void vertex_box(const float* vertices4, int n, float lo[3], float hi[3]);
+std::vector<int> tiled_order(const float* v4, int n, bool morton);
+std::vector<float> tile_data_host(const float* v4, const int* orig, int n);
+
+// ceil(2^32 / d): the magic number of rt_device.h div_magic (0 stands for d == 1)
+inline uint32_t div_magic_for(int d) { return d > 1 ? (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d) : 0u; }
+
+// Tuning knobs, read from the environment ONCE per context (rt_init); 0 / false = the built-in choice
+struct Tuning {
+  int job_tasks = 0;          // UOB_RT_JOB_TASKS: 64-ray tasks per job of the wave kernel
+  int heavy_factor4 = 8;      // UOB_RT_HEAVY_FACTOR4: a job is expensive above this / 4 times the average cost
+  bool plain_order = false;   // RT_FLAG_PLAIN_ORDER or UOB_RT_PLAIN_ORDER
+  bool full_grid = false;     // UOB_RT_FULL_GRID: a rank of a multi-GPU job fills every wave slot too
+  float l1_inflate = 3.5f;    // UOB_RT_L1_INFLATE: width of the point set level 1 bounds, in units of the task's own spread (1 .. 64)
+  bool heavy_dilate = true;   // UOB_RT_HEAVY_DILATE=0: expensive jobs are listed without their row neighbours
+  bool no_specialise = false; // UOB_RT_NO_SPECIALISE: the generic wave-kernel instantiation also where a specialised one exists
+  int grid_per_cu = 0;        // UOB_RT_GRID_PER_CU: workgroups per CU of the wave kernel's persistent grid (experiments)
+  bool phase_profile = false; // UOB_RT_PHASE_PROFILE: rt_count_executed returns s_memtime shares per phase
+  bool timeline = false;      // UOB_RT_TIMELINE: the wave kernel records when its waves start and end (rt_debug_wave_timeline)
+  int mask_debug = 0;         // UOB_RT_MASK_DEBUG: mesh kernel, switch single tile-mask stages off (fault isolation)
+  bool tile_morton = false;   // UOB_RT_TILE_ORDER=morton: the mesh kernel's tiles in plain Morton order (tiled_order)
+};
+
+// A device buffer that only ever grows (ensure_bytes, rt_calls.hip)
+struct DevBuffer {
+  char* p = nullptr;
+  size_t bytes = 0;
+};
+
+// One family of calls beside the frame (rt_calls.hip): ray queries, shade calls, radiance calls, AOV passes.
+// Who waits for whose event is DESIGN.md 4.9; wait_scene_readers and wait_aov below are the only places that say it.
+struct SideCall {
+  hipEvent_t ev = nullptr;                 // recorded behind the latest call, created on first use
+  bool pending = false;                    // a call has been enqueued: ev is worth waiting for
+  unsigned long long* d_stats = nullptr;   // the latest call's work counters (+ its kernels' queue heads)
+  int tiles = 0;                           // tiles of the latest call's scene (0: no tiled copy)
+  DevBuffer io;                            // the blocking host entry: device copies of the caller's host arrays
+};
+
+}  // namespace uobrt
+
+struct rt_ctx {
+  rt_config cfg;
+  uobrt::Tuning tune;
+  int device = 0;
+  int n = 0, n_shadow = 0;
+  int owned_rows = 0;
+  float4 *d_verts = nullptr, *d_normals = nullptr, *d_colors = nullptr;
+  uint32_t* d_argb = nullptr;      // internal framebuffer (stripe) for rt_render
+  float4* d_rgb = nullptr;         // lazily allocated float tap
+  unsigned long long* d_counters = nullptr;
+  unsigned int* d_jobctr = nullptr; // wave kernel's job queue heads
+  int cus = 256;                    // compute units of the device
+  // wave kernel: last frame's expensive jobs go first (rt_device.h FrameParams::heavy_*); two lists, used in turn
+  unsigned int *d_heavy[2] = {nullptr, nullptr}, *d_heavy_flags = nullptr;
+  int heavy_cap = 0, heavy_phase = 0;
+  size_t heavy_jobs_max = 0;       // entries of each of the two per-job flag arrays in d_heavy_flags
+  // rt_register_output: a host range the device writes frames into directly
+  char* reg_host = nullptr; char* reg_dev = nullptr; size_t reg_bytes = 0;
+  bool reg_owner = false;        // this context called hipHostRegister (a child of a multi-device context only holds its device's alias)
+  bool timeline_valid = false;   // the last frame left one (start, end, jobs) record per wave in d_timeline
+  uint64_t* d_timeline = nullptr;
+  size_t timeline_waves = 0;
+  uint32_t heavy_gen = 0;
+  float4* d_records = nullptr;     // staged records in HBM for meshes beyond one LDS stage
+  // mesh kernel (n > 64): the scene once more, reordered so that every 64-triangle tile is spatially compact (large
+  // triangles first, then Morton order of the centroids), the original index of each triangle, and the tiles' boxes
+  float4 *d_verts_m = nullptr, *d_normals_m = nullptr, *d_colors_m = nullptr, *d_tile_box = nullptr;
+  int* d_orig = nullptr;
+  uobrt::DevSphere* d_spheres = nullptr;  // the sphere table in device memory (the wave-mapped kernels stage it into LDS)
+  unsigned int *d_mesh_cost = nullptr, *d_mesh_order = nullptr;   // per 16x16-pixel block: last frame's cost, this frame's order
+  bool mesh_order_valid = false;
+  // mesh kernel: per-frame candidate-tile masks (rt_kernel_mesh.hip) and the scene's bounding box for its world grid
+  unsigned long long *d_screen_masks = nullptr, *d_world_masks = nullptr;
+  unsigned int* d_world_occ = nullptr;
+  int nwords = 0, scx = 0, scy = 0;
+  float box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+  hipStream_t stream = nullptr;
+  hipStream_t aux_stream = nullptr;             // mesh kernel: the primary-ray masks are built beside the shadow-ray masks
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool timed = false;
+  hipStream_t last_stream = nullptr;
+  // several devices: one child context per entry of cfg.devices (then this context owns no device memory)
+  std::vector<rt_ctx*> kids;
+  hipEvent_t ev_go = nullptr;       // parent: "the caller's stream has reached this frame"
+  hipEvent_t ev_done = nullptr;     // child: "this device's bands have been delivered"
+  bool peer_ok = true;              // child: its device can copy 2-D into the destination device directly
+  // rt_update_scene_device: the latest update, enqueued on the caller's stream; later frames (any stream) wait for it
+  hipEvent_t ev_upd = nullptr;
+  bool upd_pending = false;
+  unsigned int* d_check = nullptr;  // rt_scene_check's result block (rt_scene_update.hip)
+  // The scene's readers — ray queries (rt_ray_query.hip), shade calls (rt_shade.hip), radiance calls (rt_radiance.hip): they
+  // read only the scene, so frames need not wait for them; later readers (they share the counters and staging of their
+  // family) and scene updates do
+  uobrt::SideCall query, shade, rad;
+  float4* d_qrecords = nullptr;     // queries, no tiled copy, beyond one LDS stage: their own records (d_records is the frames')
+  uobrt::DevBuffer rrec;                  // radiance calls: the records their first stage leaves for their second (both entries)
+  // AOV passes (rt_aov.hip): frame-like — they use the frames' records and screen masks, so frames, updates and later
+  // passes wait for the latest one; they touch none of the scheduling state above
+  uobrt::SideCall aov;
+  hipStream_t aov_stream = nullptr;
+};
+
+namespace uobrt {
+
+// Keeps the calling thread's current device unchanged across an API call (the caller may be a torch process)
+struct DeviceGuard {
+  int prev = -1;
+  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+  ~DeviceGuard() { if (prev >= 0) hipSetDevice(prev); }
+};
+
+// The single-device context that answers for a handle: devices[0] of a multi-device context, else the context itself
+inline rt_ctx* lead_ctx(rt_ctx* c) { return c->kids.empty() ? c : c->kids[0]; }
+
+// Frames and diagnostics read the scene that the context's latest rt_update_scene_device left, on whichever stream they run
+inline hipError_t wait_scene(const rt_ctx* c, hipStream_t s) {
+  return c->upd_pending ? hipStreamWaitEvent(s, c->ev_upd, 0) : hipSuccess;
+}
+
+// Whatever shares the frames' per-frame buffers (records, screen masks) or rewrites the scene waits for the latest AOV pass
+inline hipError_t wait_aov(const rt_ctx* c, hipStream_t s) {
+  return (c->aov.pending && s != c->aov_stream) ? hipStreamWaitEvent(s, c->aov.ev, 0) : hipSuccess;
+}
+
+// Whatever rewrites the scene, or shares a reader family's counters and staging, waits for the latest call of every
+// reader family.  The ONE place that lists them: a new family of readers is added here and nowhere else.
+inline int wait_scene_readers(const rt_ctx* c, hipStream_t s) {
+  for (const SideCall* k : {&c->query, &c->shade, &c->rad})
+    if (k->pending) HIP_TRY(hipStreamWaitEvent(s, k->ev, 0));
+  return RT_OK;
+}
+
+// rt_api.hip
+void fill_params(const rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal, FrameParams* P);
+void use_tiled_scene(const rt_ctx* c, FrameParams* P);
+void scene_params(const rt_ctx* c, const float light[3], bool tiled, FrameParams* P);
+
+}  // namespace uobrt

@@ -11,6 +11,7 @@
 // per workgroup into LDS as float4 SoA records (rt_trace.h): all lanes of a wave read the same record in
 // the intersection loops, which LDS serves as a broadcast.
 // Compiled with -ffp-contract=off: see rt_math.h for the numerics contract.
+#include "rt_host.h"
 #include "rt_trace.h"
 
 namespace uobrt {

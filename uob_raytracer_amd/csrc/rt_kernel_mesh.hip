@@ -21,6 +21,7 @@
 // tasks together, every round streaming all tiles through LDS with the same lane = triangle bound in front.
 #define RT_SPHERES_IN_LDS
 #define RT_RNG_JUMP_IN_LDS
+#include "rt_host.h"
 #include "rt_tiles.h"
 
 namespace uobrt {

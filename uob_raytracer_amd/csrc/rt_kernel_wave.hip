@@ -35,6 +35,7 @@
 // generic kernel and to the CPU oracle.
 #define RT_SPHERES_IN_LDS
 #define RT_RNG_JUMP_IN_LDS
+#include "rt_host.h"
 #include "rt_wave_common.h"
 
 #include <type_traits>

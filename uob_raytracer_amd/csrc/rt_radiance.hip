@@ -19,6 +19,7 @@
 // Every skip of the walks is a certificate that the reference's test cannot accept; rays outside the certificates' domain
 // (in_query_domain) — caller rays, bounce rays and sample rays alike — take every triangle.
 // Compiled with -ffp-contract=off: see rt_math.h for the numerics contract.
+#include "rt_host.h"
 #include "rt_shade_body.h"
 
 namespace uobrt {

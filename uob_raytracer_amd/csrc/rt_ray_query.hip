@@ -15,6 +15,7 @@
 // verified for |start| <= 2^16 and 2^-20 <= max |direction component| <= 2^16 (finite); a ray outside that domain
 // needs every tile and every triangle, i.e. it gets the brute-force answer by construction.
 // Compiled with -ffp-contract=off: see rt_math.h for the numerics contract.
+#include "rt_host.h"
 #include "rt_tiles.h"
 
 // rt_wave_common.h lets the compiler fuse the BOUNDS it defines; what follows is the reference's arithmetic again

@@ -7,10 +7,10 @@
 //   rt_scene_refit  keeps the tiling of rt_init (d_orig) and rebuilds the mesh kernel's copy of the scene for new vertices:
 //                   one wave per 64-triangle tile gathers its triangles into the tiled arrays and computes the tile's 12
 //                   floats with the same double operations, in the same order where order matters, as the host does
-//                   for rt_init (rt_api.hip tile_data_host) — so a refit context renders what a new context renders.
+//                   for rt_init (rt_tile_sort.hip tile_data_host) — so a refit context renders what a new context renders.
 #include <hip/hip_runtime.h>
 
-#include "rt_device.h"
+#include "rt_host.h"
 
 namespace uobrt {
 

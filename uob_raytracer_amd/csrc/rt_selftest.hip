@@ -1,11 +1,10 @@
 // rt_selftest.hip — on-device self tests of the numerics building blocks (C ABI: rt_selftest_rcp).
 #include <hip/hip_runtime.h>
 
-#include "rt_device.h"
+#include "rt_host.h"
 #include "rt_math.h"
 
 namespace uobrt {
-void set_error(const char* fmt, ...);
 
 // For every FP32 bit pattern x: compare the Newton-refined v_rcp_f32 (1 and 2 steps) with the correctly
 // rounded 1.0f/x.  out[0]/out[1]: mismatches of the 1-/2-step form over the "safe" magnitudes

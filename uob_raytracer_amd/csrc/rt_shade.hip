@@ -21,6 +21,7 @@
 //      then term once per unblocked sample, then / S.
 // Every skip of the walk is a certificate that the reference's test cannot accept; rays outside the certificates' domain
 // (in_query_domain) take every triangle.  Compiled with -ffp-contract=off: see rt_math.h for the numerics contract.
+#include "rt_host.h"
 #include "rt_shade_body.h"
 
 namespace uobrt {

@@ -123,6 +123,25 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _need(name, t, dtype, shape, dev):
+    """A tensor argument of a *_device method: a contiguous torch tensor of that dtype and shape on the context's device."""
+    if not isinstance(t, _torch.Tensor):
+        raise TypeError("%s must be a torch tensor" % name)
+    if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
+                         % (name, dtype, shape, dev, t.dtype, tuple(t.shape), t.device))
+
+
+def _seeds_ptr(seeds, k, what):
+    """The optional seeds of a blocking shade / radiance call as the int32 pointer the C ABI takes (None: no seeds)."""
+    if seeds is None:
+        return None
+    seeds = np.ascontiguousarray(seeds, np.int32).reshape(-1)
+    if seeds.shape[0] != k:
+        raise ValueError("seeds must have one entry per %s" % what)
+    return seeds.ctypes.data_as(C.POINTER(C.c_int32))     # (the pointer object keeps the array alive)
+
+
 def band_copy_plan(num_devices, k, device_band_rows, width, height, elem_bytes, dev_to_dev, peer_ok, same_device):
     """The copies that deliver device k's bands of a multi-device context (rt_debug_band_copy_plan): list of dicts."""
     n = _check(lib().rt_debug_band_copy_plan(num_devices, k, device_band_rows, width, height, elem_bytes, int(dev_to_dev),
@@ -274,6 +293,23 @@ class RayTracer:
         except Exception:
             pass
 
+    def _torch_device(self):
+        """The torch device the context's device entries run on (devices[0]; without one, torch's current device)."""
+        return _torch.device("cuda", self.device if self.device is not None else _torch.cuda.current_device())
+
+    @staticmethod
+    def _raw_stream(stream, dev):
+        """A torch stream or a raw hipStream_t (None: torch's current stream on dev) as the integer the C ABI takes."""
+        if stream is None:
+            stream = _torch.cuda.current_stream(dev)
+        return getattr(stream, "cuda_stream", stream) or 0
+
+    def _stats(self, export, keys):
+        """The eight counters a rt_debug_*_stats export reports for the context's most recent call of its family."""
+        out = (C.c_uint64 * 8)()
+        _check(getattr(lib(), export)(self._h, out))
+        return {key: int(out[i]) for i, key in enumerate(keys)}
+
     @staticmethod
     def _args(rot, cam, light):
         return (np.ascontiguousarray(rot, np.float32), np.ascontiguousarray(cam, np.float32)[:3].copy(),
@@ -374,34 +410,25 @@ class RayTracer:
         import torch
         if what not in (abi.RT_TRACE_IN_SHADOW, abi.RT_TRACE_CLOSEST_HIT):
             raise ValueError("unknown query mode %r" % (what,))
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-
-        def _need(name, t, dtype, shape):
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("%s must be a torch tensor" % name)
-            if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
-                                 % (name, dtype, shape, dev, t.dtype, tuple(t.shape), t.device))
+        dev = self._torch_device()
 
         if not isinstance(rays, torch.Tensor) or rays.dim() != 2:
             raise ValueError("rays must be a torch tensor of shape [k, 6]")
         k = rays.shape[0]
-        _need("rays", rays, torch.float32, (k, 6))
+        _need("rays", rays, torch.float32, (k, 6), dev)
         shadow = what == abi.RT_TRACE_IN_SHADOW
         if shadow:
             if radius_sq is None:
                 raise ValueError("in_shadow queries need radius_sq")
-            _need("radius_sq", radius_sq, torch.float32, (k,))
+            _need("radius_sq", radius_sq, torch.float32, (k,), dev)
         if out_tri is None:
             out_tri = torch.empty(k, dtype=torch.int32, device=dev)
-        _need("out_tri", out_tri, torch.int32, (k,))
+        _need("out_tri", out_tri, torch.int32, (k,), dev)
         if not shadow:
             if out10 is None:
                 out10 = torch.empty((k, 10), dtype=torch.float32, device=dev)
-            _need("out10", out10, torch.float32, (k, 10))
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        raw = getattr(stream, "cuda_stream", stream) or 0
+            _need("out10", out10, torch.float32, (k, 10), dev)
+        raw = self._raw_stream(stream, dev)
         if k:
             _check(lib().rt_trace_rays_device(self._h, what, C.c_void_p(rays.data_ptr()),
                                               C.c_void_p(radius_sq.data_ptr() if shadow else 0), k,
@@ -438,7 +465,7 @@ class RayTracer:
         import torch
         if not out:
             raise ValueError("out must name at least one plane")
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        dev = self._torch_device()
         rot, cam, _ = self._args(rot, cam, cam)
         bufs = abi.RtAovBuffers()
         for name, t in out.items():
@@ -447,9 +474,7 @@ class RayTracer:
             if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
                 raise ValueError("plane %r must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
             setattr(bufs, abi.AOV_PLANES[name][0], t.data_ptr())
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        raw = getattr(stream, "cuda_stream", stream) or 0
+        raw = self._raw_stream(stream, dev)
         _check(lib().rt_render_aov_device(self._h, _fp(rot), _fp(cam), C.c_float(focal),
                                           abi.RT_AOV_ALL_SAMPLES if sample is None else int(sample), C.byref(bufs),
                                           C.c_void_p(raw)))
@@ -457,9 +482,7 @@ class RayTracer:
 
     def aov_stats(self):
         """Work counters of the context's most recent AOV pass (rt_debug_aov_stats): dict of AOV_STATS_KEYS."""
-        out = (C.c_uint64 * 8)()
-        _check(lib().rt_debug_aov_stats(self._h, out))
-        return {key: int(out[i]) for i, key in enumerate(AOV_STATS_KEYS)}
+        return self._stats("rt_debug_aov_stats", AOV_STATS_KEYS)
 
     def shade_points(self, points, normals, light, seeds=None, want_counts=False):
         """Soft-shadowed direct light at caller points (rt_shade_points), blocking: points, normals [k,3] (intersect and
@@ -473,12 +496,7 @@ class RayTracer:
         k = p.shape[0]
         p6 = np.ascontiguousarray(np.concatenate([p, nr], 1), np.float32)
         li = np.ascontiguousarray(light, np.float32)[:3].copy()
-        sp = None
-        if seeds is not None:
-            seeds = np.ascontiguousarray(seeds, np.int32).reshape(-1)
-            if seeds.shape[0] != k:
-                raise ValueError("seeds must have one entry per point")
-            sp = seeds.ctypes.data_as(C.POINTER(C.c_int32))
+        sp = _seeds_ptr(seeds, k, "point")
         out = np.zeros(k, np.float32)
         cnt = np.zeros(k, np.int32) if want_counts else None
         _check(lib().rt_shade_points(self._h, _fp(p6), sp, k, _fp(li), _fp(out),
@@ -491,32 +509,23 @@ class RayTracer:
         want_counts).  stream: a torch stream or a raw hipStream_t (default: torch's current stream).  Returns out_light, or
         (out_light, out_counts) when counts are asked for."""
         import torch
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-
-        def _need(name, t, dtype, shape):
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("%s must be a torch tensor" % name)
-            if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
-                                 % (name, dtype, shape, dev, t.dtype, tuple(t.shape), t.device))
+        dev = self._torch_device()
 
         if not isinstance(points6, torch.Tensor) or points6.dim() != 2:
             raise ValueError("points6 must be a torch tensor of shape [k, 6]")
         k = points6.shape[0]
-        _need("points6", points6, torch.float32, (k, 6))
+        _need("points6", points6, torch.float32, (k, 6), dev)
         if seeds is not None:
-            _need("seeds", seeds, torch.int32, (k,))
+            _need("seeds", seeds, torch.int32, (k,), dev)
         if out_light is None:
             out_light = torch.empty(k, dtype=torch.float32, device=dev)
-        _need("out_light", out_light, torch.float32, (k,))
+        _need("out_light", out_light, torch.float32, (k,), dev)
         if out_counts is None and want_counts:
             out_counts = torch.empty(k, dtype=torch.int32, device=dev)
         if out_counts is not None:
-            _need("out_counts", out_counts, torch.int32, (k,))
+            _need("out_counts", out_counts, torch.int32, (k,), dev)
         li = np.ascontiguousarray(light, np.float32)[:3].copy()
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        raw = getattr(stream, "cuda_stream", stream) or 0
+        raw = self._raw_stream(stream, dev)
         if k:
             _check(lib().rt_shade_points_device(self._h, C.c_void_p(points6.data_ptr()),
                                                 C.c_void_p(seeds.data_ptr() if seeds is not None else 0), k, _fp(li),
@@ -538,7 +547,7 @@ class RayTracer:
             raise ValueError("sample must be one AA sample index in [0, %d)" % aa)
         if self.cfg.width * self.cfg.height > abi.RT_SHADE_SEED_MAX:
             raise ValueError("render_direct_light: %d x %d pixels exceed the seed domain of 2^24 ids" % (self.cfg.width, self.cfg.height))
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        dev = self._torch_device()
         shape = (self.rows, self.width)
         planes = {"prim": torch.empty(shape, dtype=torch.int32, device=dev),
                   "position": torch.empty(shape + (4,), dtype=torch.float32, device=dev),
@@ -554,9 +563,7 @@ class RayTracer:
 
     def shade_stats(self):
         """Work counters of the context's most recent shade call (rt_debug_shade_stats): dict of SHADE_STATS_KEYS."""
-        out = (C.c_uint64 * 8)()
-        _check(lib().rt_debug_shade_stats(self._h, out))
-        return {key: int(out[i]) for i, key in enumerate(SHADE_STATS_KEYS)}
+        return self._stats("rt_debug_shade_stats", SHADE_STATS_KEYS)
 
     def radiance_rays(self, rays, light, seeds=None, want_prim=False):
         """The frame's full colour along caller rays (rt_radiance_rays), blocking: rays [k,6] = start, direction (used as
@@ -566,12 +573,7 @@ class RayTracer:
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
         k = rays.shape[0]
         li = np.ascontiguousarray(light, np.float32)[:3].copy()
-        sp = None
-        if seeds is not None:
-            seeds = np.ascontiguousarray(seeds, np.int32).reshape(-1)
-            if seeds.shape[0] != k:
-                raise ValueError("seeds must have one entry per ray")
-            sp = seeds.ctypes.data_as(C.POINTER(C.c_int32))
+        sp = _seeds_ptr(seeds, k, "ray")
         out = np.zeros((k, 4), np.float32)
         prim = np.zeros(k, np.int32) if want_prim else None
         _check(lib().rt_radiance_rays(self._h, _fp(rays), sp, k, _fp(li), _fp(out),
@@ -584,30 +586,21 @@ class RayTracer:
         None (not computed).  stream: a torch stream or a raw hipStream_t (default: torch's current stream).  Returns out,
         or (out, out_prim) when out_prim is given."""
         import torch
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
-
-        def _need(name, t, dtype, shape):
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("%s must be a torch tensor" % name)
-            if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
-                                 % (name, dtype, shape, dev, t.dtype, tuple(t.shape), t.device))
+        dev = self._torch_device()
 
         if not isinstance(rays6, torch.Tensor) or rays6.dim() != 2:
             raise ValueError("rays6 must be a torch tensor of shape [k, 6]")
         k = rays6.shape[0]
-        _need("rays6", rays6, torch.float32, (k, 6))
+        _need("rays6", rays6, torch.float32, (k, 6), dev)
         if seeds is not None:
-            _need("seeds", seeds, torch.int32, (k,))
+            _need("seeds", seeds, torch.int32, (k,), dev)
         if out is None:
             out = torch.empty((k, 4), dtype=torch.float32, device=dev)
-        _need("out", out, torch.float32, (k, 4))
+        _need("out", out, torch.float32, (k, 4), dev)
         if out_prim is not None:
-            _need("out_prim", out_prim, torch.int32, (k,))
+            _need("out_prim", out_prim, torch.int32, (k,), dev)
         li = np.ascontiguousarray(light, np.float32)[:3].copy()
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        raw = getattr(stream, "cuda_stream", stream) or 0
+        raw = self._raw_stream(stream, dev)
         if k:
             _check(lib().rt_radiance_rays_device(self._h, C.c_void_p(rays6.data_ptr()),
                                                  C.c_void_p(seeds.data_ptr() if seeds is not None else 0), k, _fp(li),
@@ -618,9 +611,7 @@ class RayTracer:
 
     def radiance_stats(self):
         """Work counters of the context's most recent radiance call (rt_debug_radiance_stats): dict of RADIANCE_STATS_KEYS."""
-        out = (C.c_uint64 * 8)()
-        _check(lib().rt_debug_radiance_stats(self._h, out))
-        return {key: int(out[i]) for i, key in enumerate(RADIANCE_STATS_KEYS)}
+        return self._stats("rt_debug_radiance_stats", RADIANCE_STATS_KEYS)
 
     def render_panorama(self, width, height, cam, light, yaw=0.0):
         """An equirectangular 360 x 180 degree view from `cam`, on the device (rt_radiance_rays_device) -> torch float32
@@ -635,7 +626,7 @@ class RayTracer:
         width, height = int(width), int(height)
         if width < 1 or height < 1:
             raise ValueError("width and height must be positive")
-        dev = torch.device("cuda", self.device if self.device is not None else torch.cuda.current_device())
+        dev = self._torch_device()
         f32 = dict(dtype=torch.float32, device=dev)
         xs = (torch.arange(width, **f32) + 0.5) * torch.tensor(2.0 * math.pi, **f32) / torch.tensor(float(width), **f32)
         phi = torch.tensor(float(yaw), **f32) + xs - torch.tensor(math.pi, **f32)
@@ -651,9 +642,7 @@ class RayTracer:
 
     def trace_stats(self):
         """Work counters of the context's most recent query (rt_debug_trace_stats): dict of TRACE_STATS_KEYS."""
-        out = (C.c_uint64 * 8)()
-        _check(lib().rt_debug_trace_stats(self._h, out))
-        return {key: int(out[i]) for i, key in enumerate(TRACE_STATS_KEYS)}
+        return self._stats("rt_debug_trace_stats", TRACE_STATS_KEYS)
 
     def wave_timeline(self):
         """Wave kernel, context created with UOB_RT_TIMELINE=1: start / end statistics of the last frame's persistent waves
