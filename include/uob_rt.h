@@ -130,6 +130,45 @@ int rt_update_scene(rt_ctx* ctx, const float* vertices4, const float* normals4, 
 int rt_update_scene_device(rt_ctx* ctx, const void* d_vertices4, const void* d_normals4, const void* d_colors4, int32_t n,
                            uint32_t flags, void* hip_stream);
 
+/* RT_UPDATE_DEVICE_TILES (both entries above and both below; excludes RT_UPDATE_REORDER): the triangles are sorted into
+ * tiles again ON THE DEVICE, large triangles first and the rest in Morton order of their centres — for a mesh that has
+ * deformed far from its old tiles without leaving the GPU.  The order is the one rt_init makes under
+ * UOB_RT_TILE_ORDER=morton, index for index; the kd split of rt_init's default order exists on the host only.      */
+#define RT_UPDATE_DEVICE_TILES 2u
+
+/* Replace the context's triangles by a scene of ANY count n_new >= 1 (rt_init's limits on n apply): objects appear and
+ * disappear, a level of detail switches.  Same packed layout and ownership as rt_init.  After RT_OK every later operation
+ * of the context — frames, AOV passes, ray queries, shade and radiance calls, the counting passes — gives exactly the bits
+ * that a context rt_init'ed with the new scene, the context's current spheres and the same rt_config gives.  Which kernel
+ * runs is decided as rt_init decides it, so a replace may cross n = 64 in either direction.  The registered output range,
+ * the multi-device layout, the tuning read at rt_init and the staging of the calls beside the frame survive; so does the
+ * scheduling state ("last frame's expensive jobs first") unless the scene crosses n = 64: then the next frame is a first
+ * frame.  Validation is rt_init's (finite, |x| <= 2^16, count limits); on any validation or allocation error the context
+ * keeps its previous scene, whole.  The buffers sized by n only grow: a replace that fits the capacity
+ * (rt_debug_scene_capacity) allocates and frees none of them, and a smaller scene keeps the capacity.  The tiles of a mesh
+ * are made on the host as rt_init makes them (RT_UPDATE_REORDER is accepted and changes nothing), or on the device with
+ * RT_UPDATE_DEVICE_TILES.  Ordering as rt_update_scene: it waits for the context's previous frame and calls; a
+ * multi-device context replaces the scene of every device.  Blocking.                                               */
+int rt_replace_scene(rt_ctx* ctx, const float* vertices4, const float* normals4, const float* colors4, int32_t n_new,
+                     uint32_t flags);
+
+/* Same, from device memory on the context's device, enqueued on hip_stream exactly like rt_update_scene_device: the call
+ * returns once the first pass (bound, n_shadow, box) has been read back; copies, the tile build and the refit may still be
+ * running, nothing of the scene goes through host memory, and later operations of the context, on any stream, wait for
+ * them on the device.  The tiles are made on the device (RT_UPDATE_DEVICE_TILES is implied); RT_UPDATE_REORDER asks for
+ * the host's tiles instead and stages the scene through the host.  A scene beyond the capacity allocates new buffers and
+ * frees the old ones, which synchronises the device.  If the check fails the context keeps its previous scene.        */
+int rt_replace_scene_device(rt_ctx* ctx, const void* d_vertices4, const void* d_normals4, const void* d_colors4,
+                            int32_t n_new, uint32_t flags, void* hip_stream);
+
+/* Replace the sphere table (0..RT_MAX_SPHERES entries; centres, radii and materials may all change).  Validation is
+ * rt_init's; on an error the context keeps its spheres.  Later operations see the new table exactly as a context
+ * rt_init'ed with it in rt_config would.  Waits for the context's earlier work; blocking, tiny.                     */
+int rt_update_spheres(rt_ctx* ctx, const rt_sphere* spheres, int32_t num_spheres);
+
+/* Diagnostic: triangles the context's buffers can hold without allocating.                                          */
+int rt_debug_scene_capacity(rt_ctx* ctx, int64_t* out_triangles);
+
 /* Render one frame and read it back: rot = 3 rows x (x,y,z,pad) exactly as rot_matrix[12] at
  * skeleton.cpp:149-151; cam/light = first 12 bytes of camera_position / light_position (:162,:164);
  * focal = focal_length (:166), in units of AA sub-pixels along x.  out_argb receives

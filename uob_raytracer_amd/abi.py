@@ -12,6 +12,7 @@ RT_FLAG_PLAIN_ORDER = 16
 RT_FLAG_STAGED_GATHER = 32
 RT_TRACE_IN_SHADOW, RT_TRACE_CLOSEST_HIT = 0, 1
 RT_UPDATE_REORDER = 1
+RT_UPDATE_DEVICE_TILES = 2
 RT_AOV_ALL_SAMPLES = -1
 RT_SHADE_SEED_MAX = 1 << 24     # rt_shade_points: seeds are global ids 0 .. 2^24; NULL seeds = k & RT_SHADE_SEED_MASK
 RT_SHADE_SEED_MASK = 0xFFFFFF

@@ -13,6 +13,7 @@
 //                 [--obj mesh.obj]            append load_obj(mesh.obj) to the box, as skeleton.cpp:102-103 does
 //                 [--move DX,DY,DZ]           with --obj: update() slides the mesh by (DX,DY,DZ) every frame (float32
 //                                             adds to its vertices; normals do not change), rt_update_scene before the frame
+//                 [--bounce-sphere]           sphere 0 follows a parabola, frame by frame (rt_update_spheres)
 //                 [--gpus N | --devices a,b,..]  render every frame on several GPUs inside the one context
 //                 [--copy-back]                  device buffer + blocking read-back instead of rt_register_output
 #include <chrono>
@@ -46,6 +47,9 @@ static size_t g_key_at = 0;
 static size_t g_obj_first = 0;                                 // --move: the loaded mesh is triangles[g_obj_first..]
 static bool g_move = false;
 static float g_move_by[3] = {0.0f, 0.0f, 0.0f};
+static bool g_bounce = false;                                  // --bounce-sphere: sphere 0 follows a parabola, frame by frame
+static rt_sphere g_spheres[RT_MAX_SPHERES];
+static int g_num_spheres = 0;
 
 static void die(const char* op) {                              // checkError(), :499-507
   fprintf(stderr, "Error during operation '%s': %s\n", op, rt_last_error());
@@ -65,6 +69,14 @@ void update_scene() {
   vector<float> v(12 * (size_t)n), nr(4 * (size_t)n), col(4 * (size_t)n);
   rt_scene_pack(triangles.data(), n, v.data(), nr.data(), col.data());
   if (rt_update_scene(g_rt, v.data(), nr.data(), col.data(), n, 0) != RT_OK) die("rt_update_scene");
+}
+
+// Sphere 0 of frame f = 1, 2, ... on a fixed parabola (one bounce in eight frames), to the device before the frame
+void bounce_sphere(int f) {
+  const float u = (float)(f % 8) * 0.125f;
+  g_spheres[0].center[0] = 0.3f - u * 0.25f;
+  g_spheres[0].center[1] = 0.1f - (u * (1.0f - u)) * 0.8f;
+  if (rt_update_spheres(g_rt, g_spheres, g_num_spheres) != RT_OK) die("rt_update_spheres");
 }
 
 void offload_rendering(screen* screen) {                       // :146-182
@@ -134,6 +146,7 @@ int main(int argc, char* argv[]) {
       if (sscanf(argv[++i], "%f,%f,%f", &g_move_by[0], &g_move_by[1], &g_move_by[2]) != 3) { fprintf(stderr, "--move DX,DY,DZ\n"); return 2; }
       g_move = true;
     }
+    else if (a == "--bounce-sphere") g_bounce = true;
     else if (a == "--copy-back") direct_out = false;           // render into device memory + blocking copy, as the reference reads back
     else if (a == "--gpus" && i + 1 < argc) {
       cfg.num_devices = atoi(argv[++i]);
@@ -155,6 +168,8 @@ int main(int argc, char* argv[]) {
   triangles.resize(n);
   g_obj_first = triangles.size();
   if (g_move && !obj) { fprintf(stderr, "--move needs --obj\n"); return 2; }
+  g_num_spheres = cfg.num_spheres;
+  for (int i = 0; i < RT_MAX_SPHERES; ++i) g_spheres[i] = cfg.spheres[i];
   if (obj) {                                                                   // load_obj + insert, :102-103
     const int m = rt_scene_load_obj(obj, nullptr, 0);
     if (m < 0) die("rt_scene_load_obj");
@@ -173,6 +188,7 @@ int main(int argc, char* argv[]) {
   for (int f = 0; f < frames && !quit; ++f) {                                  // :117-138
     update();
     if (g_move) update_scene();
+    if (g_bounce) bounce_sphere(f + 1);
     auto start = high_resolution_clock::now();
     offload_rendering(screen);
     auto stop = high_resolution_clock::now();

@@ -46,6 +46,17 @@ using namespace uobrt;
 
 constexpr int kWorldGrid = 32;       // world cells per axis of the mesh kernel's shadow-ray tile masks
 
+// rt_init's and rt_update_spheres' bounds of a sphere table (the count is checked by the caller)
+static int validate_spheres(const rt_sphere* sph, int num) {
+  for (int i = 0; i < num; ++i) {
+    const rt_sphere& s = sph[i];
+    for (int k = 0; k < 3; ++k)
+      if (!(fabsf(s.center[k]) <= kMaxCoordinate)) { set_error("sphere %d: |centre| must be finite and <= 2^16", i); return RT_E_INVALID; }
+    if (!(fabsf(s.radius_sq) <= kMaxCoordinate * kMaxCoordinate)) { set_error("sphere %d: radius_sq must be finite and <= 2^32", i); return RT_E_INVALID; }
+  }
+  return RT_OK;
+}
+
 static int validate_config(const rt_config* c) {
   if (!c) { set_error("rt_config is NULL"); return RT_E_INVALID; }
   if (c->width < 1 || c->height < 1 || c->width > 32767 || c->height > 32767) {
@@ -60,12 +71,7 @@ static int validate_config(const rt_config* c) {
     set_error("band partition invalid (rows=%d index=%d count=%d)", c->band_rows, c->band_index, c->band_count); return RT_E_INVALID;
   }
   if (!(c->light_spread >= 0.0f) || !(c->light_spread <= kMaxCoordinate)) { set_error("light_spread must be in [0, 2^16]"); return RT_E_INVALID; }
-  for (int i = 0; i < c->num_spheres; ++i) {
-    const rt_sphere& s = c->spheres[i];
-    for (int k = 0; k < 3; ++k)
-      if (!(fabsf(s.center[k]) <= kMaxCoordinate)) { set_error("sphere %d: |centre| must be finite and <= 2^16", i); return RT_E_INVALID; }
-    if (!(fabsf(s.radius_sq) <= kMaxCoordinate * kMaxCoordinate)) { set_error("sphere %d: radius_sq must be finite and <= 2^32", i); return RT_E_INVALID; }
-  }
+  if (validate_spheres(c->spheres, c->num_spheres) != RT_OK) return RT_E_INVALID;
   if ((double)c->width * c->height > 16777216.0) {
     // global_id = y*W+x is formed in FP32 by the reference (kernels.cl:380): exact only up to 2^24
     set_error("width*height must not exceed 2^24 (the reference's FP32 pixel id)"); return RT_E_INVALID;
@@ -115,7 +121,7 @@ static int count_shadow_casters(const float* colors4, int n) {
   return cnt;
 }
 
-// The tiled copy into the context's buffers (allocated on first use), on c->stream; blocking
+// The tiled copy into the context's buffers (scene_reserve has made them), on c->stream; blocking
 static int upload_tiled(rt_ctx* c, const float* v4, const float* n4, const float* c4, const std::vector<int>& orig,
                         const std::vector<float>& box) {
   const int n = c->n, ntiles = mesh_tiles(n);
@@ -127,12 +133,6 @@ static int upload_tiled(rt_ctx* c, const float* v4, const float* n4, const float
     memcpy(&pc[(size_t)4 * j], c4 + (size_t)4 * i, 16);
   }
   const size_t nb = (size_t)n * sizeof(float4);
-  if (!c->d_verts_m &&
-      (hipMalloc(&c->d_verts_m, 3 * nb) != hipSuccess || hipMalloc(&c->d_normals_m, nb) != hipSuccess ||
-       hipMalloc(&c->d_colors_m, nb) != hipSuccess || hipMalloc(&c->d_orig, (size_t)n * sizeof(int)) != hipSuccess ||
-       hipMalloc(&c->d_tile_box, (size_t)ntiles * 3 * sizeof(float4)) != hipSuccess)) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
-  }
   if (hipMemcpyAsync(c->d_verts_m, pv.data(), 3 * nb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipMemcpyAsync(c->d_normals_m, pn.data(), nb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipMemcpyAsync(c->d_colors_m, pc.data(), nb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -143,6 +143,24 @@ static int upload_tiled(rt_ctx* c, const float* v4, const float* n4, const float
   }
   return RT_OK;
 }
+
+// The context's sphere table (cfg.spheres) into device memory; blocking
+static int upload_spheres(rt_ctx* c) {
+  const rt_config* cfg = &c->cfg;
+  DevSphere tab[RT_MAX_SPHERES];
+  memset(tab, 0, sizeof tab);
+  for (int i = 0; i < cfg->num_spheres; ++i) {
+    tab[i].cx = cfg->spheres[i].center[0]; tab[i].cy = cfg->spheres[i].center[1]; tab[i].cz = cfg->spheres[i].center[2];
+    tab[i].r2 = cfg->spheres[i].radius_sq;
+    memcpy(tab[i].col, cfg->spheres[i].color, 16);
+  }
+  if (hipMemcpy(c->d_spheres, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("sphere table upload failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
+  }
+  return RT_OK;
+}
+
+static int scene_first(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n);   // below, with the scene updates
 
 static int upload_tiled_scene(rt_ctx* c, const float* v4, const float* n4, const float* c4) {
   const std::vector<int> orig = tiled_order(v4, c->n, c->tune.tile_morton);
@@ -180,7 +198,7 @@ int32_t rt_config_owned_rows(const rt_config* c) {
 // Every surface point lies on a triangle or a sphere: their bounding box, from the vertices' (the world grid of the
 // mesh kernel's shadow-ray tile masks spans it: fill_params)
 static void set_scene_box(rt_ctx* c, const float vlo[3], const float vhi[3]) {
-  for (int k = 0; k < 3; ++k) { c->box_lo[k] = vlo[k]; c->box_hi[k] = vhi[k]; }
+  for (int k = 0; k < 3; ++k) { c->box_lo[k] = c->vbox_lo[k] = vlo[k]; c->box_hi[k] = c->vbox_hi[k] = vhi[k]; }
   const rt_config* cfg = &c->cfg;
   for (int i = 0; i < cfg->num_spheres; ++i) {
     const float r = sqrtf(fmaxf(cfg->spheres[i].radius_sq, 0.0f)) * 1.0001f + 1e-6f;
@@ -205,7 +223,7 @@ static int init_parent(const rt_config* cfg, const float* vertices4, const float
   std::string downgrade;                     // devices that will copy band by band (reported through rt_last_error)
   p->cfg = *cfg;
   p->device = cfg->devices[0];
-  p->n = n;
+  p->n = n; p->cap = n > 0 ? n : 1;
   p->owned_rows = rt_config_owned_rows(cfg);
   const int dbr = cfg->device_band_rows > 0 ? cfg->device_band_rows : 32;
   p->cfg.device_band_rows = dbr;
@@ -272,37 +290,13 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
   else hipGetDevice(&c->device);
   auto fail = [&](int code) { rt_destroy(c); return code; };
   if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", c->device); return fail(RT_E_DEVICE); }
-  c->n = n;
   c->owned_rows = rt_config_owned_rows(cfg);
   if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || c->cus < 1) c->cus = 256;
-  const size_t nb = (size_t)(n > 0 ? n : 1) * sizeof(float4);
   const size_t px = (size_t)(c->owned_rows > 0 ? c->owned_rows : 1) * cfg->width;
-  if (hipMalloc(&c->d_verts, 3 * nb) != hipSuccess || hipMalloc(&c->d_normals, nb) != hipSuccess ||
-      hipMalloc(&c->d_colors, nb) != hipSuccess || hipMalloc(&c->d_argb, px * 4) != hipSuccess ||
-      hipMalloc(&c->d_counters, sizeof(rt_work)) != hipSuccess || hipMalloc(&c->d_jobctr, (2 * kJobHeads + 2) * kJobHeadStride * sizeof(unsigned int)) != hipSuccess) {
+  if (hipMalloc(&c->d_argb, px * 4) != hipSuccess || hipMalloc(&c->d_counters, sizeof(rt_work)) != hipSuccess ||
+      hipMalloc(&c->d_jobctr, (2 * kJobHeads + 2) * kJobHeadStride * sizeof(unsigned int)) != hipSuccess ||
+      hipMalloc(&c->d_spheres, RT_MAX_SPHERES * sizeof(DevSphere)) != hipSuccess) {
     set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_NOMEM);
-  }
-  if (n > 64 && hipMalloc(&c->d_records, (size_t)n * kRecordsPerTriangle * sizeof(float4)) != hipSuccess) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_NOMEM);
-  }
-  // candidate-tile masks: from 17 tiles on (with fewer, building and reading them costs more than the visits they save)
-  if (n > 16 * 64 && !(cfg->flags & (RT_FLAG_NO_TILE_BINS | RT_FLAG_NO_CULL | RT_FLAG_GENERIC_KERNEL))) {
-    c->nwords = (mesh_tiles(n) + 63) / 64;
-    c->scx = mesh_screen_cells(cfg->width); c->scy = mesh_screen_cells(cfg->height);
-    const size_t g3 = (size_t)kWorldGrid * kWorldGrid * kWorldGrid;
-    if (hipMalloc(&c->d_screen_masks, (size_t)c->scx * c->scy * c->nwords * 8) != hipSuccess ||
-        hipMalloc(&c->d_world_masks, g3 * c->nwords * 8) != hipSuccess ||
-        hipMalloc(&c->d_world_occ, (size_t)mesh_occ_words(kWorldGrid) * sizeof(unsigned int)) != hipSuccess) {
-      set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_NOMEM);
-    }
-    if (hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
-      set_error("stream/event creation failed"); return fail(RT_E_DEVICE);
-    }
-    float lo[3], hi[3];
-    vertex_box(vertices4, n, lo, hi);
-    set_scene_box(c, lo, hi);
   }
   {   // wave kernel: lists of last frame's expensive jobs (sized for the smallest job, one 64-ray task)
     const int aa = cfg->aa_x * cfg->aa_y;
@@ -310,50 +304,15 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
     const size_t jobs_max = (size_t)((cfg->width + pt - 1) / pt) * (size_t)(c->owned_rows > 0 ? c->owned_rows : 1);
     c->heavy_cap = (int)(jobs_max / 3 > 64 ? jobs_max / 3 : 64);
     c->heavy_jobs_max = jobs_max;
-    if (hipMemset(c->d_jobctr, 0, (2 * kJobHeads + 2) * kJobHeadStride * sizeof(unsigned int)) != hipSuccess) {
-      set_error("hipMemset failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_DEVICE);
-    }
-    if (n >= 1 && n <= 64 && !c->tune.plain_order) {
-      if (hipMalloc(&c->d_heavy[0], (size_t)c->heavy_cap * 4) != hipSuccess || hipMalloc(&c->d_heavy[1], (size_t)c->heavy_cap * 4) != hipSuccess ||
-          hipMalloc(&c->d_heavy_flags, 2 * jobs_max * 4) != hipSuccess || hipMemset(c->d_heavy_flags, 0, 2 * jobs_max * 4) != hipSuccess) {
-        set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_NOMEM);
-      }
-    }
   }
   if (hipStreamCreate(&c->stream) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
     set_error("stream/event creation failed"); return fail(RT_E_DEVICE);
   }
-  if (n > 0) {   // blocking uploads, as the CL_TRUE writes at skeleton.cpp:486-496
-    if (hipMemcpy(c->d_verts, vertices4, 3 * nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_normals, normals4, nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_colors, colors4, nb, hipMemcpyHostToDevice) != hipSuccess) {
-      set_error("scene upload failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_DEVICE);
-    }
-  }
-  {
-    DevSphere tab[RT_MAX_SPHERES];
-    memset(tab, 0, sizeof tab);
-    for (int i = 0; i < cfg->num_spheres; ++i) {
-      tab[i].cx = cfg->spheres[i].center[0]; tab[i].cy = cfg->spheres[i].center[1]; tab[i].cz = cfg->spheres[i].center[2];
-      tab[i].r2 = cfg->spheres[i].radius_sq;
-      memcpy(tab[i].col, cfg->spheres[i].color, 16);
-    }
-    if (hipMalloc(&c->d_spheres, sizeof tab) != hipSuccess || hipMemcpy(c->d_spheres, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) {
-      set_error("sphere table upload failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_DEVICE);
-    }
-  }
-  c->n_shadow = count_shadow_casters(colors4, n);
-  if (n > 64 && !(cfg->flags & RT_FLAG_GENERIC_KERNEL)) {
-    rc = upload_tiled_scene(c, vertices4, normals4, colors4);
-    if (rc != RT_OK) return fail(rc);
-    if (!c->tune.plain_order) {
-      const size_t jobs = (size_t)((cfg->width + 15) / 16) * (size_t)((c->owned_rows + 15) / 16);
-      // order list: up to four entries per block, + its length in the word behind it
-      if (hipMalloc(&c->d_mesh_cost, (jobs ? jobs : 1) * 4) != hipSuccess || hipMalloc(&c->d_mesh_order, (4 * (jobs ? jobs : 1) + 1) * 4) != hipSuccess) {
-        set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_NOMEM);
-      }
-    }
-  }
+  rc = upload_spheres(c);
+  if (rc != RT_OK) return fail(rc);
+  // the scene: buffers by n, upload, tiles, n_shadow, scene box, kernel family — the routine rt_replace_scene calls too
+  rc = scene_first(c, vertices4, normals4, colors4, n);
+  if (rc != RT_OK) return fail(rc);
   *out_ctx = c;
   return RT_OK;
 }
@@ -586,23 +545,183 @@ static void update_state(rt_ctx* c, const SceneSummary& sum) {
   if (c->d_screen_masks) set_scene_box(c, sum.lo, sum.hi);
 }
 
-// Host arrays (validated) into one single-device context; blocking
-static int update_host_one(rt_ctx* c, const float* v4, const float* n4, const float* c4, uint32_t flags, const SceneSummary& sum) {
-  const int n = c->n;
+// ---- the scene of a context: rt_init's first one and every replacement (rt_replace_scene*) ---------------------------
+// Which buffers a scene of n triangles needs, by rt_init's rules
+struct SceneNeeds {
+  bool records, tiled, masks, heavy, mesh_sched;
+};
+
+static SceneNeeds scene_needs(const rt_ctx* c, int n) {
+  const int f = c->cfg.flags;
+  SceneNeeds q;
+  q.records = n > 64;                                        // the staged records of the generic and mesh kernels
+  q.tiled = n > 64 && !(f & RT_FLAG_GENERIC_KERNEL);         // the mesh kernel's tiled copy
+  // candidate-tile masks: from 17 tiles on (with fewer, building and reading them costs more than the visits they save)
+  q.masks = n > 16 * 64 && !(f & (RT_FLAG_NO_TILE_BINS | RT_FLAG_NO_CULL | RT_FLAG_GENERIC_KERNEL));
+  q.heavy = n >= 1 && n <= 64 && !c->tune.plain_order;       // wave kernel: last frame's expensive jobs
+  q.mesh_sched = q.tiled && !c->tune.plain_order;            // mesh kernel: last frame's block costs
+  return q;
+}
+
+// New buffers of a scene that outgrows the context's capacity; they replace the old ones only in scene_commit, when every
+// allocation of every device has succeeded
+struct SceneGrowth {
+  int cap = 0;                                               // 0: the scene fits, nothing to replace
+  float4 *verts = nullptr, *normals = nullptr, *colors = nullptr;
+  SceneStore t;
+};
+
+static void free_growth(SceneGrowth* g) {
+  hipFree(g->verts); hipFree(g->normals); hipFree(g->colors); hipFree(g->t.records);
+  hipFree(g->t.verts_m); hipFree(g->t.normals_m); hipFree(g->t.colors_m); hipFree(g->t.orig); hipFree(g->t.tile_box);
+  hipFree(g->t.screen_masks); hipFree(g->t.world_masks);
+  *g = SceneGrowth();
+}
+
+// Everything a scene of n triangles needs that the context does not hold yet.  Nothing the context renders from is touched:
+// what outgrows the capacity goes into *g; what the context meets for the first time (the buffers of a kernel family it has
+// not run yet) goes into its store, which no frame reads before scene_select.  device_tiles: the device tile build will run.
+static int scene_reserve(rt_ctx* c, int n, bool device_tiles, SceneGrowth* g) {
+  if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", c->device); return RT_E_DEVICE; }
+  const SceneNeeds q = scene_needs(c, n);
+  const rt_config& cfg = c->cfg;
+  SceneStore& o = c->own;
+  bool ok = true;
+  auto get = [&](auto** p, size_t bytes) { if (ok && hipMalloc(p, bytes ? bytes : 1) != hipSuccess) ok = false; };
+  auto tiled_set = [&](SceneStore* t, int cap) {
+    const size_t nb = (size_t)cap * sizeof(float4);
+    get(&t->verts_m, 3 * nb); get(&t->normals_m, nb); get(&t->colors_m, nb); get(&t->orig, (size_t)cap * sizeof(int));
+    get(&t->tile_box, (size_t)mesh_tiles(cap) * 3 * sizeof(float4));
+  };
+  auto mask_set = [&](SceneStore* t, int cap) {
+    const size_t nwords = (size_t)((mesh_tiles(cap) + 63) / 64), g3 = (size_t)kWorldGrid * kWorldGrid * kWorldGrid;
+    get(&t->screen_masks, (size_t)mesh_screen_cells(cfg.width) * mesh_screen_cells(cfg.height) * nwords * 8);
+    get(&t->world_masks, g3 * nwords * 8);
+  };
+  const bool grow = n > c->cap || !c->d_verts;
+  const int cap = grow ? (n > 0 ? n : 1) : c->cap;
+  if (grow) {    // (what the context already keeps for another family grows too: a later replace within capacity allocates nothing)
+    const size_t nb = (size_t)cap * sizeof(float4);
+    g->cap = cap;
+    get(&g->verts, 3 * nb); get(&g->normals, nb); get(&g->colors, nb);
+    if (q.records || o.records) get(&g->t.records, (size_t)cap * kRecordsPerTriangle * sizeof(float4));
+    if (q.tiled || o.verts_m) tiled_set(&g->t, cap);
+    if (q.masks || o.screen_masks) mask_set(&g->t, cap);
+  } else {
+    if (q.records && !o.records) get(&o.records, (size_t)cap * kRecordsPerTriangle * sizeof(float4));
+    if (q.tiled && !o.verts_m) tiled_set(&o, cap);
+    if (q.masks && !o.screen_masks) mask_set(&o, cap);
+  }
+  if (q.masks && !o.world_occ) get(&o.world_occ, (size_t)mesh_occ_words(kWorldGrid) * sizeof(unsigned int));
+  if (q.heavy && !o.heavy_flags) {
+    get(&o.heavy[0], (size_t)c->heavy_cap * 4); get(&o.heavy[1], (size_t)c->heavy_cap * 4); get(&o.heavy_flags, 2 * c->heavy_jobs_max * 4);
+  }
+  if (q.mesh_sched && !o.mesh_cost) {
+    const size_t jobs = (size_t)((cfg.width + 15) / 16) * (size_t)((c->owned_rows + 15) / 16);
+    // order list: up to four entries per block, + its length in the word behind it
+    get(&o.mesh_cost, (jobs ? jobs : 1) * 4); get(&o.mesh_order, (4 * (jobs ? jobs : 1) + 1) * 4);
+  }
+  if (!ok) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); free_growth(g); return RT_E_NOMEM; }
+  if (device_tiles && q.tiled) {
+    const int rc = ensure_bytes(&c->tile_scratch, tile_build_scratch_bytes(cap));
+    if (rc != RT_OK) { free_growth(g); return rc; }
+  }
+  if (q.masks && !c->aux_stream &&
+      (hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess ||
+       hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
+       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)) {
+    set_error("stream/event creation failed"); free_growth(g); return RT_E_DEVICE;
+  }
+  return RT_OK;
+}
+
+// The grown buffers take the place of the old ones.  hipFree waits for whatever still uses what it frees.  From here to
+// scene_select the context's working pointers are stale: the caller installs the new scene next, and nothing in between fails
+// for a reason the caller could have (validation and allocation are behind it).
+static void scene_commit(rt_ctx* c, SceneGrowth* g) {
+  if (!g->cap) return;
+  hipSetDevice(c->device);
+  SceneStore& o = c->own;
+  hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);
+  hipFree(o.records); hipFree(o.verts_m); hipFree(o.normals_m); hipFree(o.colors_m); hipFree(o.orig); hipFree(o.tile_box);
+  hipFree(o.screen_masks); hipFree(o.world_masks);
+  hipFree(c->d_qrecords); c->d_qrecords = nullptr;           // (the queries make theirs on demand, for the capacity)
+  c->d_verts = g->verts; c->d_normals = g->normals; c->d_colors = g->colors;
+  o.records = g->t.records;
+  o.verts_m = g->t.verts_m; o.normals_m = g->t.normals_m; o.colors_m = g->t.colors_m; o.orig = g->t.orig; o.tile_box = g->t.tile_box;
+  o.screen_masks = g->t.screen_masks; o.world_masks = g->t.world_masks;
+  c->cap = g->cap;
+  *g = SceneGrowth();
+}
+
+// The working pointers for a scene of n triangles: which kernel runs is decided from them, as rt_init decides it
+static void scene_select(rt_ctx* c, int n) {
+  const SceneNeeds q = scene_needs(c, n);
+  const SceneStore& o = c->own;
+  c->n = n;
+  c->d_records = q.records ? o.records : nullptr;
+  c->d_verts_m = q.tiled ? o.verts_m : nullptr; c->d_normals_m = q.tiled ? o.normals_m : nullptr;
+  c->d_colors_m = q.tiled ? o.colors_m : nullptr; c->d_orig = q.tiled ? o.orig : nullptr; c->d_tile_box = q.tiled ? o.tile_box : nullptr;
+  c->d_screen_masks = q.masks ? o.screen_masks : nullptr; c->d_world_masks = q.masks ? o.world_masks : nullptr;
+  c->d_world_occ = q.masks ? o.world_occ : nullptr;
+  c->nwords = q.masks ? (mesh_tiles(n) + 63) / 64 : 0;
+  c->scx = q.masks ? mesh_screen_cells(c->cfg.width) : 0; c->scy = q.masks ? mesh_screen_cells(c->cfg.height) : 0;
+  c->d_heavy[0] = q.heavy ? o.heavy[0] : nullptr; c->d_heavy[1] = q.heavy ? o.heavy[1] : nullptr;
+  c->d_heavy_flags = q.heavy ? o.heavy_flags : nullptr;
+  c->d_mesh_cost = q.mesh_sched ? o.mesh_cost : nullptr; c->d_mesh_order = q.mesh_sched ? o.mesh_order : nullptr;
+}
+
+// Switch the context to a scene of n triangles, on stream s behind update_begin.  The scheduling state is indexed by screen
+// jobs and blocks, not by triangles: it is kept unless the scene crosses n = 64 (or is the first): then the next frame is a
+// first frame, the state rt_init leaves.
+static int scene_switch(rt_ctx* c, int n, bool first, hipStream_t s) {
+  const bool restart = first || (c->n > 64) != (n > 64);
+  scene_select(c, n);
+  if (!restart) return RT_OK;
+  c->mesh_order_valid = false;
+  c->heavy_phase = 0; c->heavy_gen = 0;
+  HIP_TRY(hipMemsetAsync(c->d_jobctr, 0, (2 * kJobHeads + 2) * kJobHeadStride * sizeof(unsigned int), s));
+  if (c->d_heavy_flags) HIP_TRY(hipMemsetAsync(c->d_heavy_flags, 0, 2 * c->heavy_jobs_max * 4, s));
+  return RT_OK;
+}
+
+// Morton tiles on the device into d_orig (rt_tile_build.hip); rt_scene_refit follows
+static int device_tiles(rt_ctx* c, const SceneSummary& sum, hipStream_t s) {
+  if (launch_tile_build(c->d_verts, c->n, sum.lo, sum.hi, c->d_orig, c->tile_scratch.p, s) != 0) {
+    set_error("tile build launch failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
+  }
+  return RT_OK;
+}
+
+static void refit(rt_ctx* c, hipStream_t s) {
+  launch_scene_refit(c->d_verts, c->d_normals, c->d_colors, c->d_orig, c->n, c->d_verts_m, c->d_normals_m, c->d_colors_m,
+                     c->d_tile_box, s);
+}
+
+// Host arrays (validated) into one single-device context; blocking.  replace: a scene of n triangles takes the place of
+// the context's (scene_reserve / scene_commit are behind it); else n is the context's count.
+static int scene_host_one(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n, uint32_t flags,
+                          const SceneSummary& sum, bool replace, bool first = false) {
   int rc = update_begin(c, c->stream);
   if (rc != RT_OK) return rc;
+  if (replace) { rc = scene_switch(c, n, first, c->stream); if (rc != RT_OK) return rc; }
   const size_t nb = (size_t)n * sizeof(float4);
-  HIP_TRY(hipMemcpyAsync(c->d_verts, v4, 3 * nb, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_normals, n4, nb, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->d_colors, c4, nb, hipMemcpyHostToDevice, c->stream));
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(c->d_verts, v4, 3 * nb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_normals, n4, nb, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_colors, c4, nb, hipMemcpyHostToDevice, c->stream));
+  }
   if (c->d_verts_m) {
-    if (flags & RT_UPDATE_REORDER) {
-      const std::vector<int> orig = tiled_order(v4, n, c->tune.tile_morton);
-      rc = upload_tiled(c, v4, n4, c4, orig, tile_data_host(v4, orig.data(), n));
+    if (flags & RT_UPDATE_DEVICE_TILES) {
+      rc = device_tiles(c, sum, c->stream);
+      if (rc != RT_OK) return rc;
+      refit(c, c->stream);
+      HIP_TRY(hipGetLastError());
+    } else if (replace || (flags & RT_UPDATE_REORDER)) {
+      rc = upload_tiled_scene(c, v4, n4, c4);
       if (rc != RT_OK) return rc;
     } else {
-      launch_scene_refit(c->d_verts, c->d_normals, c->d_colors, c->d_orig, n, c->d_verts_m, c->d_normals_m, c->d_colors_m,
-                         c->d_tile_box, c->stream);
+      refit(c, c->stream);
       HIP_TRY(hipGetLastError());
     }
   }
@@ -612,12 +731,12 @@ static int update_host_one(rt_ctx* c, const float* v4, const float* n4, const fl
 }
 
 // Device arrays on device src_dev (validated) into one single-device context, enqueued on `s` (a stream of c->device)
-static int update_device_one(rt_ctx* c, const void* dv, const void* dn, const void* dc, int src_dev, hipStream_t s,
-                             const SceneSummary& sum) {
-  const int n = c->n;
+static int scene_device_one(rt_ctx* c, const void* dv, const void* dn, const void* dc, int src_dev, int n, uint32_t flags,
+                            hipStream_t s, const SceneSummary& sum, bool replace) {
   int rc = update_begin(c, s);
   if (rc != RT_OK) return rc;
   if (!c->ev_upd) HIP_TRY(hipEventCreateWithFlags(&c->ev_upd, hipEventDisableTiming));
+  if (replace) { rc = scene_switch(c, n, false, s); if (rc != RT_OK) return rc; }
   const size_t nb = (size_t)n * sizeof(float4);
   if (src_dev == c->device) {
     HIP_TRY(hipMemcpyAsync(c->d_verts, dv, 3 * nb, hipMemcpyDeviceToDevice, s));
@@ -629,8 +748,8 @@ static int update_device_one(rt_ctx* c, const void* dv, const void* dn, const vo
     HIP_TRY(hipMemcpyPeerAsync(c->d_colors, c->device, dc, src_dev, nb, s));
   }
   if (c->d_verts_m) {
-    launch_scene_refit(c->d_verts, c->d_normals, c->d_colors, c->d_orig, n, c->d_verts_m, c->d_normals_m, c->d_colors_m,
-                       c->d_tile_box, s);
+    if (replace || (flags & RT_UPDATE_DEVICE_TILES)) { rc = device_tiles(c, sum, s); if (rc != RT_OK) return rc; }
+    refit(c, s);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(c->ev_upd, s));
@@ -639,11 +758,90 @@ static int update_device_one(rt_ctx* c, const void* dv, const void* dn, const vo
   return RT_OK;
 }
 
+// The single-device contexts behind a handle
+static std::vector<rt_ctx*> device_ctxs(rt_ctx* c) { return c->kids.empty() ? std::vector<rt_ctx*>(1, c) : c->kids; }
+
+// Room for a scene of n triangles on every device of the handle, or no change at all
+static int scene_reserve_all(rt_ctx* c, int n, bool device_tiles_wanted) {
+  const std::vector<rt_ctx*> ks = device_ctxs(c);
+  std::vector<SceneGrowth> grown(ks.size());
+  for (size_t i = 0; i < ks.size(); ++i) {
+    const int rc = scene_reserve(ks[i], n, device_tiles_wanted, &grown[i]);
+    if (rc != RT_OK) {
+      const std::string msg = g_last_error;
+      for (size_t j = 0; j < i; ++j) { hipSetDevice(ks[j]->device); free_growth(&grown[j]); }
+      g_last_error = msg;
+      return rc;
+    }
+  }
+  for (size_t i = 0; i < ks.size(); ++i) scene_commit(ks[i], &grown[i]);
+  return RT_OK;
+}
+
+// What a multi-device handle itself reports of the scene
+static void parent_follows(rt_ctx* c) {
+  if (!c->kids.empty()) { c->n = c->kids[0]->n; c->cap = c->kids[0]->cap; c->n_shadow = c->kids[0]->n_shadow; }
+}
+
+static int scene_first(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n) {
+  SceneGrowth g;
+  int rc = scene_reserve(c, n, false, &g);
+  if (rc != RT_OK) return rc;
+  scene_commit(c, &g);
+  SceneSummary sum;
+  sum.n_shadow = count_shadow_casters(c4, n);
+  if (scene_needs(c, n).masks) vertex_box(v4, n, sum.lo, sum.hi);
+  return scene_host_one(c, v4, n4, c4, n, 0, sum, true, true);
+}
+
+static int replace_host_all(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n, uint32_t flags, const SceneSummary& sum) {
+  int rc = scene_reserve_all(c, n, (flags & RT_UPDATE_DEVICE_TILES) != 0);
+  if (rc != RT_OK) return rc;
+  for (rt_ctx* k : device_ctxs(c)) {
+    rc = scene_host_one(k, v4, n4, c4, n, flags, sum, true);
+    if (rc != RT_OK) return rc;
+  }
+  parent_follows(c);
+  return RT_OK;
+}
+
+static int update_host_all(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n, uint32_t flags, const SceneSummary& sum) {
+  for (rt_ctx* k : device_ctxs(c)) {
+    int rc = RT_OK;
+    if ((flags & RT_UPDATE_DEVICE_TILES) && k->d_verts_m) {
+      HIP_TRY(hipSetDevice(k->device));
+      rc = ensure_bytes(&k->tile_scratch, tile_build_scratch_bytes(k->cap));
+    }
+    if (rc == RT_OK) rc = scene_host_one(k, v4, n4, c4, n, flags, sum, false);
+    if (rc != RT_OK) return rc;
+  }
+  return RT_OK;
+}
+
+static const uint32_t kUpdateFlags = RT_UPDATE_REORDER | RT_UPDATE_DEVICE_TILES;
+
+static int check_scene_flags(uint32_t flags, const char* fn) {
+  if (flags & ~kUpdateFlags) { set_error("%s: unknown flags 0x%x", fn, flags); return RT_E_INVALID; }
+  if ((flags & kUpdateFlags) == kUpdateFlags) {
+    set_error("%s: RT_UPDATE_REORDER (host tiles) and RT_UPDATE_DEVICE_TILES exclude each other", fn); return RT_E_INVALID;
+  }
+  return RT_OK;
+}
+
 static int check_update_args(const rt_ctx* c, const void* v, const void* nr, const void* col, int32_t n, uint32_t flags) {
   if (!c) { set_error("NULL context"); return RT_E_INVALID; }
   if (n != c->n) { set_error("rt_update_scene: n = %d, but the context holds %d triangles", n, c->n); return RT_E_INVALID; }
   if (n > 0 && (!v || !nr || !col)) { set_error("scene arrays missing"); return RT_E_INVALID; }
-  if (flags & ~RT_UPDATE_REORDER) { set_error("rt_update_scene: unknown flags 0x%x", flags); return RT_E_INVALID; }
+  return check_scene_flags(flags, "rt_update_scene");
+}
+
+static int check_replace_args(const rt_ctx* c, const void* v, const void* nr, const void* col, int32_t n, uint32_t flags) {
+  if (!c) { set_error("rt_replace_scene: NULL context"); return RT_E_INVALID; }
+  if (!v || !nr || !col) { set_error("rt_replace_scene: scene arrays missing (NULL)"); return RT_E_INVALID; }
+  if (n <= 0) { set_error("rt_replace_scene: n_new = %d, but a scene has at least one triangle", n); return RT_E_INVALID; }
+  const int rc = check_scene_flags(flags, "rt_replace_scene");
+  if (rc != RT_OK) return rc;
+  if (n > 4000000) { set_error("triangle list of %d exceeds the supported maximum of 4000000", n); return RT_E_UNSUPPORTED; }
   return RT_OK;
 }
 
@@ -652,6 +850,54 @@ static float key_to_float(unsigned int k) {   // inverse of rt_scene_update.hip 
   float f;
   memcpy(&f, &u, 4);
   return f;
+}
+
+// First pass of a device entry, on the caller's arrays: check the bound and reduce n_shadow and the box.  Returns once the
+// result has been read back (this synchronises s); the context's buffers are untouched.
+static int device_check(rt_ctx* c, const void* dv, const void* dc, int n, hipStream_t s, SceneSummary* sum) {
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->d_check) HIP_TRY(hipMalloc(&c->d_check, 8 * sizeof(unsigned int)));
+  if (launch_scene_check((const float4*)dv, (const float4*)dc, n, c->d_check, s) != 0) {
+    set_error("scene check launch failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
+  }
+  unsigned int res[8];
+  HIP_TRY(hipMemcpyAsync(res, c->d_check, sizeof res, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (res[0] != 0u) { set_error("%u vertex coordinate(s) not finite or |x| > 2^16", res[0]); return RT_E_INVALID; }
+  sum->n_shadow = (int)res[1];
+  for (int k = 0; k < 3; ++k) { sum->lo[k] = key_to_float(res[2 + k]); sum->hi[k] = key_to_float(res[5 + k]); }
+  return RT_OK;
+}
+
+// Device arrays into every device of the handle: a single device on the caller's stream; several devices each on its own
+// stream after the caller's earlier work, copying from devices[0], and the caller's stream passes only when all have it
+static int scene_device_all(rt_ctx* c, const void* dv, const void* dn, const void* dc, int n, uint32_t flags, hipStream_t s,
+                            const SceneSummary& sum, bool replace) {
+  if (c->kids.empty()) return scene_device_one(c, dv, dn, dc, c->device, n, flags, s, sum, replace);
+  HIP_TRY(hipEventRecord(c->ev_go, s));
+  for (rt_ctx* k : c->kids) {
+    HIP_TRY(hipSetDevice(k->device));
+    HIP_TRY(hipStreamWaitEvent(k->stream, c->ev_go, 0));
+    const int rc = scene_device_one(k, dv, dn, dc, c->device, n, flags, k->stream, sum, replace);
+    if (rc != RT_OK) return rc;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  for (rt_ctx* k : c->kids) HIP_TRY(hipStreamWaitEvent(s, k->ev_upd, 0));
+  return RT_OK;
+}
+
+// The scene of a device entry through host memory (RT_UPDATE_REORDER: the tiles are sorted on the host)
+struct HostScene {
+  std::vector<float> v, nr, col;
+};
+
+static int stage_to_host(const void* dv, const void* dn, const void* dc, int n, hipStream_t s, HostScene* h) {
+  h->v.resize((size_t)n * 12); h->nr.resize((size_t)n * 4); h->col.resize((size_t)n * 4);
+  HIP_TRY(hipMemcpyAsync(h->v.data(), dv, h->v.size() * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(h->nr.data(), dn, h->nr.size() * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(h->col.data(), dc, h->col.size() * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return RT_OK;
 }
 
 extern "C" {
@@ -666,12 +912,7 @@ int rt_update_scene(rt_ctx* c, const float* vertices4, const float* normals4, co
   sum.n_shadow = count_shadow_casters(colors4, n);
   vertex_box(vertices4, n, sum.lo, sum.hi);
   DeviceGuard guard;
-  if (c->kids.empty()) return update_host_one(c, vertices4, normals4, colors4, flags, sum);
-  for (rt_ctx* k : c->kids) {
-    rc = update_host_one(k, vertices4, normals4, colors4, flags, sum);
-    if (rc != RT_OK) return rc;
-  }
-  return RT_OK;
+  return update_host_all(c, vertices4, normals4, colors4, n, flags, sum);
 }
 
 int rt_update_scene_device(rt_ctx* c, const void* d_vertices4, const void* d_normals4, const void* d_colors4, int32_t n,
@@ -682,43 +923,87 @@ int rt_update_scene_device(rt_ctx* c, const void* d_vertices4, const void* d_nor
   DeviceGuard guard;
   const hipStream_t s = (hipStream_t)hip_stream;
   // first pass: check the bound and reduce n_shadow and the box; the live buffers stay untouched until it has passed
-  HIP_TRY(hipSetDevice(c->device));
-  if (!c->d_check) HIP_TRY(hipMalloc(&c->d_check, 8 * sizeof(unsigned int)));
-  if (launch_scene_check((const float4*)d_vertices4, (const float4*)d_colors4, n, c->d_check, s) != 0) {
-    set_error("scene check launch failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
-  }
-  unsigned int res[8];
-  HIP_TRY(hipMemcpyAsync(res, c->d_check, sizeof res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (res[0] != 0u) { set_error("%u vertex coordinate(s) not finite or |x| > 2^16", res[0]); return RT_E_INVALID; }
   SceneSummary sum;
-  sum.n_shadow = (int)res[1];
-  for (int k = 0; k < 3; ++k) { sum.lo[k] = key_to_float(res[2 + k]); sum.hi[k] = key_to_float(res[5 + k]); }
+  rc = device_check(c, d_vertices4, d_colors4, n, s, &sum);
+  if (rc != RT_OK) return rc;
   if (flags & RT_UPDATE_REORDER) {             // the tiles are sorted on the host: stage the scene through it
-    std::vector<float> v((size_t)n * 12), nr((size_t)n * 4), col((size_t)n * 4);
-    HIP_TRY(hipMemcpyAsync(v.data(), d_vertices4, v.size() * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(nr.data(), d_normals4, nr.size() * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(col.data(), d_colors4, col.size() * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (c->kids.empty()) return update_host_one(c, v.data(), nr.data(), col.data(), flags, sum);
-    for (rt_ctx* k : c->kids) {
-      rc = update_host_one(k, v.data(), nr.data(), col.data(), flags, sum);
-      if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
-  }
-  if (c->kids.empty()) return update_device_one(c, d_vertices4, d_normals4, d_colors4, c->device, s, sum);
-  // several devices: every child copies from devices[0] on its own stream after the caller's earlier work, and the
-  // caller's stream passes the update only when every child has its copy
-  HIP_TRY(hipEventRecord(c->ev_go, s));
-  for (rt_ctx* k : c->kids) {
-    HIP_TRY(hipSetDevice(k->device));
-    HIP_TRY(hipStreamWaitEvent(k->stream, c->ev_go, 0));
-    rc = update_device_one(k, d_vertices4, d_normals4, d_colors4, c->device, k->stream, sum);
+    HostScene h;
+    rc = stage_to_host(d_vertices4, d_normals4, d_colors4, n, s, &h);
     if (rc != RT_OK) return rc;
+    return update_host_all(c, h.v.data(), h.nr.data(), h.col.data(), n, flags, sum);
   }
-  HIP_TRY(hipSetDevice(c->device));
-  for (rt_ctx* k : c->kids) HIP_TRY(hipStreamWaitEvent(s, k->ev_upd, 0));
+  if (flags & RT_UPDATE_DEVICE_TILES)
+    for (rt_ctx* k : device_ctxs(c))
+      if (k->d_verts_m) {
+        HIP_TRY(hipSetDevice(k->device));
+        rc = ensure_bytes(&k->tile_scratch, tile_build_scratch_bytes(k->cap));
+        if (rc != RT_OK) return rc;
+      }
+  return scene_device_all(c, d_vertices4, d_normals4, d_colors4, n, flags, s, sum, false);
+}
+
+int rt_replace_scene(rt_ctx* c, const float* vertices4, const float* normals4, const float* colors4, int32_t n_new, uint32_t flags) {
+  int rc = check_replace_args(c, vertices4, normals4, colors4, n_new, flags);
+  if (rc != RT_OK) return rc;
+  rc = validate_vertices(vertices4, n_new);    // once, before any device is touched
+  if (rc != RT_OK) return rc;
+  SceneSummary sum;
+  sum.n_shadow = count_shadow_casters(colors4, n_new);
+  vertex_box(vertices4, n_new, sum.lo, sum.hi);
+  DeviceGuard guard;
+  return replace_host_all(c, vertices4, normals4, colors4, n_new, flags, sum);
+}
+
+int rt_replace_scene_device(rt_ctx* c, const void* d_vertices4, const void* d_normals4, const void* d_colors4, int32_t n_new,
+                            uint32_t flags, void* hip_stream) {
+  int rc = check_replace_args(c, d_vertices4, d_normals4, d_colors4, n_new, flags);
+  if (rc != RT_OK) return rc;
+  DeviceGuard guard;
+  const hipStream_t s = (hipStream_t)hip_stream;
+  SceneSummary sum;
+  rc = device_check(c, d_vertices4, d_colors4, n_new, s, &sum);
+  if (rc != RT_OK) return rc;
+  if (flags & RT_UPDATE_REORDER) {             // host tiles (kd or Morton by the context's tuning): through the host
+    HostScene h;
+    rc = stage_to_host(d_vertices4, d_normals4, d_colors4, n_new, s, &h);
+    if (rc != RT_OK) return rc;
+    return replace_host_all(c, h.v.data(), h.nr.data(), h.col.data(), n_new, flags, sum);
+  }
+  rc = scene_reserve_all(c, n_new, true);
+  if (rc != RT_OK) return rc;
+  rc = scene_device_all(c, d_vertices4, d_normals4, d_colors4, n_new, flags, s, sum, true);
+  parent_follows(c);
+  return rc;
+}
+
+int rt_update_spheres(rt_ctx* c, const rt_sphere* spheres, int32_t num_spheres) {
+  if (!c) { set_error("rt_update_spheres: NULL context"); return RT_E_INVALID; }
+  if (num_spheres < 0 || num_spheres > RT_MAX_SPHERES) { set_error("rt_update_spheres: num_spheres must be in [0,%d]", RT_MAX_SPHERES); return RT_E_INVALID; }
+  if (num_spheres > 0 && !spheres) { set_error("rt_update_spheres: spheres is NULL"); return RT_E_INVALID; }
+  if (validate_spheres(spheres, num_spheres) != RT_OK) return RT_E_INVALID;
+  DeviceGuard guard;
+  auto set_cfg = [&](rt_ctx* k) {
+    k->cfg.num_spheres = num_spheres;
+    memset(k->cfg.spheres, 0, sizeof k->cfg.spheres);
+    for (int i = 0; i < num_spheres; ++i) k->cfg.spheres[i] = spheres[i];
+  };
+  if (!c->kids.empty()) set_cfg(c);
+  for (rt_ctx* k : device_ctxs(c)) {
+    // the table is read by frames, readers and AOV passes: all of them first (a scene update), then a blocking copy
+    const int rc = update_begin(k, k->stream);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(k->stream));
+    set_cfg(k);                                 // fill_params reads FrameParams::sph, nsph and the world grid's growth from it
+    const int rc2 = upload_spheres(k);
+    if (rc2 != RT_OK) return rc2;
+    if (k->d_screen_masks) set_scene_box(k, k->vbox_lo, k->vbox_hi);   // the world grid spans the spheres too
+  }
+  return RT_OK;
+}
+
+int rt_debug_scene_capacity(rt_ctx* c, int64_t* out_triangles) {
+  if (!c || !out_triangles) { set_error("rt_debug_scene_capacity: NULL argument"); return RT_E_INVALID; }
+  *out_triangles = (int64_t)lead_ctx(c)->cap;
   return RT_OK;
 }
 
@@ -1194,13 +1479,15 @@ void rt_destroy(rt_ctx* c) {
   }
   hipFree(c->d_qrecords); hipFree(c->rrec.p);
   hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);
-  hipFree(c->d_argb); hipFree(c->d_rgb); hipFree(c->d_counters); hipFree(c->d_records); hipFree(c->d_jobctr);
-  hipFree(c->d_screen_masks); hipFree(c->d_world_masks); hipFree(c->d_world_occ);
+  hipFree(c->d_argb); hipFree(c->d_rgb); hipFree(c->d_counters); hipFree(c->d_jobctr);
+  // (what a replaced scene may drop and regain is owned by the store; the working pointers are aliases)
+  const SceneStore& o = c->own;
+  hipFree(o.records); hipFree(o.screen_masks); hipFree(o.world_masks); hipFree(o.world_occ);
   if (c->reg_host && c->reg_owner) hipHostUnregister(c->reg_host);
-  hipFree(c->d_heavy[0]); hipFree(c->d_heavy[1]); hipFree(c->d_heavy_flags); hipFree(c->d_timeline);
-  hipFree(c->d_mesh_cost); hipFree(c->d_mesh_order); hipFree(c->d_spheres);
-  hipFree(c->d_verts_m); hipFree(c->d_normals_m); hipFree(c->d_colors_m); hipFree(c->d_orig); hipFree(c->d_tile_box);
-  hipFree(c->d_check);
+  hipFree(o.heavy[0]); hipFree(o.heavy[1]); hipFree(o.heavy_flags); hipFree(c->d_timeline);
+  hipFree(o.mesh_cost); hipFree(o.mesh_order); hipFree(c->d_spheres);
+  hipFree(o.verts_m); hipFree(o.normals_m); hipFree(o.colors_m); hipFree(o.orig); hipFree(o.tile_box);
+  hipFree(c->d_check); hipFree(c->tile_scratch.p);
   delete c;
 }
 

@@ -13,7 +13,7 @@ using namespace uobrt;
 
 // Make sure the buffer holds `bytes`.  Regrowing frees the old buffer first: hipFree synchronises with the device, so
 // whatever still uses the old buffer has finished before it goes.
-static int ensure_bytes(DevBuffer* b, size_t bytes) {
+int uobrt::ensure_bytes(DevBuffer* b, size_t bytes) {
   if (bytes <= b->bytes) return RT_OK;
   hipFree(b->p);
   b->p = nullptr; b->bytes = 0;
@@ -127,7 +127,7 @@ static int enqueue_query(rt_ctx* c, int32_t what, const float* d_rays, const flo
   const bool records = !tiled && generic_needs_records(c->n);
   const int rc = reader_begin(c, &c->query, query_stats_words(), s);
   if (rc != RT_OK) return rc;
-  if (records && !c->d_qrecords && hipMalloc(&c->d_qrecords, (size_t)c->n * kRecordsPerTriangle * sizeof(float4)) != hipSuccess) {
+  if (records && !c->d_qrecords && hipMalloc(&c->d_qrecords, (size_t)c->cap * kRecordsPerTriangle * sizeof(float4)) != hipSuccess) {
     set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
   }
   const float zero3[3] = {0.f, 0.f, 0.f};

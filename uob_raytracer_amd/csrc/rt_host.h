@@ -44,6 +44,9 @@ int mesh_blocks_per_cu();
 int launch_scene_check(const float4* v, const float4* col, int n, unsigned int* out, hipStream_t stream);
 void launch_scene_refit(const float4* v, const float4* nrm, const float4* col, const int* orig, int n, float4* vm, float4* nm,
                         float4* cm, float4* tile_box, hipStream_t stream);
+// rt_tile_build.hip: the tiled order of tiled_order(.., morton = true), on the device
+size_t tile_build_scratch_bytes(int n);
+int launch_tile_build(const float4* v, int n, const float lo[3], const float hi[3], int* orig, void* scratch, hipStream_t stream);
 // rt_ray_query.hip
 int query_stats_words();
 void launch_query(const FrameParams& P, bool tiled, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
@@ -89,6 +92,19 @@ struct DevBuffer {
   char* p = nullptr;
   size_t bytes = 0;
 };
+int ensure_bytes(DevBuffer* b, size_t bytes);
+
+// What a context owns of the buffers that depend on the scene's size or kernel family.  The context's working pointers
+// (rt_ctx::d_verts_m, d_records, d_screen_masks, d_heavy, d_mesh_cost, ...) are these or nullptr: "is there a tiled copy",
+// "are there tile masks" are asked of the working pointers everywhere, so a scene replaced by one of another family
+// (rt_replace_scene) switches them and keeps the memory.  Everything sized by n holds rt_ctx::cap triangles.
+struct SceneStore {
+  float4 *verts_m = nullptr, *normals_m = nullptr, *colors_m = nullptr, *tile_box = nullptr, *records = nullptr;
+  int* orig = nullptr;
+  unsigned long long *screen_masks = nullptr, *world_masks = nullptr;
+  unsigned int* world_occ = nullptr;
+  unsigned int *heavy[2] = {nullptr, nullptr}, *heavy_flags = nullptr, *mesh_cost = nullptr, *mesh_order = nullptr;
+};
 
 // One family of calls beside the frame (rt_calls.hip): ray queries, shade calls, radiance calls, AOV passes.
 // Who waits for whose event is DESIGN.md 4.9; wait_scene_readers and wait_aov below are the only places that say it.
@@ -107,6 +123,9 @@ struct rt_ctx {
   uobrt::Tuning tune;
   int device = 0;
   int n = 0, n_shadow = 0;
+  int cap = 0;                     // triangles the buffers sized by n hold: grows only (rt_replace_scene, rt_debug_scene_capacity)
+  uobrt::SceneStore own;           // the owner of what a replaced scene may drop and regain
+  uobrt::DevBuffer tile_scratch;   // rt_tile_build.hip: keys, indices and the digit table of the device tile build
   int owned_rows = 0;
   float4 *d_verts = nullptr, *d_normals = nullptr, *d_colors = nullptr;
   uint32_t* d_argb = nullptr;      // internal framebuffer (stripe) for rt_render
@@ -138,6 +157,7 @@ struct rt_ctx {
   unsigned int* d_world_occ = nullptr;
   int nwords = 0, scx = 0, scy = 0;
   float box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+  float vbox_lo[3] = {0, 0, 0}, vbox_hi[3] = {0, 0, 0};   // the vertices' part of it (rt_update_spheres adds the new spheres)
   hipStream_t stream = nullptr;
   hipStream_t aux_stream = nullptr;             // mesh kernel: the primary-ray masks are built beside the shadow-ray masks
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;

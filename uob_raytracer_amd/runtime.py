@@ -32,6 +32,7 @@ EXPORTS = (
     "rt_render_aov", "rt_render_aov_device", "rt_debug_aov_stats",
     "rt_shade_points", "rt_shade_points_device", "rt_debug_shade_stats",
     "rt_radiance_rays", "rt_radiance_rays_device", "rt_debug_radiance_stats",
+    "rt_replace_scene", "rt_replace_scene_device", "rt_update_spheres", "rt_debug_scene_capacity",
 )
 
 # rt_debug_trace_stats slots (include/uob_rt.h)
@@ -72,6 +73,10 @@ def lib():
         L.rt_update_scene.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_uint32]
         L.rt_update_scene_device.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint32, vp]
         L.rt_debug_tile_data.argtypes = [vp, C.POINTER(C.c_int32), fp, C.c_int32]
+        L.rt_replace_scene.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_uint32]
+        L.rt_replace_scene_device.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint32, vp]
+        L.rt_update_spheres.argtypes = [vp, C.POINTER(abi.RtSphere), C.c_int32]
+        L.rt_debug_scene_capacity.argtypes = [vp, C.POINTER(C.c_int64)]
         L.rt_render.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(C.c_uint32), fp]
         L.rt_render_device.argtypes = [vp, fp, fp, fp, C.c_float, vp, vp, vp]
         L.rt_count_work.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(abi.RtWork)]
@@ -259,20 +264,81 @@ class RayTracer:
         # the device the context's queries run on (devices[0]; None: the device that was current at rt_init)
         self.device = cfg.devices[0] if cfg.num_devices >= 1 else (cfg.device if cfg.device >= 0 else None)
 
-    def update_scene(self, scene, reorder=False):
+    @staticmethod
+    def _update_flags(reorder, device_tiles):
+        return (abi.RT_UPDATE_REORDER if reorder else 0) | (abi.RT_UPDATE_DEVICE_TILES if device_tiles else 0)
+
+    def update_scene(self, scene, reorder=False, device_tiles=False):
         """Replace the context's triangles (same count) between frames (rt_update_scene): refit the mesh kernel's tiles on
-        the device, or sort them again on the host with reorder=True."""
+        the device, or sort them again on the host with reorder=True, or on the device with device_tiles=True."""
         v, nr, c = scene.packed()
-        _check(lib().rt_update_scene(self._h, _fp(v), _fp(nr), _fp(c), len(scene),
-                                     abi.RT_UPDATE_REORDER if reorder else 0))
+        _check(lib().rt_update_scene(self._h, _fp(v), _fp(nr), _fp(c), len(scene), self._update_flags(reorder, device_tiles)))
         self.scene = scene
         self._keep = (v, nr, c)
 
-    def update_scene_device(self, v_ptr, n_ptr, c_ptr, n, stream=None, reorder=False):
+    def update_scene_device(self, v_ptr, n_ptr, c_ptr, n, stream=None, reorder=False, device_tiles=False):
         """The same from device memory (raw pointers, e.g. torch .data_ptr() of float32 [3n,4] / [n,4] / [n,4]), enqueued
         on `stream` (rt_update_scene_device).  The source buffers must stay unchanged until the stream has passed it."""
         _check(lib().rt_update_scene_device(self._h, C.c_void_p(v_ptr), C.c_void_p(n_ptr), C.c_void_p(c_ptr), n,
-                                            abi.RT_UPDATE_REORDER if reorder else 0, C.c_void_p(stream or 0)))
+                                            self._update_flags(reorder, device_tiles), C.c_void_p(stream or 0)))
+
+    def replace_scene(self, scene, device_tiles=False):
+        """Replace the context's triangles by a scene of any count (rt_replace_scene), blocking.  scene: a Scene, or the three
+        packed arrays (vertices [3n,4], normals [n,4], colours [n,4]) of Scene.packed().  The tiles of a mesh are made on the
+        host as rt_init makes them, or on the device (Morton order) with device_tiles=True."""
+        if isinstance(scene, Scene):
+            v, nr, c = scene.packed()
+        else:
+            v, nr, c = (np.ascontiguousarray(a, np.float32).reshape(-1, 4) for a in scene)
+            if v.shape[0] != 3 * nr.shape[0] or c.shape[0] != nr.shape[0]:
+                raise ValueError("packed arrays must have shapes [3n,4], [n,4], [n,4]")
+            scene = None
+        n = nr.shape[0]
+        _check(lib().rt_replace_scene(self._h, _fp(v), _fp(nr), _fp(c), n, self._update_flags(False, device_tiles)))
+        self.scene = scene
+        self._keep = (v, nr, c)
+        self.n_triangles = n
+
+    def replace_scene_device(self, vertices, normals, colors, stream=None, reorder=False):
+        """The same from torch tensors on the context's device (float32 [3n,4] / [n,4] / [n,4]), enqueued on `stream` (a torch
+        stream or a raw hipStream_t; default: torch's current stream) (rt_replace_scene_device): the tiles are made on the
+        device; reorder=True asks for the host's tiles and stages the scene through the host.  The tensors must stay
+        unchanged until the stream has passed the call."""
+        dev = self._torch_device()
+        if not isinstance(normals, _torch.Tensor) or normals.dim() != 2:
+            raise ValueError("normals must be a torch tensor of shape [n, 4]")
+        n = normals.shape[0]
+        _need("vertices", vertices, _torch.float32, (3 * n, 4), dev)
+        _need("normals", normals, _torch.float32, (n, 4), dev)
+        _need("colors", colors, _torch.float32, (n, 4), dev)
+        raw = self._raw_stream(stream, dev)
+        _check(lib().rt_replace_scene_device(self._h, C.c_void_p(vertices.data_ptr()), C.c_void_p(normals.data_ptr()),
+                                             C.c_void_p(colors.data_ptr()), n, self._update_flags(reorder, False),
+                                             C.c_void_p(raw)))
+        self.scene = None
+        self.n_triangles = n
+
+    def update_spheres(self, spheres):
+        """Replace the sphere table (rt_update_spheres): a list of up to RT_MAX_SPHERES (centre, radius_sq, colour rgba)
+        tuples, as abi.make_config takes them.  self.cfg follows."""
+        spheres = tuple(spheres or ())
+        if len(spheres) > abi.RT_MAX_SPHERES:
+            raise ValueError("at most %d spheres" % abi.RT_MAX_SPHERES)
+        tab = (abi.RtSphere * abi.RT_MAX_SPHERES)()
+        for i, (ctr, r2, col) in enumerate(spheres):
+            tab[i].center[:] = ctr
+            tab[i].radius_sq = r2
+            tab[i].color[:] = col
+        _check(lib().rt_update_spheres(self._h, tab, len(spheres)))
+        self.cfg.num_spheres = len(spheres)
+        for i in range(abi.RT_MAX_SPHERES):
+            self.cfg.spheres[i] = tab[i]
+
+    def scene_capacity(self):
+        """Triangles the context's buffers can hold without allocating (rt_debug_scene_capacity)."""
+        out = C.c_int64()
+        _check(lib().rt_debug_scene_capacity(self._h, C.byref(out)))
+        return int(out.value)
 
     def tile_data(self):
         """Mesh kernel: (orig int32 [n], tiles float32 [ntiles, 12]) — the tiled order and per-tile data (rt_debug_tile_data)."""
