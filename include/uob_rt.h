@@ -169,6 +169,43 @@ int rt_update_spheres(rt_ctx* ctx, const rt_sphere* spheres, int32_t num_spheres
 /* Diagnostic: triangles the context's buffers can hold without allocating.                                          */
 int rt_debug_scene_capacity(rt_ctx* ctx, int64_t* out_triangles);
 
+/* ---- rigid objects: pose triangle ranges on the device from a rest pose (rt_scene_pose.hip) ----------
+ * An OBJECT is a range [first, first + count) of the context's triangles, in the caller's original order.  A POSE is one
+ * xform12 per object: 3 rows x (m_r0, m_r1, m_r2, t_r) — the layout of rot[12] with the translation in the pad column.
+ * Posing the rest scene R with the poses X gives the scene P(R, X), rt_scene_transform's arithmetic (below):
+ *   every vertex of an object's triangles becomes v'_r = ((v.x*m_r0 + v.y*m_r1) + v.z*m_r2) + t_r, FP32 without contraction;
+ *   the normal of each such triangle is recomputed as rt_triangle_compute_normal does, always (also for an identity);
+ *   triangles in no object, and all colours, are the rest scene's, bit for bit.
+ * After RT_OK every later operation of the context — frames, AOV passes, ray queries, shade and radiance calls, the counting
+ * passes — gives exactly the bits that rt_update_scene(ctx, pack(P(R, X)), flags) would have given.  A pose always starts
+ * from R, never from the previous pose: nothing drifts.
+ *
+ * rt_set_objects snapshots the context's current scene (vertices, normals) as the rest pose R, in device memory, and records
+ * the ranges: non-empty, inside [0, n), pairwise disjoint; nobj in 0 .. 65535.  nobj == 0 drops the table and frees the rest
+ * pose.  Anything else is RT_E_INVALID, and the previous table survives.  Waits like rt_update_scene; blocking.  A context
+ * that never calls it allocates nothing for it.  (A multi-device context keeps the rest pose on devices[0], which poses.)
+ * rt_update_scene* and rt_replace_scene* change the scene behind the rest pose, so they drop the table; rt_update_spheres
+ * does not touch it.  A pose call without a table is RT_E_INVALID.                                                          */
+int rt_set_objects(rt_ctx* ctx, const int32_t* first, const int32_t* count, int32_t nobj);
+
+/* Pose the objects: xforms12 = float32 [nobj][12] in host memory; nobj * 48 bytes are uploaded and nothing else.  The posed
+ * scene is written on the device and goes through rt_update_scene_device's path: flags 0 refits into the existing tiles,
+ * RT_UPDATE_DEVICE_TILES sorts the tiles again on the device, RT_UPDATE_REORDER makes host tiles and stages the posed scene
+ * through the host.  Validation is rt_update_scene's, applied to the posed scene (finite, |x| <= 2^16): on any failure — a
+ * NaN in a matrix, an object pushed out of range — the context keeps its previous scene, whole, and its rest pose.
+ * Blocking.                                                                                                              */
+int rt_pose_objects(rt_ctx* ctx, const float* xforms12, uint32_t flags);
+
+/* Same, with the matrices in device memory on the context's device (devices[0]), e.g. the output of a simulation step;
+ * stream-ordered exactly like rt_update_scene_device: the call returns once the first pass (bound, n_shadow, box) has been
+ * read back, later operations of the context wait on the device, d_xforms12 may change once hip_stream has passed the call,
+ * and nothing of the scene goes through host memory (unless RT_UPDATE_REORDER asks for it).  A multi-device context poses
+ * on devices[0]; the other devices receive the posed scene by peer copy.                                                 */
+int rt_pose_objects_device(rt_ctx* ctx, const void* d_xforms12, uint32_t flags, void* hip_stream);
+
+/* Diagnostic: objects in the context's table (0: none).                                                              */
+int rt_debug_object_count(rt_ctx* ctx, int32_t* out);
+
 /* Render one frame and read it back: rot = 3 rows x (x,y,z,pad) exactly as rot_matrix[12] at
  * skeleton.cpp:149-151; cam/light = first 12 bytes of camera_position / light_position (:162,:164);
  * focal = focal_length (:166), in units of AA sub-pixels along x.  out_argb receives
@@ -463,6 +500,11 @@ int rt_scene_load_obj_ex(const char* path, const float color[4], float scale, co
                          rt_triangle* out, int32_t cap);
 /* ComputeNormal (TestModelH.h:26-35): normal = normalize(cross(v2-v0, v1-v0)), w = 1.               */
 void rt_triangle_compute_normal(rt_triangle* t);
+/* The pose arithmetic on the host (CPU only): the triangles [first, first + count) of tris[0 .. n) get every vertex replaced
+ * by v'_r = ((v.x*m_r0 + v.y*m_r1) + v.z*m_r2) + t_r with xform12 = 3 rows x (m_r0, m_r1, m_r2, t_r), FP32 without
+ * contraction (w stays), and their normals recomputed by rt_triangle_compute_normal.  A range that is not inside [0, n)
+ * changes nothing.                                                                                                   */
+void rt_scene_transform(rt_triangle* tris, int32_t n, int32_t first, int32_t count, const float xform12[12]);
 /* AoS -> the three packed float4 arrays (skeleton.cpp:474-484).                                      */
 void rt_scene_pack(const rt_triangle* tris, int32_t n, float* vertices4, float* normals4, float* colors4);
 /* Rotation matrix from yaw/pitch exactly as skeleton.cpp:149-151 (float cos/sin).                    */

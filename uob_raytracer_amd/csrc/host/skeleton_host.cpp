@@ -13,6 +13,9 @@
 //                 [--obj mesh.obj]            append load_obj(mesh.obj) to the box, as skeleton.cpp:102-103 does
 //                 [--move DX,DY,DZ]           with --obj: update() slides the mesh by (DX,DY,DZ) every frame (float32
 //                                             adds to its vertices; normals do not change), rt_update_scene before the frame
+//                 [--spin RAD]                with --obj: the mesh is one rigid object (rt_set_objects); frame f = 1, 2, ... poses
+//                                             it by a rotation of f * RAD about the vertical axis through the centre of
+//                                             its rest bounding box (rt_pose_objects: 48 bytes per frame cross the bus)
 //                 [--bounce-sphere]           sphere 0 follows a parabola, frame by frame (rt_update_spheres)
 //                 [--gpus N | --devices a,b,..]  render every frame on several GPUs inside the one context
 //                 [--copy-back]                  device buffer + blocking read-back instead of rt_register_output
@@ -47,6 +50,9 @@ static size_t g_key_at = 0;
 static size_t g_obj_first = 0;                                 // --move: the loaded mesh is triangles[g_obj_first..]
 static bool g_move = false;
 static float g_move_by[3] = {0.0f, 0.0f, 0.0f};
+static bool g_spin = false;                                    // --spin: the loaded mesh turns as one rigid object
+static float g_spin_rad = 0.0f;
+static float g_spin_centre[3] = {0.0f, 0.0f, 0.0f};            // centre of the rest mesh's bounding box
 static bool g_bounce = false;                                  // --bounce-sphere: sphere 0 follows a parabola, frame by frame
 static rt_sphere g_spheres[RT_MAX_SPHERES];
 static int g_num_spheres = 0;
@@ -69,6 +75,28 @@ void update_scene() {
   vector<float> v(12 * (size_t)n), nr(4 * (size_t)n), col(4 * (size_t)n);
   rt_scene_pack(triangles.data(), n, v.data(), nr.data(), col.data());
   if (rt_update_scene(g_rt, v.data(), nr.data(), col.data(), n, 0) != RT_OK) die("rt_update_scene");
+}
+
+// The mesh becomes the context's one object; its rest pose is the scene as uploaded
+void spin_begin() {
+  float lo[3], hi[3];
+  for (int k = 0; k < 3; ++k) lo[k] = hi[k] = triangles[g_obj_first].v0[k];
+  for (size_t t = g_obj_first; t < triangles.size(); ++t)
+    for (const float* p : {triangles[t].v0, triangles[t].v1, triangles[t].v2})
+      for (int k = 0; k < 3; ++k) { if (p[k] < lo[k]) lo[k] = p[k]; if (p[k] > hi[k]) hi[k] = p[k]; }
+  for (int k = 0; k < 3; ++k) g_spin_centre[k] = (lo[k] + hi[k]) * 0.5f;
+  const int32_t first = (int32_t)g_obj_first, count = (int32_t)(triangles.size() - g_obj_first);
+  if (rt_set_objects(g_rt, &first, &count, 1) != RT_OK) die("rt_set_objects");
+}
+
+// The mesh of frame f = 1, 2, ...: the rest pose turned by f * RAD about the vertical axis through the centre c,
+// v' = M v + (c - M c), M as rt_rotation_matrix builds it (float cos / sin); to the device before the frame
+void spin_mesh(int f) {
+  float x[12];
+  rt_rotation_matrix((float)f * g_spin_rad, 0.0f, x);
+  const float* c = g_spin_centre;
+  for (int r = 0; r < 3; ++r) x[4 * r + 3] = c[r] - ((c[0] * x[4 * r] + c[1] * x[4 * r + 1]) + c[2] * x[4 * r + 2]);
+  if (rt_pose_objects(g_rt, x, 0) != RT_OK) die("rt_pose_objects");
 }
 
 // Sphere 0 of frame f = 1, 2, ... on a fixed parabola (one bounce in eight frames), to the device before the frame
@@ -146,6 +174,7 @@ int main(int argc, char* argv[]) {
       if (sscanf(argv[++i], "%f,%f,%f", &g_move_by[0], &g_move_by[1], &g_move_by[2]) != 3) { fprintf(stderr, "--move DX,DY,DZ\n"); return 2; }
       g_move = true;
     }
+    else if (a == "--spin" && i + 1 < argc) { g_spin_rad = (float)atof(argv[++i]); g_spin = true; }
     else if (a == "--bounce-sphere") g_bounce = true;
     else if (a == "--copy-back") direct_out = false;           // render into device memory + blocking copy, as the reference reads back
     else if (a == "--gpus" && i + 1 < argc) {
@@ -168,6 +197,8 @@ int main(int argc, char* argv[]) {
   triangles.resize(n);
   g_obj_first = triangles.size();
   if (g_move && !obj) { fprintf(stderr, "--move needs --obj\n"); return 2; }
+  if (g_spin && !obj) { fprintf(stderr, "--spin needs --obj\n"); return 2; }
+  if (g_spin && g_move) { fprintf(stderr, "--spin and --move exclude each other (--move replaces the scene behind the rest pose)\n"); return 2; }
   g_num_spheres = cfg.num_spheres;
   for (int i = 0; i < RT_MAX_SPHERES; ++i) g_spheres[i] = cfg.spheres[i];
   if (obj) {                                                                   // load_obj + insert, :102-103
@@ -178,6 +209,7 @@ int main(int argc, char* argv[]) {
   }
   printf("Triangles Length size %lu\n", triangles.size());                    // :104
   opencl_initialise(cfg);                                                      // :106
+  if (g_spin && triangles.size() > g_obj_first) spin_begin();
   // the device(s) write finished pixels straight into screen->buffer (no read-back after the kernel)
   if (direct_out &&
       rt_register_output(g_rt, screen->buffer, (size_t)SCREEN_WIDTH * SCREEN_HEIGHT * sizeof(uint32_t)) != RT_OK)
@@ -188,6 +220,7 @@ int main(int argc, char* argv[]) {
   for (int f = 0; f < frames && !quit; ++f) {                                  // :117-138
     update();
     if (g_move) update_scene();
+    if (g_spin && triangles.size() > g_obj_first) spin_mesh(f + 1);
     if (g_bounce) bounce_sphere(f + 1);
     auto start = high_resolution_clock::now();
     offload_rendering(screen);

@@ -730,7 +730,8 @@ static int scene_host_one(rt_ctx* c, const float* v4, const float* n4, const flo
   return RT_OK;
 }
 
-// Device arrays on device src_dev (validated) into one single-device context, enqueued on `s` (a stream of c->device)
+// Device arrays on device src_dev (validated) into one single-device context, enqueued on `s` (a stream of c->device);
+// dc == nullptr: the colours stay (a pose)
 static int scene_device_one(rt_ctx* c, const void* dv, const void* dn, const void* dc, int src_dev, int n, uint32_t flags,
                             hipStream_t s, const SceneSummary& sum, bool replace) {
   int rc = update_begin(c, s);
@@ -741,11 +742,11 @@ static int scene_device_one(rt_ctx* c, const void* dv, const void* dn, const voi
   if (src_dev == c->device) {
     HIP_TRY(hipMemcpyAsync(c->d_verts, dv, 3 * nb, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->d_normals, dn, nb, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->d_colors, dc, nb, hipMemcpyDeviceToDevice, s));
+    if (dc) HIP_TRY(hipMemcpyAsync(c->d_colors, dc, nb, hipMemcpyDeviceToDevice, s));
   } else {                                   // the other devices of a multi-device context: by peer copy, as the bands
     HIP_TRY(hipMemcpyPeerAsync(c->d_verts, c->device, dv, src_dev, 3 * nb, s));
     HIP_TRY(hipMemcpyPeerAsync(c->d_normals, c->device, dn, src_dev, nb, s));
-    HIP_TRY(hipMemcpyPeerAsync(c->d_colors, c->device, dc, src_dev, nb, s));
+    if (dc) HIP_TRY(hipMemcpyPeerAsync(c->d_colors, c->device, dc, src_dev, nb, s));
   }
   if (c->d_verts_m) {
     if (replace || (flags & RT_UPDATE_DEVICE_TILES)) { rc = device_tiles(c, sum, s); if (rc != RT_OK) return rc; }
@@ -900,7 +901,145 @@ static int stage_to_host(const void* dv, const void* dn, const void* dc, int n, 
   return RT_OK;
 }
 
+// A same-count scene in device memory on the handle's device that has passed device_check (the caller's arrays, or the
+// staging scene a pose has written; dc == nullptr: the colours stay) into every device of the handle, behind stream s
+static int update_from_device(rt_ctx* c, const void* dv, const void* dn, const void* dc, int n, uint32_t flags, hipStream_t s,
+                              const SceneSummary& sum) {
+  if (flags & RT_UPDATE_REORDER) {             // the tiles are sorted on the host: stage the scene through it
+    HostScene h;
+    const int rc = stage_to_host(dv, dn, dc ? dc : lead_ctx(c)->d_colors, n, s, &h);
+    if (rc != RT_OK) return rc;
+    return update_host_all(c, h.v.data(), h.nr.data(), h.col.data(), n, flags, sum);
+  }
+  if (flags & RT_UPDATE_DEVICE_TILES)
+    for (rt_ctx* k : device_ctxs(c))
+      if (k->d_verts_m) {
+        HIP_TRY(hipSetDevice(k->device));
+        const int rc = ensure_bytes(&k->tile_scratch, tile_build_scratch_bytes(k->cap));
+        if (rc != RT_OK) return rc;
+      }
+  return scene_device_all(c, dv, dn, dc, n, flags, s, sum, false);
+}
+
+// ---- rigid objects (rt_set_objects / rt_pose_objects*): DESIGN.md 4.2b -------------------------------------------------
+// The table and the rest pose live on the context that poses (lead_ctx).  Nothing here runs for a context without a table.
+static void drop_objects(rt_ctx* c) {
+  rt_ctx* L = lead_ctx(c);
+  L->nobj = 0;
+  if (!L->d_rest_verts && !L->d_rest_normals && !L->d_object_of) return;
+  DeviceGuard guard;
+  hipSetDevice(L->device);
+  hipFree(L->d_rest_verts); hipFree(L->d_rest_normals); hipFree(L->d_object_of);   // (hipFree waits for a pose still reading them)
+  L->d_rest_verts = L->d_rest_normals = nullptr; L->d_object_of = nullptr;
+}
+
+static int check_pose_args(rt_ctx* c, const void* xforms, uint32_t flags, const char* fn) {
+  if (!c) { set_error("%s: NULL context", fn); return RT_E_INVALID; }
+  if (!xforms) { set_error("%s: the matrices are missing (NULL)", fn); return RT_E_INVALID; }
+  const int rc = check_scene_flags(flags, fn);
+  if (rc != RT_OK) return rc;
+  if (lead_ctx(c)->nobj == 0) {
+    set_error("%s: the context has no object table (rt_set_objects first; a scene update or replace drops it)", fn);
+    return RT_E_INVALID;
+  }
+  return RT_OK;
+}
+
+// The rest pose posed by the matrices at d_xforms12 (device memory of the lead device) into the staging scene, on s, and
+// from there into the context as a device update: the check runs on the staging scene, before anything live is written
+static int pose_from_device(rt_ctx* c, const void* d_xforms12, uint32_t flags, hipStream_t s) {
+  rt_ctx* L = lead_ctx(c);
+  HIP_TRY(hipSetDevice(L->device));
+  const size_t nb = (size_t)L->cap * sizeof(float4);
+  int rc = ensure_bytes(&L->pose_verts, 3 * nb);
+  if (rc == RT_OK) rc = ensure_bytes(&L->pose_normals, nb);
+  if (rc != RT_OK) return rc;
+  // the staging scene may still be the source of the previous pose's copies, on whichever streams they run
+  for (rt_ctx* k : device_ctxs(c)) HIP_TRY(wait_scene(k, s));
+  launch_pose(L->d_rest_verts, L->d_rest_normals, L->d_object_of, (const float*)d_xforms12, L->n, (float4*)L->pose_verts.p,
+              (float4*)L->pose_normals.p, s);
+  HIP_TRY(hipGetLastError());
+  SceneSummary sum;
+  rc = device_check(c, L->pose_verts.p, L->d_colors, L->n, s, &sum);
+  if (rc != RT_OK) return rc;
+  return update_from_device(c, L->pose_verts.p, L->pose_normals.p, nullptr, L->n, flags, s, sum);
+}
+
 extern "C" {
+
+int rt_set_objects(rt_ctx* c, const int32_t* first, const int32_t* count, int32_t nobj) {
+  if (!c) { set_error("rt_set_objects: NULL context"); return RT_E_INVALID; }
+  if (nobj < 0 || nobj > (int32_t)kPoseStatic) { set_error("rt_set_objects: nobj = %d outside [0, 65535]", nobj); return RT_E_INVALID; }
+  if (nobj > 0 && (!first || !count)) { set_error("rt_set_objects: first / count is NULL"); return RT_E_INVALID; }
+  if (nobj == 0) { drop_objects(c); return RT_OK; }
+  rt_ctx* L = lead_ctx(c);
+  const int n = L->n;
+  std::vector<unsigned short> object_of((size_t)n, (unsigned short)kPoseStatic);
+  for (int k = 0; k < nobj; ++k) {
+    const int f = first[k], cnt = count[k];
+    if (cnt < 1 || f < 0 || f >= n || cnt > n - f) {
+      set_error("rt_set_objects: object %d = [%d, %d + %d) is empty or not inside the context's %d triangles", k, f, f, cnt, n);
+      return RT_E_INVALID;
+    }
+    for (int i = f; i < f + cnt; ++i) {
+      if (object_of[(size_t)i] != kPoseStatic) {
+        set_error("rt_set_objects: objects %d and %d overlap at triangle %d", (int)object_of[(size_t)i], k, i); return RT_E_INVALID;
+      }
+      object_of[(size_t)i] = (unsigned short)k;
+    }
+  }
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(L->device));
+  const size_t nb = (size_t)n * sizeof(float4);
+  if (!L->d_rest_verts &&      // (a table in force has buffers of this n: whatever changes n drops the table)
+      (hipMalloc(&L->d_rest_verts, 3 * nb) != hipSuccess || hipMalloc(&L->d_rest_normals, nb) != hipSuccess ||
+       hipMalloc(&L->d_object_of, (size_t)n * sizeof(unsigned short)) != hipSuccess)) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
+    drop_objects(c);
+    return RT_E_NOMEM;
+  }
+  // the snapshot waits for whatever still writes the scene, and a pose still reading the old rest pose (an update's event)
+  int rc = update_begin(L, L->stream);
+  if (rc == RT_OK &&
+      (hipMemcpyAsync(L->d_rest_verts, L->d_verts, 3 * nb, hipMemcpyDeviceToDevice, L->stream) != hipSuccess ||
+       hipMemcpyAsync(L->d_rest_normals, L->d_normals, nb, hipMemcpyDeviceToDevice, L->stream) != hipSuccess ||
+       hipMemcpyAsync(L->d_object_of, object_of.data(), (size_t)n * sizeof(unsigned short), hipMemcpyHostToDevice, L->stream) != hipSuccess ||
+       hipStreamSynchronize(L->stream) != hipSuccess)) {
+    set_error("rt_set_objects: snapshot failed: %s", hipGetErrorString(hipGetLastError())); rc = RT_E_DEVICE;
+  }
+  if (rc != RT_OK) { const std::string msg = g_last_error; drop_objects(c); g_last_error = msg; return rc; }
+  L->nobj = nobj;
+  return RT_OK;
+}
+
+int rt_pose_objects(rt_ctx* c, const float* xforms12, uint32_t flags) {
+  int rc = check_pose_args(c, xforms12, flags, "rt_pose_objects");
+  if (rc != RT_OK) return rc;
+  rt_ctx* L = lead_ctx(c);
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(L->device));
+  const size_t bytes = (size_t)L->nobj * 12 * sizeof(float);
+  rc = ensure_bytes(&L->pose_xforms, bytes);     // (only this blocking entry uses the buffer: nothing can still be reading it)
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(L->pose_xforms.p, xforms12, bytes, hipMemcpyHostToDevice, c->stream));
+  rc = pose_from_device(c, L->pose_xforms.p, flags, c->stream);
+  if (rc != RT_OK) { const std::string msg = g_last_error; hipStreamSynchronize(c->stream); (void)hipGetLastError(); g_last_error = msg; return rc; }
+  HIP_TRY(hipStreamSynchronize(c->stream));      // (the stream of a multi-device handle has waited for every device)
+  return RT_OK;
+}
+
+int rt_pose_objects_device(rt_ctx* c, const void* d_xforms12, uint32_t flags, void* hip_stream) {
+  const int rc = check_pose_args(c, d_xforms12, flags, "rt_pose_objects_device");
+  if (rc != RT_OK) return rc;
+  DeviceGuard guard;
+  return pose_from_device(c, d_xforms12, flags, (hipStream_t)hip_stream);
+}
+
+int rt_debug_object_count(rt_ctx* c, int32_t* out) {
+  if (!c || !out) { set_error("rt_debug_object_count: NULL argument"); return RT_E_INVALID; }
+  *out = lead_ctx(c)->nobj;
+  return RT_OK;
+}
 
 int rt_update_scene(rt_ctx* c, const float* vertices4, const float* normals4, const float* colors4, int32_t n, uint32_t flags) {
   int rc = check_update_args(c, vertices4, normals4, colors4, n, flags);
@@ -912,6 +1051,7 @@ int rt_update_scene(rt_ctx* c, const float* vertices4, const float* normals4, co
   sum.n_shadow = count_shadow_casters(colors4, n);
   vertex_box(vertices4, n, sum.lo, sum.hi);
   DeviceGuard guard;
+  drop_objects(c);                             // the scene behind the rest pose changes
   return update_host_all(c, vertices4, normals4, colors4, n, flags, sum);
 }
 
@@ -926,20 +1066,8 @@ int rt_update_scene_device(rt_ctx* c, const void* d_vertices4, const void* d_nor
   SceneSummary sum;
   rc = device_check(c, d_vertices4, d_colors4, n, s, &sum);
   if (rc != RT_OK) return rc;
-  if (flags & RT_UPDATE_REORDER) {             // the tiles are sorted on the host: stage the scene through it
-    HostScene h;
-    rc = stage_to_host(d_vertices4, d_normals4, d_colors4, n, s, &h);
-    if (rc != RT_OK) return rc;
-    return update_host_all(c, h.v.data(), h.nr.data(), h.col.data(), n, flags, sum);
-  }
-  if (flags & RT_UPDATE_DEVICE_TILES)
-    for (rt_ctx* k : device_ctxs(c))
-      if (k->d_verts_m) {
-        HIP_TRY(hipSetDevice(k->device));
-        rc = ensure_bytes(&k->tile_scratch, tile_build_scratch_bytes(k->cap));
-        if (rc != RT_OK) return rc;
-      }
-  return scene_device_all(c, d_vertices4, d_normals4, d_colors4, n, flags, s, sum, false);
+  drop_objects(c);
+  return update_from_device(c, d_vertices4, d_normals4, d_colors4, n, flags, s, sum);
 }
 
 int rt_replace_scene(rt_ctx* c, const float* vertices4, const float* normals4, const float* colors4, int32_t n_new, uint32_t flags) {
@@ -951,6 +1079,7 @@ int rt_replace_scene(rt_ctx* c, const float* vertices4, const float* normals4, c
   sum.n_shadow = count_shadow_casters(colors4, n_new);
   vertex_box(vertices4, n_new, sum.lo, sum.hi);
   DeviceGuard guard;
+  drop_objects(c);
   return replace_host_all(c, vertices4, normals4, colors4, n_new, flags, sum);
 }
 
@@ -963,6 +1092,7 @@ int rt_replace_scene_device(rt_ctx* c, const void* d_vertices4, const void* d_no
   SceneSummary sum;
   rc = device_check(c, d_vertices4, d_colors4, n_new, s, &sum);
   if (rc != RT_OK) return rc;
+  drop_objects(c);
   if (flags & RT_UPDATE_REORDER) {             // host tiles (kd or Morton by the context's tuning): through the host
     HostScene h;
     rc = stage_to_host(d_vertices4, d_normals4, d_colors4, n_new, s, &h);
@@ -1488,6 +1618,8 @@ void rt_destroy(rt_ctx* c) {
   hipFree(o.mesh_cost); hipFree(o.mesh_order); hipFree(c->d_spheres);
   hipFree(o.verts_m); hipFree(o.normals_m); hipFree(o.colors_m); hipFree(o.orig); hipFree(o.tile_box);
   hipFree(c->d_check); hipFree(c->tile_scratch.p);
+  hipFree(c->d_rest_verts); hipFree(c->d_rest_normals); hipFree(c->d_object_of);
+  hipFree(c->pose_verts.p); hipFree(c->pose_normals.p); hipFree(c->pose_xforms.p);
   delete c;
 }
 

@@ -44,6 +44,10 @@ int mesh_blocks_per_cu();
 int launch_scene_check(const float4* v, const float4* col, int n, unsigned int* out, hipStream_t stream);
 void launch_scene_refit(const float4* v, const float4* nrm, const float4* col, const int* orig, int n, float4* vm, float4* nm,
                         float4* cm, float4* tile_box, hipStream_t stream);
+// rt_scene_pose.hip: the rest pose and one xform12 per object into a posed scene (vertices, normals)
+constexpr unsigned int kPoseStatic = 0xffffu;   // object_of[i] of a triangle in no object (so at most 65535 objects)
+void launch_pose(const float4* rest_v, const float4* rest_n, const unsigned short* object_of, const float* d_xforms12, int n,
+                 float4* out_v, float4* out_n, hipStream_t stream);
 // rt_tile_build.hip: the tiled order of tiled_order(.., morton = true), on the device
 size_t tile_build_scratch_bytes(int n);
 int launch_tile_build(const float4* v, int n, const float lo[3], const float hi[3], int* orig, void* scratch, hipStream_t stream);
@@ -173,6 +177,13 @@ struct rt_ctx {
   hipEvent_t ev_upd = nullptr;
   bool upd_pending = false;
   unsigned int* d_check = nullptr;  // rt_scene_check's result block (rt_scene_update.hip)
+  // Rigid objects (rt_set_objects / rt_pose_objects*, rt_scene_pose.hip), on the context that poses (lead_ctx): the rest pose
+  // and the per-triangle object table exist while nobj > 0; the staging scene (sized by cap) and the host entry's matrices
+  // are kept once made
+  int nobj = 0;
+  float4 *d_rest_verts = nullptr, *d_rest_normals = nullptr;
+  unsigned short* d_object_of = nullptr;
+  uobrt::DevBuffer pose_verts, pose_normals, pose_xforms;
   // The scene's readers — ray queries (rt_ray_query.hip), shade calls (rt_shade.hip), radiance calls (rt_radiance.hip): they
   // read only the scene, so frames need not wait for them; later readers (they share the counters and staging of their
   // family) and scene updates do

@@ -85,6 +85,20 @@ void rt_triangle_compute_normal(rt_triangle* t) {
   t->normal[0] = nx * inv; t->normal[1] = ny * inv; t->normal[2] = nz * inv; t->normal[3] = 1.0f;
 }
 
+// The pose arithmetic (include/uob_rt.h "rigid objects"): what rt_scene_pose.hip computes on the device, term by term
+void rt_scene_transform(rt_triangle* tris, int32_t n, int32_t first, int32_t count, const float xform12[12]) {
+  if (!tris || !xform12 || first < 0 || count < 0 || first > n || count > n - first) return;
+  const float* m = xform12;
+  for (int i = first; i < first + count; ++i) {
+    rt_triangle& t = tris[i];
+    for (float* v : {t.v0, t.v1, t.v2}) {
+      const float x = v[0], y = v[1], z = v[2];
+      for (int r = 0; r < 3; ++r) v[r] = ((x * m[4 * r] + y * m[4 * r + 1]) + z * m[4 * r + 2]) + m[4 * r + 3];
+    }
+    rt_triangle_compute_normal(&t);
+  }
+}
+
 int rt_scene_cornell_box(rt_triangle* out, int32_t cap) {
   if (!out || cap < 0) { uobrt::set_error("rt_scene_cornell_box: bad arguments"); return RT_E_INVALID; }
   const float L = 555;   // side of the Cornell Box, TestModelH.h:69

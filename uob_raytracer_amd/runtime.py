@@ -33,6 +33,7 @@ EXPORTS = (
     "rt_shade_points", "rt_shade_points_device", "rt_debug_shade_stats",
     "rt_radiance_rays", "rt_radiance_rays_device", "rt_debug_radiance_stats",
     "rt_replace_scene", "rt_replace_scene_device", "rt_update_spheres", "rt_debug_scene_capacity",
+    "rt_scene_transform", "rt_set_objects", "rt_pose_objects", "rt_pose_objects_device", "rt_debug_object_count",
 )
 
 # rt_debug_trace_stats slots (include/uob_rt.h)
@@ -77,6 +78,12 @@ def lib():
         L.rt_replace_scene_device.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint32, vp]
         L.rt_update_spheres.argtypes = [vp, C.POINTER(abi.RtSphere), C.c_int32]
         L.rt_debug_scene_capacity.argtypes = [vp, C.POINTER(C.c_int64)]
+        L.rt_scene_transform.argtypes = [C.POINTER(abi.RtTriangle), C.c_int32, C.c_int32, C.c_int32, fp]
+        L.rt_scene_transform.restype = None
+        L.rt_set_objects.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32]
+        L.rt_pose_objects.argtypes = [vp, fp, C.c_uint32]
+        L.rt_pose_objects_device.argtypes = [vp, vp, C.c_uint32, vp]
+        L.rt_debug_object_count.argtypes = [vp, C.POINTER(C.c_int32)]
         L.rt_render.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(C.c_uint32), fp]
         L.rt_render_device.argtypes = [vp, fp, fp, fp, C.c_float, vp, vp, vp]
         L.rt_count_work.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(abi.RtWork)]
@@ -187,6 +194,22 @@ def rotation_matrix(yaw, pitch):
     return rot
 
 
+def _object_ranges(ranges, n):
+    """The objects of set_objects / Scene.posed as a list of (first, count): each entry a (first, count) pair or a slice of
+    step 1 over n triangles."""
+    out = []
+    for r in ranges:
+        if isinstance(r, slice):
+            first, stop, step = r.indices(n)
+            if step != 1:
+                raise ValueError("an object is a contiguous range of triangles (slice step 1)")
+            out.append((first, stop - first))
+        else:
+            first, count = r
+            out.append((int(first), int(count)))
+    return out
+
+
 class Scene:
     """Triangle list in the reference's AoS format (TestModelH.h:11-38): array [n,5,4] = v0,v1,v2,normal,color."""
 
@@ -225,15 +248,26 @@ class Scene:
     def transformed(self, indices, matrix, offset=(0.0, 0.0, 0.0)):
         """A new Scene whose triangles `indices` have every vertex v replaced by matrix @ v + offset (float32, the products
         summed left to right) and their normals recomputed by rt_triangle_compute_normal (ComputeNormal, TestModelH.h:26)."""
-        m = np.asarray(matrix, np.float32).reshape(3, 3)
-        o = np.asarray(offset, np.float32).reshape(3)
+        xf = np.zeros((3, 4), np.float32)
+        xf[:, :3] = np.asarray(matrix, np.float32).reshape(3, 3)
+        xf[:, 3] = np.asarray(offset, np.float32).reshape(3)
         aos = self.aos.copy()
         idx = np.arange(len(self))[indices] if not isinstance(indices, (list, tuple)) else np.asarray(indices, np.int64)
-        v = aos[idx, 0:3, 0:3]
-        aos[idx, 0:3, 0:3] = ((v[..., 0:1] * m[:, 0] + v[..., 1:2] * m[:, 1]) + v[..., 2:3] * m[:, 2]) + o
-        tris = (abi.RtTriangle * len(self)).from_buffer(aos)
-        for i in idx:
-            lib().rt_triangle_compute_normal(C.byref(tris[int(i)]))
+        sel = np.ascontiguousarray(aos[idx])                 # the chosen triangles as one range: one call
+        lib().rt_scene_transform(sel.ctypes.data_as(C.POINTER(abi.RtTriangle)), len(sel), 0, len(sel), _fp(xf))
+        aos[idx] = sel
+        return Scene(aos)
+
+    def posed(self, ranges, xforms):
+        """The scene P(self, xforms) of include/uob_rt.h "rigid objects": object k = the triangles ranges[k] ((first, count)
+        or a slice) transformed by xforms[k] ([3,4]: matrix | translation) with rt_scene_transform, the host restatement of
+        RayTracer.pose_objects."""
+        ranges = _object_ranges(ranges, len(self))
+        xf = np.ascontiguousarray(xforms, np.float32).reshape(len(ranges), 3, 4)
+        aos = self.aos.copy()
+        tris = aos.ctypes.data_as(C.POINTER(abi.RtTriangle))
+        for (first, count), x in zip(ranges, xf):
+            lib().rt_scene_transform(tris, len(self), first, count, _fp(np.ascontiguousarray(x)))
         return Scene(aos)
 
     def packed(self):
@@ -261,6 +295,7 @@ class RayTracer:
         self.width = cfg.width
         self.n_triangles = len(scene)
         self.rows = lib().rt_config_owned_rows(C.byref(cfg))
+        self.objects = None         # the (first, count) ranges of set_objects; a scene update or replace forgets them
         # the device the context's queries run on (devices[0]; None: the device that was current at rt_init)
         self.device = cfg.devices[0] if cfg.num_devices >= 1 else (cfg.device if cfg.device >= 0 else None)
 
@@ -275,12 +310,14 @@ class RayTracer:
         _check(lib().rt_update_scene(self._h, _fp(v), _fp(nr), _fp(c), len(scene), self._update_flags(reorder, device_tiles)))
         self.scene = scene
         self._keep = (v, nr, c)
+        self.objects = None
 
     def update_scene_device(self, v_ptr, n_ptr, c_ptr, n, stream=None, reorder=False, device_tiles=False):
         """The same from device memory (raw pointers, e.g. torch .data_ptr() of float32 [3n,4] / [n,4] / [n,4]), enqueued
         on `stream` (rt_update_scene_device).  The source buffers must stay unchanged until the stream has passed it."""
         _check(lib().rt_update_scene_device(self._h, C.c_void_p(v_ptr), C.c_void_p(n_ptr), C.c_void_p(c_ptr), n,
                                             self._update_flags(reorder, device_tiles), C.c_void_p(stream or 0)))
+        self.objects = None
 
     def replace_scene(self, scene, device_tiles=False):
         """Replace the context's triangles by a scene of any count (rt_replace_scene), blocking.  scene: a Scene, or the three
@@ -298,6 +335,7 @@ class RayTracer:
         self.scene = scene
         self._keep = (v, nr, c)
         self.n_triangles = n
+        self.objects = None
 
     def replace_scene_device(self, vertices, normals, colors, stream=None, reorder=False):
         """The same from torch tensors on the context's device (float32 [3n,4] / [n,4] / [n,4]), enqueued on `stream` (a torch
@@ -317,6 +355,44 @@ class RayTracer:
                                              C.c_void_p(raw)))
         self.scene = None
         self.n_triangles = n
+        self.objects = None
+
+    def set_objects(self, ranges):
+        """Make the context's current scene the rest pose of rigid objects (rt_set_objects): ranges = a list of
+        (first, count) pairs or slices of triangles, non-empty and disjoint; an empty list drops the table."""
+        ranges = _object_ranges(ranges or (), self.n_triangles)
+        first = np.asarray([r[0] for r in ranges], np.int32)
+        count = np.asarray([r[1] for r in ranges], np.int32)
+        ip = C.POINTER(C.c_int32)
+        _check(lib().rt_set_objects(self._h, first.ctypes.data_as(ip), count.ctypes.data_as(ip), len(ranges)))
+        self.objects = ranges or None
+
+    def object_count(self):
+        """Objects in the context's table (rt_debug_object_count)."""
+        out = C.c_int32()
+        _check(lib().rt_debug_object_count(self._h, C.byref(out)))
+        return int(out.value)
+
+    def pose_objects(self, xforms, reorder=False, device_tiles=False):
+        """Pose the objects from the rest pose (rt_pose_objects), blocking: xforms = array [nobj, 3, 4], per object the matrix
+        and, in the last column, the translation.  The tiles are refitted, or made again with reorder / device_tiles as in
+        update_scene.  The context then holds Scene.posed(ranges, xforms) of the rest scene."""
+        xf = np.ascontiguousarray(xforms, np.float32)
+        if xf.shape != (len(self.objects or ()), 3, 4):
+            raise ValueError("xforms must have shape [%d, 3, 4]" % len(self.objects or ()))
+        _check(lib().rt_pose_objects(self._h, _fp(xf), self._update_flags(reorder, device_tiles)))
+        self.scene = None
+
+    def pose_objects_device(self, xforms, stream=None, device_tiles=False, reorder=False):
+        """The same with the matrices in a torch tensor float32 [nobj, 3, 4] on the context's device, enqueued on `stream` (a
+        torch stream or a raw hipStream_t; default: torch's current stream) (rt_pose_objects_device).  The tensor must stay
+        unchanged until the stream has passed the call."""
+        dev = self._torch_device()
+        _need("xforms", xforms, _torch.float32, (len(self.objects or ()), 3, 4), dev)
+        raw = self._raw_stream(stream, dev)
+        _check(lib().rt_pose_objects_device(self._h, C.c_void_p(xforms.data_ptr()), self._update_flags(reorder, device_tiles),
+                                            C.c_void_p(raw)))
+        self.scene = None
 
     def update_spheres(self, spheres):
         """Replace the sphere table (rt_update_spheres): a list of up to RT_MAX_SPHERES (centre, radius_sq, colour rgba)
