@@ -14,8 +14,9 @@
 // IS N-1 independent peer copies; they occupy no compute unit, so they run beside the next frame's persistent
 // grid.  (The one-process-per-GPU flow of bench.py gathers with RCCL through torch.distributed instead.)
 //
-// Here: contexts, frames, delivery across devices, scene updates, output registration and diagnostics.  The calls beside
-// the frame (ray queries, shade and radiance calls, AOV passes) are rt_calls.hip; the context itself is rt_host.h.
+// Here: the error text, contexts, frames, delivery across devices, output registration and diagnostics.  The scene of a
+// context — rt_init's first one (scene_first) and every later edit of it — is rt_scene.hip; the calls beside the frame (ray
+// queries, shade and radiance calls, AOV passes) are rt_calls.hip; the context itself is rt_host.h.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -40,22 +41,12 @@ void set_error(const char* fmt, ...) {
   g_last_error = buf;
 }
 
+KeepError::KeepError() : text(g_last_error) {}
+KeepError::~KeepError() { g_last_error = text; }
+
 }  // namespace uobrt
 
 using namespace uobrt;
-
-constexpr int kWorldGrid = 32;       // world cells per axis of the mesh kernel's shadow-ray tile masks
-
-// rt_init's and rt_update_spheres' bounds of a sphere table (the count is checked by the caller)
-static int validate_spheres(const rt_sphere* sph, int num) {
-  for (int i = 0; i < num; ++i) {
-    const rt_sphere& s = sph[i];
-    for (int k = 0; k < 3; ++k)
-      if (!(fabsf(s.center[k]) <= kMaxCoordinate)) { set_error("sphere %d: |centre| must be finite and <= 2^16", i); return RT_E_INVALID; }
-    if (!(fabsf(s.radius_sq) <= kMaxCoordinate * kMaxCoordinate)) { set_error("sphere %d: radius_sq must be finite and <= 2^32", i); return RT_E_INVALID; }
-  }
-  return RT_OK;
-}
 
 static int validate_config(const rt_config* c) {
   if (!c) { set_error("rt_config is NULL"); return RT_E_INVALID; }
@@ -103,70 +94,6 @@ static Tuning read_tuning(const rt_config& cfg) {
   return t;
 }
 
-// Coordinate bound: the range over which the exact culls are verified and which keeps every
-// determinant of the intersection tests below 2^126, where the v_rcp_f32 + Newton reciprocal equals IEEE
-// division bit for bit (rt_math.h rcp_exact).
-static int validate_vertices(const float* vertices4, int n) {
-  for (size_t k = 0; k < (size_t)n * 12; ++k) {
-    if ((k & 3) != 3 && !(fabsf(vertices4[k]) <= kMaxCoordinate)) {
-      set_error("vertex %zu: coordinates must be finite and |x| <= 2^16", k / 4); return RT_E_INVALID;
-    }
-  }
-  return RT_OK;
-}
-
-static int count_shadow_casters(const float* colors4, int n) {
-  int cnt = 0;
-  for (int i = 0; i < n; ++i) cnt += (colors4[4 * i + 3] != -1.0f);
-  return cnt;
-}
-
-// The tiled copy into the context's buffers (scene_reserve has made them), on c->stream; blocking
-static int upload_tiled(rt_ctx* c, const float* v4, const float* n4, const float* c4, const std::vector<int>& orig,
-                        const std::vector<float>& box) {
-  const int n = c->n, ntiles = mesh_tiles(n);
-  std::vector<float> pv((size_t)n * 12), pn((size_t)n * 4), pc((size_t)n * 4);
-  for (int j = 0; j < n; ++j) {
-    const int i = orig[(size_t)j];
-    memcpy(&pv[(size_t)12 * j], v4 + (size_t)12 * i, 48);
-    memcpy(&pn[(size_t)4 * j], n4 + (size_t)4 * i, 16);
-    memcpy(&pc[(size_t)4 * j], c4 + (size_t)4 * i, 16);
-  }
-  const size_t nb = (size_t)n * sizeof(float4);
-  if (hipMemcpyAsync(c->d_verts_m, pv.data(), 3 * nb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(c->d_normals_m, pn.data(), nb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(c->d_colors_m, pc.data(), nb, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(c->d_orig, orig.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(c->d_tile_box, box.data(), (size_t)ntiles * 3 * sizeof(float4), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess) {
-    set_error("scene upload failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
-  }
-  return RT_OK;
-}
-
-// The context's sphere table (cfg.spheres) into device memory; blocking
-static int upload_spheres(rt_ctx* c) {
-  const rt_config* cfg = &c->cfg;
-  DevSphere tab[RT_MAX_SPHERES];
-  memset(tab, 0, sizeof tab);
-  for (int i = 0; i < cfg->num_spheres; ++i) {
-    tab[i].cx = cfg->spheres[i].center[0]; tab[i].cy = cfg->spheres[i].center[1]; tab[i].cz = cfg->spheres[i].center[2];
-    tab[i].r2 = cfg->spheres[i].radius_sq;
-    memcpy(tab[i].col, cfg->spheres[i].color, 16);
-  }
-  if (hipMemcpy(c->d_spheres, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("sphere table upload failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
-  }
-  return RT_OK;
-}
-
-static int scene_first(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n);   // below, with the scene updates
-
-static int upload_tiled_scene(rt_ctx* c, const float* v4, const float* n4, const float* c4) {
-  const std::vector<int> orig = tiled_order(v4, c->n, c->tune.tile_morton);
-  return upload_tiled(c, v4, n4, c4, orig, tile_data_host(v4, orig.data(), c->n));
-}
-
 extern "C" {
 
 int rt_abi_version(void) { return RT_ABI_VERSION; }
@@ -193,20 +120,6 @@ int32_t rt_config_owned_rows(const rt_config* c) {
   int rows = 0;
   for (int y = 0; y < c->height; ++y) rows += ((y / c->band_rows) % c->band_count) == c->band_index;
   return rows;
-}
-
-// Every surface point lies on a triangle or a sphere: their bounding box, from the vertices' (the world grid of the
-// mesh kernel's shadow-ray tile masks spans it: fill_params)
-static void set_scene_box(rt_ctx* c, const float vlo[3], const float vhi[3]) {
-  for (int k = 0; k < 3; ++k) { c->box_lo[k] = c->vbox_lo[k] = vlo[k]; c->box_hi[k] = c->vbox_hi[k] = vhi[k]; }
-  const rt_config* cfg = &c->cfg;
-  for (int i = 0; i < cfg->num_spheres; ++i) {
-    const float r = sqrtf(fmaxf(cfg->spheres[i].radius_sq, 0.0f)) * 1.0001f + 1e-6f;
-    for (int k = 0; k < 3; ++k) {
-      c->box_lo[k] = fminf(c->box_lo[k], cfg->spheres[i].center[k] - r);
-      c->box_hi[k] = fmaxf(c->box_hi[k], cfg->spheres[i].center[k] + r);
-    }
-  }
 }
 
 static int init_parent(const rt_config* cfg, const float* vertices4, const float* normals4, const float* colors4,
@@ -310,7 +223,7 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
   }
   rc = upload_spheres(c);
   if (rc != RT_OK) return fail(rc);
-  // the scene: buffers by n, upload, tiles, n_shadow, scene box, kernel family — the routine rt_replace_scene calls too
+  // the scene: buffers by n, upload, tiles, n_shadow, scene box, kernel family — the routine every later edit goes through (rt_scene.hip)
   rc = scene_first(c, vertices4, normals4, colors4, n);
   if (rc != RT_OK) return fail(rc);
   *out_ctx = c;
@@ -430,7 +343,7 @@ void uobrt::fill_params(const rt_ctx* c, const float rot[12], const float cam[3]
   }
 }
 
-// The mesh kernel works on the reordered copy of the scene (upload_tiled_scene)
+// The mesh kernel works on the reordered copy of the scene (rt_scene.hip upload_tiled_scene)
 void uobrt::use_tiled_scene(const rt_ctx* c, FrameParams* P) {
   P->verts = c->d_verts_m; P->normals = c->d_normals_m; P->colors = c->d_colors_m;
   P->orig = c->d_orig; P->tile_box = c->d_tile_box;
@@ -517,644 +430,6 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
   return RT_OK;
 }
 
-// ---- scene updates (rt_update_scene / rt_update_scene_device) ----------------------------------------------
-// The tiling of rt_init is kept: tile membership is a free choice (the closest hit resolves ties by the original index,
-// d_orig), so only the tiles' data are recomputed for the new vertices (rt_scene_update.hip rt_scene_refit), unless the
-// caller asks for the tiles to be sorted again (RT_UPDATE_REORDER: the rt_init path on the host).
-
-// An update enqueued on `s` first waits for everything that may still read the buffers it overwrites: the context's
-// previous frame (ev1, on whichever stream it ran), the calls that still read the scene, its latest AOV pass and its
-// previous update
-static int update_begin(rt_ctx* c, hipStream_t s) {
-  HIP_TRY(hipSetDevice(c->device));
-  if (c->timed) HIP_TRY(hipStreamWaitEvent(s, c->ev1, 0));
-  if (wait_scene_readers(c, s) != RT_OK) return RT_E_DEVICE;
-  HIP_TRY(wait_aov(c, s));
-  HIP_TRY(wait_scene(c, s));
-  return RT_OK;
-}
-
-// What the checks of a new scene derive from it, before any buffer is touched
-struct SceneSummary {
-  int n_shadow = 0;
-  float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // the vertices' box
-};
-
-static void update_state(rt_ctx* c, const SceneSummary& sum) {
-  c->n_shadow = sum.n_shadow;
-  if (c->d_screen_masks) set_scene_box(c, sum.lo, sum.hi);
-}
-
-// ---- the scene of a context: rt_init's first one and every replacement (rt_replace_scene*) ---------------------------
-// Which buffers a scene of n triangles needs, by rt_init's rules
-struct SceneNeeds {
-  bool records, tiled, masks, heavy, mesh_sched;
-};
-
-static SceneNeeds scene_needs(const rt_ctx* c, int n) {
-  const int f = c->cfg.flags;
-  SceneNeeds q;
-  q.records = n > 64;                                        // the staged records of the generic and mesh kernels
-  q.tiled = n > 64 && !(f & RT_FLAG_GENERIC_KERNEL);         // the mesh kernel's tiled copy
-  // candidate-tile masks: from 17 tiles on (with fewer, building and reading them costs more than the visits they save)
-  q.masks = n > 16 * 64 && !(f & (RT_FLAG_NO_TILE_BINS | RT_FLAG_NO_CULL | RT_FLAG_GENERIC_KERNEL));
-  q.heavy = n >= 1 && n <= 64 && !c->tune.plain_order;       // wave kernel: last frame's expensive jobs
-  q.mesh_sched = q.tiled && !c->tune.plain_order;            // mesh kernel: last frame's block costs
-  return q;
-}
-
-// New buffers of a scene that outgrows the context's capacity; they replace the old ones only in scene_commit, when every
-// allocation of every device has succeeded
-struct SceneGrowth {
-  int cap = 0;                                               // 0: the scene fits, nothing to replace
-  float4 *verts = nullptr, *normals = nullptr, *colors = nullptr;
-  SceneStore t;
-};
-
-static void free_growth(SceneGrowth* g) {
-  hipFree(g->verts); hipFree(g->normals); hipFree(g->colors); hipFree(g->t.records);
-  hipFree(g->t.verts_m); hipFree(g->t.normals_m); hipFree(g->t.colors_m); hipFree(g->t.orig); hipFree(g->t.tile_box);
-  hipFree(g->t.screen_masks); hipFree(g->t.world_masks);
-  *g = SceneGrowth();
-}
-
-// Everything a scene of n triangles needs that the context does not hold yet.  Nothing the context renders from is touched:
-// what outgrows the capacity goes into *g; what the context meets for the first time (the buffers of a kernel family it has
-// not run yet) goes into its store, which no frame reads before scene_select.  device_tiles: the device tile build will run.
-static int scene_reserve(rt_ctx* c, int n, bool device_tiles, SceneGrowth* g) {
-  if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", c->device); return RT_E_DEVICE; }
-  const SceneNeeds q = scene_needs(c, n);
-  const rt_config& cfg = c->cfg;
-  SceneStore& o = c->own;
-  bool ok = true;
-  auto get = [&](auto** p, size_t bytes) { if (ok && hipMalloc(p, bytes ? bytes : 1) != hipSuccess) ok = false; };
-  auto tiled_set = [&](SceneStore* t, int cap) {
-    const size_t nb = (size_t)cap * sizeof(float4);
-    get(&t->verts_m, 3 * nb); get(&t->normals_m, nb); get(&t->colors_m, nb); get(&t->orig, (size_t)cap * sizeof(int));
-    get(&t->tile_box, (size_t)mesh_tiles(cap) * 3 * sizeof(float4));
-  };
-  auto mask_set = [&](SceneStore* t, int cap) {
-    const size_t nwords = (size_t)((mesh_tiles(cap) + 63) / 64), g3 = (size_t)kWorldGrid * kWorldGrid * kWorldGrid;
-    get(&t->screen_masks, (size_t)mesh_screen_cells(cfg.width) * mesh_screen_cells(cfg.height) * nwords * 8);
-    get(&t->world_masks, g3 * nwords * 8);
-  };
-  const bool grow = n > c->cap || !c->d_verts;
-  const int cap = grow ? (n > 0 ? n : 1) : c->cap;
-  if (grow) {    // (what the context already keeps for another family grows too: a later replace within capacity allocates nothing)
-    const size_t nb = (size_t)cap * sizeof(float4);
-    g->cap = cap;
-    get(&g->verts, 3 * nb); get(&g->normals, nb); get(&g->colors, nb);
-    if (q.records || o.records) get(&g->t.records, (size_t)cap * kRecordsPerTriangle * sizeof(float4));
-    if (q.tiled || o.verts_m) tiled_set(&g->t, cap);
-    if (q.masks || o.screen_masks) mask_set(&g->t, cap);
-  } else {
-    if (q.records && !o.records) get(&o.records, (size_t)cap * kRecordsPerTriangle * sizeof(float4));
-    if (q.tiled && !o.verts_m) tiled_set(&o, cap);
-    if (q.masks && !o.screen_masks) mask_set(&o, cap);
-  }
-  if (q.masks && !o.world_occ) get(&o.world_occ, (size_t)mesh_occ_words(kWorldGrid) * sizeof(unsigned int));
-  if (q.heavy && !o.heavy_flags) {
-    get(&o.heavy[0], (size_t)c->heavy_cap * 4); get(&o.heavy[1], (size_t)c->heavy_cap * 4); get(&o.heavy_flags, 2 * c->heavy_jobs_max * 4);
-  }
-  if (q.mesh_sched && !o.mesh_cost) {
-    const size_t jobs = (size_t)((cfg.width + 15) / 16) * (size_t)((c->owned_rows + 15) / 16);
-    // order list: up to four entries per block, + its length in the word behind it
-    get(&o.mesh_cost, (jobs ? jobs : 1) * 4); get(&o.mesh_order, (4 * (jobs ? jobs : 1) + 1) * 4);
-  }
-  if (!ok) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); free_growth(g); return RT_E_NOMEM; }
-  if (device_tiles && q.tiled) {
-    const int rc = ensure_bytes(&c->tile_scratch, tile_build_scratch_bytes(cap));
-    if (rc != RT_OK) { free_growth(g); return rc; }
-  }
-  if (q.masks && !c->aux_stream &&
-      (hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess ||
-       hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)) {
-    set_error("stream/event creation failed"); free_growth(g); return RT_E_DEVICE;
-  }
-  return RT_OK;
-}
-
-// The grown buffers take the place of the old ones.  hipFree waits for whatever still uses what it frees.  From here to
-// scene_select the context's working pointers are stale: the caller installs the new scene next, and nothing in between fails
-// for a reason the caller could have (validation and allocation are behind it).
-static void scene_commit(rt_ctx* c, SceneGrowth* g) {
-  if (!g->cap) return;
-  hipSetDevice(c->device);
-  SceneStore& o = c->own;
-  hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);
-  hipFree(o.records); hipFree(o.verts_m); hipFree(o.normals_m); hipFree(o.colors_m); hipFree(o.orig); hipFree(o.tile_box);
-  hipFree(o.screen_masks); hipFree(o.world_masks);
-  hipFree(c->d_qrecords); c->d_qrecords = nullptr;           // (the queries make theirs on demand, for the capacity)
-  c->d_verts = g->verts; c->d_normals = g->normals; c->d_colors = g->colors;
-  o.records = g->t.records;
-  o.verts_m = g->t.verts_m; o.normals_m = g->t.normals_m; o.colors_m = g->t.colors_m; o.orig = g->t.orig; o.tile_box = g->t.tile_box;
-  o.screen_masks = g->t.screen_masks; o.world_masks = g->t.world_masks;
-  c->cap = g->cap;
-  *g = SceneGrowth();
-}
-
-// The working pointers for a scene of n triangles: which kernel runs is decided from them, as rt_init decides it
-static void scene_select(rt_ctx* c, int n) {
-  const SceneNeeds q = scene_needs(c, n);
-  const SceneStore& o = c->own;
-  c->n = n;
-  c->d_records = q.records ? o.records : nullptr;
-  c->d_verts_m = q.tiled ? o.verts_m : nullptr; c->d_normals_m = q.tiled ? o.normals_m : nullptr;
-  c->d_colors_m = q.tiled ? o.colors_m : nullptr; c->d_orig = q.tiled ? o.orig : nullptr; c->d_tile_box = q.tiled ? o.tile_box : nullptr;
-  c->d_screen_masks = q.masks ? o.screen_masks : nullptr; c->d_world_masks = q.masks ? o.world_masks : nullptr;
-  c->d_world_occ = q.masks ? o.world_occ : nullptr;
-  c->nwords = q.masks ? (mesh_tiles(n) + 63) / 64 : 0;
-  c->scx = q.masks ? mesh_screen_cells(c->cfg.width) : 0; c->scy = q.masks ? mesh_screen_cells(c->cfg.height) : 0;
-  c->d_heavy[0] = q.heavy ? o.heavy[0] : nullptr; c->d_heavy[1] = q.heavy ? o.heavy[1] : nullptr;
-  c->d_heavy_flags = q.heavy ? o.heavy_flags : nullptr;
-  c->d_mesh_cost = q.mesh_sched ? o.mesh_cost : nullptr; c->d_mesh_order = q.mesh_sched ? o.mesh_order : nullptr;
-}
-
-// Switch the context to a scene of n triangles, on stream s behind update_begin.  The scheduling state is indexed by screen
-// jobs and blocks, not by triangles: it is kept unless the scene crosses n = 64 (or is the first): then the next frame is a
-// first frame, the state rt_init leaves.
-static int scene_switch(rt_ctx* c, int n, bool first, hipStream_t s) {
-  const bool restart = first || (c->n > 64) != (n > 64);
-  scene_select(c, n);
-  if (!restart) return RT_OK;
-  c->mesh_order_valid = false;
-  c->heavy_phase = 0; c->heavy_gen = 0;
-  HIP_TRY(hipMemsetAsync(c->d_jobctr, 0, (2 * kJobHeads + 2) * kJobHeadStride * sizeof(unsigned int), s));
-  if (c->d_heavy_flags) HIP_TRY(hipMemsetAsync(c->d_heavy_flags, 0, 2 * c->heavy_jobs_max * 4, s));
-  return RT_OK;
-}
-
-// Morton tiles on the device into d_orig (rt_tile_build.hip); rt_scene_refit follows
-static int device_tiles(rt_ctx* c, const SceneSummary& sum, hipStream_t s) {
-  if (launch_tile_build(c->d_verts, c->n, sum.lo, sum.hi, c->d_orig, c->tile_scratch.p, s) != 0) {
-    set_error("tile build launch failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
-  }
-  return RT_OK;
-}
-
-static void refit(rt_ctx* c, hipStream_t s) {
-  launch_scene_refit(c->d_verts, c->d_normals, c->d_colors, c->d_orig, c->n, c->d_verts_m, c->d_normals_m, c->d_colors_m,
-                     c->d_tile_box, s);
-}
-
-// Host arrays (validated) into one single-device context; blocking.  replace: a scene of n triangles takes the place of
-// the context's (scene_reserve / scene_commit are behind it); else n is the context's count.
-static int scene_host_one(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n, uint32_t flags,
-                          const SceneSummary& sum, bool replace, bool first = false) {
-  int rc = update_begin(c, c->stream);
-  if (rc != RT_OK) return rc;
-  if (replace) { rc = scene_switch(c, n, first, c->stream); if (rc != RT_OK) return rc; }
-  const size_t nb = (size_t)n * sizeof(float4);
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(c->d_verts, v4, 3 * nb, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_normals, n4, nb, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_colors, c4, nb, hipMemcpyHostToDevice, c->stream));
-  }
-  if (c->d_verts_m) {
-    if (flags & RT_UPDATE_DEVICE_TILES) {
-      rc = device_tiles(c, sum, c->stream);
-      if (rc != RT_OK) return rc;
-      refit(c, c->stream);
-      HIP_TRY(hipGetLastError());
-    } else if (replace || (flags & RT_UPDATE_REORDER)) {
-      rc = upload_tiled_scene(c, v4, n4, c4);
-      if (rc != RT_OK) return rc;
-    } else {
-      refit(c, c->stream);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  update_state(c, sum);
-  return RT_OK;
-}
-
-// Device arrays on device src_dev (validated) into one single-device context, enqueued on `s` (a stream of c->device);
-// dc == nullptr: the colours stay (a pose)
-static int scene_device_one(rt_ctx* c, const void* dv, const void* dn, const void* dc, int src_dev, int n, uint32_t flags,
-                            hipStream_t s, const SceneSummary& sum, bool replace) {
-  int rc = update_begin(c, s);
-  if (rc != RT_OK) return rc;
-  if (!c->ev_upd) HIP_TRY(hipEventCreateWithFlags(&c->ev_upd, hipEventDisableTiming));
-  if (replace) { rc = scene_switch(c, n, false, s); if (rc != RT_OK) return rc; }
-  const size_t nb = (size_t)n * sizeof(float4);
-  if (src_dev == c->device) {
-    HIP_TRY(hipMemcpyAsync(c->d_verts, dv, 3 * nb, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->d_normals, dn, nb, hipMemcpyDeviceToDevice, s));
-    if (dc) HIP_TRY(hipMemcpyAsync(c->d_colors, dc, nb, hipMemcpyDeviceToDevice, s));
-  } else {                                   // the other devices of a multi-device context: by peer copy, as the bands
-    HIP_TRY(hipMemcpyPeerAsync(c->d_verts, c->device, dv, src_dev, 3 * nb, s));
-    HIP_TRY(hipMemcpyPeerAsync(c->d_normals, c->device, dn, src_dev, nb, s));
-    if (dc) HIP_TRY(hipMemcpyPeerAsync(c->d_colors, c->device, dc, src_dev, nb, s));
-  }
-  if (c->d_verts_m) {
-    if (replace || (flags & RT_UPDATE_DEVICE_TILES)) { rc = device_tiles(c, sum, s); if (rc != RT_OK) return rc; }
-    refit(c, s);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipEventRecord(c->ev_upd, s));
-  c->upd_pending = true;
-  update_state(c, sum);
-  return RT_OK;
-}
-
-// The single-device contexts behind a handle
-static std::vector<rt_ctx*> device_ctxs(rt_ctx* c) { return c->kids.empty() ? std::vector<rt_ctx*>(1, c) : c->kids; }
-
-// Room for a scene of n triangles on every device of the handle, or no change at all
-static int scene_reserve_all(rt_ctx* c, int n, bool device_tiles_wanted) {
-  const std::vector<rt_ctx*> ks = device_ctxs(c);
-  std::vector<SceneGrowth> grown(ks.size());
-  for (size_t i = 0; i < ks.size(); ++i) {
-    const int rc = scene_reserve(ks[i], n, device_tiles_wanted, &grown[i]);
-    if (rc != RT_OK) {
-      const std::string msg = g_last_error;
-      for (size_t j = 0; j < i; ++j) { hipSetDevice(ks[j]->device); free_growth(&grown[j]); }
-      g_last_error = msg;
-      return rc;
-    }
-  }
-  for (size_t i = 0; i < ks.size(); ++i) scene_commit(ks[i], &grown[i]);
-  return RT_OK;
-}
-
-// What a multi-device handle itself reports of the scene
-static void parent_follows(rt_ctx* c) {
-  if (!c->kids.empty()) { c->n = c->kids[0]->n; c->cap = c->kids[0]->cap; c->n_shadow = c->kids[0]->n_shadow; }
-}
-
-static int scene_first(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n) {
-  SceneGrowth g;
-  int rc = scene_reserve(c, n, false, &g);
-  if (rc != RT_OK) return rc;
-  scene_commit(c, &g);
-  SceneSummary sum;
-  sum.n_shadow = count_shadow_casters(c4, n);
-  if (scene_needs(c, n).masks) vertex_box(v4, n, sum.lo, sum.hi);
-  return scene_host_one(c, v4, n4, c4, n, 0, sum, true, true);
-}
-
-static int replace_host_all(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n, uint32_t flags, const SceneSummary& sum) {
-  int rc = scene_reserve_all(c, n, (flags & RT_UPDATE_DEVICE_TILES) != 0);
-  if (rc != RT_OK) return rc;
-  for (rt_ctx* k : device_ctxs(c)) {
-    rc = scene_host_one(k, v4, n4, c4, n, flags, sum, true);
-    if (rc != RT_OK) return rc;
-  }
-  parent_follows(c);
-  return RT_OK;
-}
-
-static int update_host_all(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n, uint32_t flags, const SceneSummary& sum) {
-  for (rt_ctx* k : device_ctxs(c)) {
-    int rc = RT_OK;
-    if ((flags & RT_UPDATE_DEVICE_TILES) && k->d_verts_m) {
-      HIP_TRY(hipSetDevice(k->device));
-      rc = ensure_bytes(&k->tile_scratch, tile_build_scratch_bytes(k->cap));
-    }
-    if (rc == RT_OK) rc = scene_host_one(k, v4, n4, c4, n, flags, sum, false);
-    if (rc != RT_OK) return rc;
-  }
-  return RT_OK;
-}
-
-static const uint32_t kUpdateFlags = RT_UPDATE_REORDER | RT_UPDATE_DEVICE_TILES;
-
-static int check_scene_flags(uint32_t flags, const char* fn) {
-  if (flags & ~kUpdateFlags) { set_error("%s: unknown flags 0x%x", fn, flags); return RT_E_INVALID; }
-  if ((flags & kUpdateFlags) == kUpdateFlags) {
-    set_error("%s: RT_UPDATE_REORDER (host tiles) and RT_UPDATE_DEVICE_TILES exclude each other", fn); return RT_E_INVALID;
-  }
-  return RT_OK;
-}
-
-static int check_update_args(const rt_ctx* c, const void* v, const void* nr, const void* col, int32_t n, uint32_t flags) {
-  if (!c) { set_error("NULL context"); return RT_E_INVALID; }
-  if (n != c->n) { set_error("rt_update_scene: n = %d, but the context holds %d triangles", n, c->n); return RT_E_INVALID; }
-  if (n > 0 && (!v || !nr || !col)) { set_error("scene arrays missing"); return RT_E_INVALID; }
-  return check_scene_flags(flags, "rt_update_scene");
-}
-
-static int check_replace_args(const rt_ctx* c, const void* v, const void* nr, const void* col, int32_t n, uint32_t flags) {
-  if (!c) { set_error("rt_replace_scene: NULL context"); return RT_E_INVALID; }
-  if (!v || !nr || !col) { set_error("rt_replace_scene: scene arrays missing (NULL)"); return RT_E_INVALID; }
-  if (n <= 0) { set_error("rt_replace_scene: n_new = %d, but a scene has at least one triangle", n); return RT_E_INVALID; }
-  const int rc = check_scene_flags(flags, "rt_replace_scene");
-  if (rc != RT_OK) return rc;
-  if (n > 4000000) { set_error("triangle list of %d exceeds the supported maximum of 4000000", n); return RT_E_UNSUPPORTED; }
-  return RT_OK;
-}
-
-static float key_to_float(unsigned int k) {   // inverse of rt_scene_update.hip order_key
-  const unsigned int u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-// First pass of a device entry, on the caller's arrays: check the bound and reduce n_shadow and the box.  Returns once the
-// result has been read back (this synchronises s); the context's buffers are untouched.
-static int device_check(rt_ctx* c, const void* dv, const void* dc, int n, hipStream_t s, SceneSummary* sum) {
-  HIP_TRY(hipSetDevice(c->device));
-  if (!c->d_check) HIP_TRY(hipMalloc(&c->d_check, 8 * sizeof(unsigned int)));
-  if (launch_scene_check((const float4*)dv, (const float4*)dc, n, c->d_check, s) != 0) {
-    set_error("scene check launch failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
-  }
-  unsigned int res[8];
-  HIP_TRY(hipMemcpyAsync(res, c->d_check, sizeof res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (res[0] != 0u) { set_error("%u vertex coordinate(s) not finite or |x| > 2^16", res[0]); return RT_E_INVALID; }
-  sum->n_shadow = (int)res[1];
-  for (int k = 0; k < 3; ++k) { sum->lo[k] = key_to_float(res[2 + k]); sum->hi[k] = key_to_float(res[5 + k]); }
-  return RT_OK;
-}
-
-// Device arrays into every device of the handle: a single device on the caller's stream; several devices each on its own
-// stream after the caller's earlier work, copying from devices[0], and the caller's stream passes only when all have it
-static int scene_device_all(rt_ctx* c, const void* dv, const void* dn, const void* dc, int n, uint32_t flags, hipStream_t s,
-                            const SceneSummary& sum, bool replace) {
-  if (c->kids.empty()) return scene_device_one(c, dv, dn, dc, c->device, n, flags, s, sum, replace);
-  HIP_TRY(hipEventRecord(c->ev_go, s));
-  for (rt_ctx* k : c->kids) {
-    HIP_TRY(hipSetDevice(k->device));
-    HIP_TRY(hipStreamWaitEvent(k->stream, c->ev_go, 0));
-    const int rc = scene_device_one(k, dv, dn, dc, c->device, n, flags, k->stream, sum, replace);
-    if (rc != RT_OK) return rc;
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  for (rt_ctx* k : c->kids) HIP_TRY(hipStreamWaitEvent(s, k->ev_upd, 0));
-  return RT_OK;
-}
-
-// The scene of a device entry through host memory (RT_UPDATE_REORDER: the tiles are sorted on the host)
-struct HostScene {
-  std::vector<float> v, nr, col;
-};
-
-static int stage_to_host(const void* dv, const void* dn, const void* dc, int n, hipStream_t s, HostScene* h) {
-  h->v.resize((size_t)n * 12); h->nr.resize((size_t)n * 4); h->col.resize((size_t)n * 4);
-  HIP_TRY(hipMemcpyAsync(h->v.data(), dv, h->v.size() * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(h->nr.data(), dn, h->nr.size() * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(h->col.data(), dc, h->col.size() * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return RT_OK;
-}
-
-// A same-count scene in device memory on the handle's device that has passed device_check (the caller's arrays, or the
-// staging scene a pose has written; dc == nullptr: the colours stay) into every device of the handle, behind stream s
-static int update_from_device(rt_ctx* c, const void* dv, const void* dn, const void* dc, int n, uint32_t flags, hipStream_t s,
-                              const SceneSummary& sum) {
-  if (flags & RT_UPDATE_REORDER) {             // the tiles are sorted on the host: stage the scene through it
-    HostScene h;
-    const int rc = stage_to_host(dv, dn, dc ? dc : lead_ctx(c)->d_colors, n, s, &h);
-    if (rc != RT_OK) return rc;
-    return update_host_all(c, h.v.data(), h.nr.data(), h.col.data(), n, flags, sum);
-  }
-  if (flags & RT_UPDATE_DEVICE_TILES)
-    for (rt_ctx* k : device_ctxs(c))
-      if (k->d_verts_m) {
-        HIP_TRY(hipSetDevice(k->device));
-        const int rc = ensure_bytes(&k->tile_scratch, tile_build_scratch_bytes(k->cap));
-        if (rc != RT_OK) return rc;
-      }
-  return scene_device_all(c, dv, dn, dc, n, flags, s, sum, false);
-}
-
-// ---- rigid objects (rt_set_objects / rt_pose_objects*): DESIGN.md 4.2b -------------------------------------------------
-// The table and the rest pose live on the context that poses (lead_ctx).  Nothing here runs for a context without a table.
-static void drop_objects(rt_ctx* c) {
-  rt_ctx* L = lead_ctx(c);
-  L->nobj = 0;
-  if (!L->d_rest_verts && !L->d_rest_normals && !L->d_object_of) return;
-  DeviceGuard guard;
-  hipSetDevice(L->device);
-  hipFree(L->d_rest_verts); hipFree(L->d_rest_normals); hipFree(L->d_object_of);   // (hipFree waits for a pose still reading them)
-  L->d_rest_verts = L->d_rest_normals = nullptr; L->d_object_of = nullptr;
-}
-
-static int check_pose_args(rt_ctx* c, const void* xforms, uint32_t flags, const char* fn) {
-  if (!c) { set_error("%s: NULL context", fn); return RT_E_INVALID; }
-  if (!xforms) { set_error("%s: the matrices are missing (NULL)", fn); return RT_E_INVALID; }
-  const int rc = check_scene_flags(flags, fn);
-  if (rc != RT_OK) return rc;
-  if (lead_ctx(c)->nobj == 0) {
-    set_error("%s: the context has no object table (rt_set_objects first; a scene update or replace drops it)", fn);
-    return RT_E_INVALID;
-  }
-  return RT_OK;
-}
-
-// The rest pose posed by the matrices at d_xforms12 (device memory of the lead device) into the staging scene, on s, and
-// from there into the context as a device update: the check runs on the staging scene, before anything live is written
-static int pose_from_device(rt_ctx* c, const void* d_xforms12, uint32_t flags, hipStream_t s) {
-  rt_ctx* L = lead_ctx(c);
-  HIP_TRY(hipSetDevice(L->device));
-  const size_t nb = (size_t)L->cap * sizeof(float4);
-  int rc = ensure_bytes(&L->pose_verts, 3 * nb);
-  if (rc == RT_OK) rc = ensure_bytes(&L->pose_normals, nb);
-  if (rc != RT_OK) return rc;
-  // the staging scene may still be the source of the previous pose's copies, on whichever streams they run
-  for (rt_ctx* k : device_ctxs(c)) HIP_TRY(wait_scene(k, s));
-  launch_pose(L->d_rest_verts, L->d_rest_normals, L->d_object_of, (const float*)d_xforms12, L->n, (float4*)L->pose_verts.p,
-              (float4*)L->pose_normals.p, s);
-  HIP_TRY(hipGetLastError());
-  SceneSummary sum;
-  rc = device_check(c, L->pose_verts.p, L->d_colors, L->n, s, &sum);
-  if (rc != RT_OK) return rc;
-  return update_from_device(c, L->pose_verts.p, L->pose_normals.p, nullptr, L->n, flags, s, sum);
-}
-
-extern "C" {
-
-int rt_set_objects(rt_ctx* c, const int32_t* first, const int32_t* count, int32_t nobj) {
-  if (!c) { set_error("rt_set_objects: NULL context"); return RT_E_INVALID; }
-  if (nobj < 0 || nobj > (int32_t)kPoseStatic) { set_error("rt_set_objects: nobj = %d outside [0, 65535]", nobj); return RT_E_INVALID; }
-  if (nobj > 0 && (!first || !count)) { set_error("rt_set_objects: first / count is NULL"); return RT_E_INVALID; }
-  if (nobj == 0) { drop_objects(c); return RT_OK; }
-  rt_ctx* L = lead_ctx(c);
-  const int n = L->n;
-  std::vector<unsigned short> object_of((size_t)n, (unsigned short)kPoseStatic);
-  for (int k = 0; k < nobj; ++k) {
-    const int f = first[k], cnt = count[k];
-    if (cnt < 1 || f < 0 || f >= n || cnt > n - f) {
-      set_error("rt_set_objects: object %d = [%d, %d + %d) is empty or not inside the context's %d triangles", k, f, f, cnt, n);
-      return RT_E_INVALID;
-    }
-    for (int i = f; i < f + cnt; ++i) {
-      if (object_of[(size_t)i] != kPoseStatic) {
-        set_error("rt_set_objects: objects %d and %d overlap at triangle %d", (int)object_of[(size_t)i], k, i); return RT_E_INVALID;
-      }
-      object_of[(size_t)i] = (unsigned short)k;
-    }
-  }
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(L->device));
-  const size_t nb = (size_t)n * sizeof(float4);
-  if (!L->d_rest_verts &&      // (a table in force has buffers of this n: whatever changes n drops the table)
-      (hipMalloc(&L->d_rest_verts, 3 * nb) != hipSuccess || hipMalloc(&L->d_rest_normals, nb) != hipSuccess ||
-       hipMalloc(&L->d_object_of, (size_t)n * sizeof(unsigned short)) != hipSuccess)) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
-    drop_objects(c);
-    return RT_E_NOMEM;
-  }
-  // the snapshot waits for whatever still writes the scene, and a pose still reading the old rest pose (an update's event)
-  int rc = update_begin(L, L->stream);
-  if (rc == RT_OK &&
-      (hipMemcpyAsync(L->d_rest_verts, L->d_verts, 3 * nb, hipMemcpyDeviceToDevice, L->stream) != hipSuccess ||
-       hipMemcpyAsync(L->d_rest_normals, L->d_normals, nb, hipMemcpyDeviceToDevice, L->stream) != hipSuccess ||
-       hipMemcpyAsync(L->d_object_of, object_of.data(), (size_t)n * sizeof(unsigned short), hipMemcpyHostToDevice, L->stream) != hipSuccess ||
-       hipStreamSynchronize(L->stream) != hipSuccess)) {
-    set_error("rt_set_objects: snapshot failed: %s", hipGetErrorString(hipGetLastError())); rc = RT_E_DEVICE;
-  }
-  if (rc != RT_OK) { const std::string msg = g_last_error; drop_objects(c); g_last_error = msg; return rc; }
-  L->nobj = nobj;
-  return RT_OK;
-}
-
-int rt_pose_objects(rt_ctx* c, const float* xforms12, uint32_t flags) {
-  int rc = check_pose_args(c, xforms12, flags, "rt_pose_objects");
-  if (rc != RT_OK) return rc;
-  rt_ctx* L = lead_ctx(c);
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(L->device));
-  const size_t bytes = (size_t)L->nobj * 12 * sizeof(float);
-  rc = ensure_bytes(&L->pose_xforms, bytes);     // (only this blocking entry uses the buffer: nothing can still be reading it)
-  if (rc != RT_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(L->pose_xforms.p, xforms12, bytes, hipMemcpyHostToDevice, c->stream));
-  rc = pose_from_device(c, L->pose_xforms.p, flags, c->stream);
-  if (rc != RT_OK) { const std::string msg = g_last_error; hipStreamSynchronize(c->stream); (void)hipGetLastError(); g_last_error = msg; return rc; }
-  HIP_TRY(hipStreamSynchronize(c->stream));      // (the stream of a multi-device handle has waited for every device)
-  return RT_OK;
-}
-
-int rt_pose_objects_device(rt_ctx* c, const void* d_xforms12, uint32_t flags, void* hip_stream) {
-  const int rc = check_pose_args(c, d_xforms12, flags, "rt_pose_objects_device");
-  if (rc != RT_OK) return rc;
-  DeviceGuard guard;
-  return pose_from_device(c, d_xforms12, flags, (hipStream_t)hip_stream);
-}
-
-int rt_debug_object_count(rt_ctx* c, int32_t* out) {
-  if (!c || !out) { set_error("rt_debug_object_count: NULL argument"); return RT_E_INVALID; }
-  *out = lead_ctx(c)->nobj;
-  return RT_OK;
-}
-
-int rt_update_scene(rt_ctx* c, const float* vertices4, const float* normals4, const float* colors4, int32_t n, uint32_t flags) {
-  int rc = check_update_args(c, vertices4, normals4, colors4, n, flags);
-  if (rc != RT_OK) return rc;
-  rc = validate_vertices(vertices4, n);        // once, before any device is touched
-  if (rc != RT_OK) return rc;
-  if (n == 0) return RT_OK;
-  SceneSummary sum;
-  sum.n_shadow = count_shadow_casters(colors4, n);
-  vertex_box(vertices4, n, sum.lo, sum.hi);
-  DeviceGuard guard;
-  drop_objects(c);                             // the scene behind the rest pose changes
-  return update_host_all(c, vertices4, normals4, colors4, n, flags, sum);
-}
-
-int rt_update_scene_device(rt_ctx* c, const void* d_vertices4, const void* d_normals4, const void* d_colors4, int32_t n,
-                           uint32_t flags, void* hip_stream) {
-  int rc = check_update_args(c, d_vertices4, d_normals4, d_colors4, n, flags);
-  if (rc != RT_OK) return rc;
-  if (n == 0) return RT_OK;
-  DeviceGuard guard;
-  const hipStream_t s = (hipStream_t)hip_stream;
-  // first pass: check the bound and reduce n_shadow and the box; the live buffers stay untouched until it has passed
-  SceneSummary sum;
-  rc = device_check(c, d_vertices4, d_colors4, n, s, &sum);
-  if (rc != RT_OK) return rc;
-  drop_objects(c);
-  return update_from_device(c, d_vertices4, d_normals4, d_colors4, n, flags, s, sum);
-}
-
-int rt_replace_scene(rt_ctx* c, const float* vertices4, const float* normals4, const float* colors4, int32_t n_new, uint32_t flags) {
-  int rc = check_replace_args(c, vertices4, normals4, colors4, n_new, flags);
-  if (rc != RT_OK) return rc;
-  rc = validate_vertices(vertices4, n_new);    // once, before any device is touched
-  if (rc != RT_OK) return rc;
-  SceneSummary sum;
-  sum.n_shadow = count_shadow_casters(colors4, n_new);
-  vertex_box(vertices4, n_new, sum.lo, sum.hi);
-  DeviceGuard guard;
-  drop_objects(c);
-  return replace_host_all(c, vertices4, normals4, colors4, n_new, flags, sum);
-}
-
-int rt_replace_scene_device(rt_ctx* c, const void* d_vertices4, const void* d_normals4, const void* d_colors4, int32_t n_new,
-                            uint32_t flags, void* hip_stream) {
-  int rc = check_replace_args(c, d_vertices4, d_normals4, d_colors4, n_new, flags);
-  if (rc != RT_OK) return rc;
-  DeviceGuard guard;
-  const hipStream_t s = (hipStream_t)hip_stream;
-  SceneSummary sum;
-  rc = device_check(c, d_vertices4, d_colors4, n_new, s, &sum);
-  if (rc != RT_OK) return rc;
-  drop_objects(c);
-  if (flags & RT_UPDATE_REORDER) {             // host tiles (kd or Morton by the context's tuning): through the host
-    HostScene h;
-    rc = stage_to_host(d_vertices4, d_normals4, d_colors4, n_new, s, &h);
-    if (rc != RT_OK) return rc;
-    return replace_host_all(c, h.v.data(), h.nr.data(), h.col.data(), n_new, flags, sum);
-  }
-  rc = scene_reserve_all(c, n_new, true);
-  if (rc != RT_OK) return rc;
-  rc = scene_device_all(c, d_vertices4, d_normals4, d_colors4, n_new, flags, s, sum, true);
-  parent_follows(c);
-  return rc;
-}
-
-int rt_update_spheres(rt_ctx* c, const rt_sphere* spheres, int32_t num_spheres) {
-  if (!c) { set_error("rt_update_spheres: NULL context"); return RT_E_INVALID; }
-  if (num_spheres < 0 || num_spheres > RT_MAX_SPHERES) { set_error("rt_update_spheres: num_spheres must be in [0,%d]", RT_MAX_SPHERES); return RT_E_INVALID; }
-  if (num_spheres > 0 && !spheres) { set_error("rt_update_spheres: spheres is NULL"); return RT_E_INVALID; }
-  if (validate_spheres(spheres, num_spheres) != RT_OK) return RT_E_INVALID;
-  DeviceGuard guard;
-  auto set_cfg = [&](rt_ctx* k) {
-    k->cfg.num_spheres = num_spheres;
-    memset(k->cfg.spheres, 0, sizeof k->cfg.spheres);
-    for (int i = 0; i < num_spheres; ++i) k->cfg.spheres[i] = spheres[i];
-  };
-  if (!c->kids.empty()) set_cfg(c);
-  for (rt_ctx* k : device_ctxs(c)) {
-    // the table is read by frames, readers and AOV passes: all of them first (a scene update), then a blocking copy
-    const int rc = update_begin(k, k->stream);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(k->stream));
-    set_cfg(k);                                 // fill_params reads FrameParams::sph, nsph and the world grid's growth from it
-    const int rc2 = upload_spheres(k);
-    if (rc2 != RT_OK) return rc2;
-    if (k->d_screen_masks) set_scene_box(k, k->vbox_lo, k->vbox_hi);   // the world grid spans the spheres too
-  }
-  return RT_OK;
-}
-
-int rt_debug_scene_capacity(rt_ctx* c, int64_t* out_triangles) {
-  if (!c || !out_triangles) { set_error("rt_debug_scene_capacity: NULL argument"); return RT_E_INVALID; }
-  *out_triangles = (int64_t)lead_ctx(c)->cap;
-  return RT_OK;
-}
-
-int rt_debug_tile_data(rt_ctx* c, int32_t* orig, float* tiles, int32_t cap_tiles) {
-  if (!c || cap_tiles < 0 || (cap_tiles > 0 && (!orig || !tiles))) { set_error("NULL argument"); return RT_E_INVALID; }
-  c = lead_ctx(c);
-  if (!c->d_tile_box) { set_error("rt_debug_tile_data: this context keeps no tiled copy of the scene"); return RT_E_UNSUPPORTED; }
-  const int ntiles = mesh_tiles(c->n);
-  if (cap_tiles == 0) return ntiles;
-  if (cap_tiles < ntiles) { set_error("rt_debug_tile_data: room for %d tiles, %d needed", cap_tiles, ntiles); return RT_E_INVALID; }
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(wait_scene(c, c->stream));
-  HIP_TRY(hipMemcpyAsync(orig, c->d_orig, (size_t)c->n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(tiles, c->d_tile_box, (size_t)ntiles * 3 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return ntiles;
-}
-
-}  // extern "C"
-
 // ---- several devices --------------------------------------------------------------------------------------
 // Child k of a parent with N children owns the bands k, k+N, ... of `dbr` rows; its stripe holds them packed.
 // band_copy_plan lists the copies that put them into image order at the destination (row pitch W elements of `elem`
@@ -1238,11 +513,10 @@ static int parent_render(rt_ctx* p, const float rot[12], const float cam[3], con
   std::vector<char> launched(nk, 0), direct(nk, 0);
   // On an error the devices already launched may still be writing into the caller's buffers: wait for them before returning
   auto fail = [&](int rc) {
-    const std::string msg = g_last_error;
+    KeepError keep;
     for (size_t k = 0; k < nk; ++k)
       if (launched[k]) { hipSetDevice(p->kids[k]->device); hipStreamSynchronize(p->kids[k]->stream); }
     (void)hipGetLastError();
-    g_last_error = msg;
     return rc;
   };
   // pass 1: every device's frame is launched before any band is delivered.  (Delivering inside this loop made the host

@@ -1,9 +1,10 @@
 // rt_host.h — what the host side of the library shares: the context, the error text, and the prototypes of the host
-// functions that the kernel files define.  Included by the API files (rt_api.hip, rt_calls.hip, rt_tile_sort.hip) AND by
+// functions that the kernel files define.  Included by the API files (rt_api.hip, rt_scene.hip, rt_calls.hip, rt_tile_sort.hip) AND by
 // the kernel files that define launch_* and friends, so the compiler checks every prototype against its definition.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <string>
 #include <vector>
 
 #include "rt_device.h"
@@ -20,6 +21,15 @@
 namespace uobrt {
 
 void set_error(const char* fmt, ...);      // the text behind rt_last_error (rt_api.hip)
+
+// Keeps the calling thread's error text across clean-up calls that may set their own: taken here, put back when the scope ends
+struct KeepError {
+  std::string text;
+  KeepError();
+  ~KeepError();
+};
+
+constexpr int kWorldGrid = 32;             // world cells per axis of the mesh kernel's shadow-ray tile masks
 
 // rt_kernel_generic.hip
 void launch_generic(const FrameParams& P, bool count, hipStream_t stream);
@@ -226,9 +236,14 @@ inline int wait_scene_readers(const rt_ctx* c, hipStream_t s) {
   return RT_OK;
 }
 
-// rt_api.hip
+// rt_api.hip: what a frame's kernels are given, and the same for what looks at the scene only
 void fill_params(const rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal, FrameParams* P);
 void use_tiled_scene(const rt_ctx* c, FrameParams* P);
 void scene_params(const rt_ctx* c, const float light[3], bool tiled, FrameParams* P);
+// rt_scene.hip: what rt_init needs of the scene — the bounds of its arguments, the sphere table, the first scene
+int validate_spheres(const rt_sphere* sph, int num);
+int validate_vertices(const float* vertices4, int n);
+int upload_spheres(rt_ctx* c);
+int scene_first(rt_ctx* c, const float* v4, const float* n4, const float* c4, int n);
 
 }  // namespace uobrt

@@ -33,7 +33,7 @@ static uint32_t spread3(uint32_t v) {
 // — so the triangles are sorted into spatially compact tiles of 64: a task's rays then meet few tiles.  Triangles whose
 // extent exceeds a quarter of the scene's (walls) come first, the rest in Morton order of their centroids.
 // Three parts, shared by rt_init and rt_update_scene(RT_UPDATE_REORDER): the order (tiled_order), the per-tile data for an
-// order (tile_data_host; rt_scene_update.hip's refit computes the same floats on the device) and the upload (rt_api.hip upload_tiled).
+// order (tile_data_host; rt_scene_update.hip's refit computes the same floats on the device) and the upload (rt_scene.hip upload_tiled).
 // Returns orig: orig[j] = original index of the triangle at tiled position j.
 std::vector<int> tiled_order(const float* v4, int n, bool morton) {
   float lo[3], hi[3];
