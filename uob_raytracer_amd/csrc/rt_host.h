@@ -85,6 +85,16 @@ std::vector<float> tile_data_host(const float* v4, const int* orig, int n);
 // ceil(2^32 / d): the magic number of rt_device.h div_magic (0 stands for d == 1)
 inline uint32_t div_magic_for(int d) { return d > 1 ? (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d) : 0u; }
 
+// Resident workgroups per CU of `kernel` launched with `threads` per workgroup and its static LDS (a persistent grid), asked
+// of the current device at every launch: nothing is cached across contexts, devices or threads
+inline int blocks_per_cu(const void* kernel, int threads) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+  return per_cu;
+}
+// The workgroups of a grid that has work for `want` and room for `cap`: never none
+inline unsigned grid_blocks(long want, long cap) { return (unsigned)(want < cap ? (want > 0 ? want : 1) : cap); }
+
 // Tuning knobs, read from the environment ONCE per context (rt_init); 0 / false = the built-in choice
 struct Tuning {
   int job_tasks = 0;          // UOB_RT_JOB_TASKS: 64-ray tasks per job of the wave kernel

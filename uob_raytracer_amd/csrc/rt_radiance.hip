@@ -4,7 +4,7 @@
 // diffuse surface reached, bit for bit.  Two kernels on one stream, no host round trip between them:
 //   A. rt_radiance_trace, lane = ray.  Persistent waves pull runs of 64-ray groups from a queue head behind the counters.
 //      The first hit is tile_walk<false> (rt_tiles.h, the walk of rt_trace_rays' closest-hit queries; BOXES = false for
-//      contexts without a tiled copy) finished from the scene arrays, then closest_spheres.  The bounce loop is wave-wide:
+//      contexts without a tiled copy) finished from the scene arrays (finish_hit), then closest_spheres.  The bounce loop is wave-wide:
 //      while any lane is on a mirror or glass surface and b < max_bounces, those lanes take reflect_ray / refract_ray
 //      (rt_trace.h; the medium is carried in the lane's ray) and the wave walks again with only them active — the walk is
 //      one call site inside the loop, iteration 0 being the caller's ray.  A ray that ends black (miss, or the loop ran
@@ -16,6 +16,8 @@
 //      device memory.  The record's first lane turns the light L into the colour, albedo * (0.5f + L) for a first hit and
 //      (0.9f * (0.5f + L)) * albedo behind a bounce, and stores out_rgba4[ray index] itself.  A record whose term is 0 is not
 //      traced: its light is +0 whatever its samples see, so the skip changes no bit.
+// Both kernels pop their queue with queue_pop and leave their counters through flush_counters (rt_tiles.h): stage A in its own
+// slots, stage B after renaming the three of the shade body's counters that a radiance call reports.
 // Every skip of the walks is a certificate that the reference's test cannot accept; rays outside the certificates' domain
 // (in_query_domain) — caller rays, bounce rays and sample rays alike — take every triangle.
 // Compiled with -ffp-contract=off: see rt_math.h for the numerics contract.
@@ -70,13 +72,12 @@ void rt_radiance_trace(const FrameParams P, const float* __restrict__ rays, cons
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long ngroups = (nray + 63) >> 6;
   unsigned int* const head = reinterpret_cast<unsigned int*>(stats + kRadHeadA);
-  unsigned long long n_rays = 0, n_bounces = 0, n_ctiles = 0, n_unculled = 0, n_bundle = 0;   // wave-uniform
-  unsigned long long tests = 0;                                                              // this lane's
+  unsigned long long w[RD_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};   // (RD_POINTS is added to as the records are appended, below)
+  unsigned long long n_bundle = 0;            // (the walk counts its candidate tiles; a radiance call does not report them)
+  unsigned long long tests = 0;               // this lane's
   Work wk;                                    // (the counting slot of closest_spheres<false>: never written)
   for (;;) {
-    unsigned int g0 = 0u;
-    if (lane == 0) g0 = atomicAdd(head, 1u);
-    g0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)g0);
+    const unsigned int g0 = queue_pop(head, lane);
     if ((long)g0 * run >= ngroups) break;
     for (int gr = 0; gr < run; ++gr) {
       const long g = (long)g0 * run + gr;
@@ -91,23 +92,16 @@ void rt_radiance_trace(const FrameParams P, const float* __restrict__ rays, cons
         ray.start = mk(rays[6 * k], rays[6 * k + 1], rays[6 * k + 2]);
         ray.dir = mk(rays[6 * k + 3], rays[6 * k + 4], rays[6 * k + 5]);
       }
-      n_rays += __popcll(ballot(act));
+      w[RD_RAYS] += __popcll(ballot(act));
       bool go = act;                          // the lane's ray is still to be traced
       bool emit = false, bounced = false;     // it ended on a diffuse surface (through a bounce)
       int prim = -1;                          // the first hit
       for (int it = 0;; ++it) {               // 0: the caller's ray; b + 1: bounce b of secondary_light
         TileHit h = no_hit();
         bool blocked = false;                 // (the any-hit slot of the shared walk: unused by closest hit)
-        tile_walk<false, BOXES>(P, s_tile[wave], lane, go, ray.start, ray.dir, 0.0f, h, blocked, n_unculled, n_bundle, n_ctiles, tests);
+        tile_walk<false, BOXES>(P, s_tile[wave], lane, go, ray.start, ray.dir, 0.0f, h, blocked, w[RD_UNCULLED], n_bundle, w[RD_CTILES], tests);
         if (go) {
-          if (h.best >= 0) {                  // set_hit (kernels.cl:198-201) on the arrays the walk read
-            const int j = h.best;
-            const f3 v0 = xyz(P.verts[3 * j]), e1 = xyz(P.verts[3 * j + 1]) - v0, e2 = xyz(P.verts[3 * j + 2]) - v0;
-            ray.tri = h.orig;
-            ray.P = (v0 + h.u * e1) + h.v * e2;
-            ray.N = xyz(P.normals[j]);
-            ray.col = P.colors[j];
-          }
+          finish_hit(P, h, ray);
           float current_t = h.t;
           closest_spheres<false>(P, ray, current_t, wk);
           if (it == 0) prim = ray.tri;
@@ -120,7 +114,7 @@ void rt_radiance_trace(const FrameParams P, const float* __restrict__ rays, cons
         if (it >= P.bounces) break;
         const unsigned long long gm = ballot(go);
         if (gm == 0ull) break;
-        n_bounces += __popcll(gm);
+        w[RD_BOUNCES] += __popcll(gm);
         if (go) ray = (ray.col.w == 0.0f) ? reflect_ray(ray) : refract_ray(ray);
       }
       // the rays that reached a diffuse surface: one slot each, in lane order, from one atomic per wave
@@ -143,14 +137,7 @@ void rt_radiance_trace(const FrameParams P, const float* __restrict__ rays, cons
       if (act && out_prim) out_prim[k] = prim;
     }
   }
-  const unsigned long long all_tests = wave_sum(tests);
-  if (lane == 0) {
-    if (n_rays) atomicAdd(&stats[RD_RAYS], n_rays);
-    if (n_bounces) atomicAdd(&stats[RD_BOUNCES], n_bounces);
-    if (n_ctiles) atomicAdd(&stats[RD_CTILES], n_ctiles);
-    if (all_tests) atomicAdd(&stats[RD_CTESTS], all_tests);
-    if (n_unculled) atomicAdd(&stats[RD_UNCULLED], n_unculled);
-  }
+  flush_counters(stats, w, RD_CTESTS, tests);
 }
 
 // Stage B.  P: the same, with the call's light.  The record count is stats[RD_POINTS] as stage A left it; the grid is sized
@@ -172,12 +159,10 @@ void rt_radiance_shade(const FrameParams P, const float4* __restrict__ records, 
   unsigned long long tests = 0, unculled = 0;
   const RadianceIO io{records, out_rgba};
   shade_groups<BOXES, MULTI>(P, io, npoints, stats + kRadHeadB, run, s_tile[wave], s_jump, lane, w, tests, unculled);
-  const unsigned long long all_tests = wave_sum(tests);
-  if (lane == 0) {
-    if (w[SH_RAYS]) atomicAdd(&stats[RD_SAMPLES], w[SH_RAYS]);
-    if (all_tests) atomicAdd(&stats[RD_STESTS], all_tests);
-    if (unculled) atomicAdd(&stats[RD_UNCULLED], unculled);
-  }
+  // of the shade body's counters a radiance call reports three, under its own names
+  unsigned long long r[RD_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  r[RD_SAMPLES] = w[SH_RAYS]; r[RD_UNCULLED] = unculled;
+  flush_counters(stats, r, RD_STESTS, tests);
 }
 
 template __global__ void rt_radiance_trace<false>(const FrameParams, const float*, const int*, long, float4*, int*, float4*, unsigned long long*, int);
@@ -202,18 +187,16 @@ void launch_radiance(const FrameParams& P, bool tiled, const float* d_rays6, con
                             : (multi ? &rt_radiance_shade<false, true> : &rt_radiance_shade<false, false>);
   {
     const long ngroups = (nray + 63) / 64;
-    const long want = (ngroups + kShadeWaves - 1) / kShadeWaves;
-    const long full = (long)cus * shade_blocks_per_cu(reinterpret_cast<const void*>(trace));
-    const dim3 grid((unsigned)(want < full ? want : full));
+    const dim3 grid(grid_blocks((ngroups + kShadeWaves - 1) / kShadeWaves,
+                                (long)cus * blocks_per_cu(reinterpret_cast<const void*>(trace), 64 * kShadeWaves)));
     const int run = shade_run(ngroups, (long)grid.x * kShadeWaves, tiled);
     hipLaunchKernelGGL(trace, grid, dim3(64 * kShadeWaves), 0, stream, P, d_rays6, d_seeds, nray, d_rgba, d_prim, d_records, stats, run);
   }
   {
     const int ppw = multi ? 1 : 64 / P.S;
     const long ngroups = (nray + ppw - 1) / ppw;                  // (at most: every ray a record)
-    const long want = (ngroups + kShadeWaves - 1) / kShadeWaves;
-    const long full = (long)cus * shade_blocks_per_cu(reinterpret_cast<const void*>(shade));
-    const dim3 grid((unsigned)(want < full ? want : full));
+    const dim3 grid(grid_blocks((ngroups + kShadeWaves - 1) / kShadeWaves,
+                                (long)cus * blocks_per_cu(reinterpret_cast<const void*>(shade), 64 * kShadeWaves)));
     hipLaunchKernelGGL(shade, grid, dim3(64 * kShadeWaves), 0, stream, P, d_records, d_rgba, stats);
   }
 }

@@ -5,12 +5,15 @@
 // Contexts without a tiled copy (n <= 64, RT_FLAG_GENERIC_KERNEL): rt_query_flat, one lane per ray over the whole scene
 // in original order, the scene staged in LDS once per workgroup (or, beyond one LDS stage, the query's own records).
 // Tiled contexts (n > 64): rt_query_tiled, persistent waves, 64 consecutive rays per wave:
-//   1.-3. tile_walk (rt_tiles.h, shared with rt_shade.hip): the bundle bound per tile, the per-lane tile certificate, the
+//   1.-3. tile_walk (rt_tiles.h, shared with rt_shade.hip, rt_radiance.hip and rt_aov.hip): the bundle bound per tile (the
+//      walk's default candidate policy, BundleCandidates), the per-lane tile certificate, the
 //      tile's records in the wave's LDS with lane = triangle bounding the bundle (task_bound; on curved meshes the tiles'
 //      normal cones are wide, and this is where most of the work goes away) and lane = ray testing the survivors with the
 //      reference's arithmetic: closest hit carried across tiles with the original-order tie rule (closer), shadow any-hit
 //      with an early exit per lane and per wave;
-//   4. the hit is finished from the tiled arrays (set_hit arithmetic), then the spheres (closest_spheres / shadow_spheres).
+//   4. the hit is finished from the tiled arrays (finish_hit: set_hit arithmetic), then the spheres (closest_spheres /
+//      shadow_spheres).
+// The queue pop (queue_pop) and the counter flush (flush_counters) are rt_tiles.h's too, as for every kernel beside the frame.
 // Every skip is a certificate that the reference's test cannot accept, so skipping changes no bit.  The certificates are
 // verified for |start| <= 2^16 and 2^-20 <= max |direction component| <= 2^16 (finite); a ray outside that domain
 // needs every tile and every triangle, i.e. it gets the brute-force answer by construction.
@@ -28,17 +31,6 @@ namespace {
 constexpr int kQueryWaves = 4;              // waves per workgroup of rt_query_tiled (independent: no barriers between them)
 // Work counters of a query (rt_debug_trace_stats), then the tiled kernel's queue head
 enum { Q_RAYS, Q_WAVES, Q_TILES, Q_BUNDLE_TILES, Q_TESTED_TILES, Q_TRI_TESTS, Q_UNCULLED, Q_SLOTS = 8 };
-
-// One atomic add per counter and wave, at its exit (all lanes active)
-__device__ __forceinline__ void flush_stats(unsigned long long* stats, const unsigned long long (&w)[Q_SLOTS], unsigned long long lane_tests) {
-  const unsigned long long tests = wave_sum(lane_tests);
-  if ((threadIdx.x & 63) == 0) {
-    for (int q = 0; q < Q_SLOTS; ++q) {
-      const unsigned long long v = q == Q_TRI_TESTS ? tests : w[q];
-      if (v) atomicAdd(&stats[q], v);
-    }
-  }
-}
 
 __device__ __forceinline__ void store_hit(float* out10, long k, const Ray& ray) {
   float* o = out10 + 10 * k;
@@ -90,7 +82,7 @@ __global__ __launch_bounds__(256) void rt_query_flat(const FrameParams P, const 
       if (out10) store_hit(out10, k, ray);
     }
   }
-  flush_stats(stats, w, wk.v[W_STRI]);
+  flush_counters(stats, w, Q_TRI_TESTS, wk.v[W_STRI]);
 }
 
 // Tiled contexts (P = the tiled copy: verts / normals / colors / orig / tile_box of use_tiled_scene).  Persistent waves pull
@@ -109,9 +101,7 @@ void rt_query_tiled(const FrameParams P, const float* __restrict__ rays, const f
   unsigned long long tests = 0;
   Work wk;
   for (;;) {
-    unsigned int g = 0u;
-    if (lane == 0) g = atomicAdd(head, 1u);
-    g = (unsigned int)__builtin_amdgcn_readfirstlane((int)g);
+    const unsigned int g = queue_pop(head, lane);
     if ((long)g >= ngroups) break;
     const long k = (long)g * 64 + lane;
     const bool act = k < nray;
@@ -131,14 +121,7 @@ void rt_query_tiled(const FrameParams P, const float* __restrict__ rays, const f
         out_tri[k] = (blocked || shadow_spheres<false>(P, o, d, rsq, wk)) ? 1 : 0;
       } else {
         Ray ray = query_ray(o, d);
-        if (h.best >= 0) {                        // set_hit (kernels.cl:198-201) on the tiled arrays
-          const int j = h.best;
-          const f3 v0 = xyz(P.verts[3 * j]), e1 = xyz(P.verts[3 * j + 1]) - v0, e2 = xyz(P.verts[3 * j + 2]) - v0;
-          ray.tri = h.orig;
-          ray.P = (v0 + h.u * e1) + h.v * e2;
-          ray.N = xyz(P.normals[j]);
-          ray.col = P.colors[j];
-        }
+        finish_hit(P, h, ray);
         float current_t = h.t;
         closest_spheres<false>(P, ray, current_t, wk);
         out_tri[k] = ray.tri;
@@ -146,7 +129,7 @@ void rt_query_tiled(const FrameParams P, const float* __restrict__ rays, const f
       }
     }
   }
-  flush_stats(stats, w, tests);
+  flush_counters(stats, w, Q_TRI_TESTS, tests);
 }
 
 template __global__ void rt_query_flat<false, false>(const FrameParams, const float*, const float*, long, int*, float*, unsigned long long*);
@@ -162,33 +145,23 @@ int query_stats_words() { return Q_SLOTS + 1; }
 // must already hold the query's staged records.  stats: query_stats_words() zeroed 64-bit words.
 void launch_query(const FrameParams& P, bool tiled, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
                   float* d_out10, unsigned long long* stats, int cus, hipStream_t stream) {
+  typedef void (*Kernel)(const FrameParams, const float*, const float*, long, int*, float*, unsigned long long*);
   const bool shadow = what == RT_TRACE_IN_SHADOW;
   if (tiled) {
-    static int per_cu = 0;                      // resident workgroups per CU (the persistent grid)
-    if (per_cu == 0) {
-      int a = 0, b = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, reinterpret_cast<const void*>(&rt_query_tiled<false>), 64 * kQueryWaves, 0) != hipSuccess) a = 2;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, reinterpret_cast<const void*>(&rt_query_tiled<true>), 64 * kQueryWaves, 0) != hipSuccess) b = 2;
-      per_cu = std::max(1, std::min(a, b));
-    }
-    const long want = ((nray + 63) / 64 + kQueryWaves - 1) / kQueryWaves;
-    const long full = (long)cus * per_cu;
-    const dim3 grid((unsigned)(want < full ? want : full));
-    if (shadow) hipLaunchKernelGGL((rt_query_tiled<true>), grid, dim3(64 * kQueryWaves), 0, stream, P, d_rays, d_r2, nray, d_tri, d_out10, stats);
-    else hipLaunchKernelGGL((rt_query_tiled<false>), grid, dim3(64 * kQueryWaves), 0, stream, P, d_rays, d_r2, nray, d_tri, d_out10, stats);
+    // (the persistent grid: the resident workgroups of whichever instantiation holds fewer, so a context's closest-hit and
+    // in-shadow queries run on grids of one size)
+    const int per_cu = std::min(blocks_per_cu(reinterpret_cast<const void*>(&rt_query_tiled<false>), 64 * kQueryWaves),
+                                blocks_per_cu(reinterpret_cast<const void*>(&rt_query_tiled<true>), 64 * kQueryWaves));
+    const Kernel kernel = shadow ? &rt_query_tiled<true> : &rt_query_tiled<false>;
+    const dim3 grid(grid_blocks(((nray + 63) / 64 + kQueryWaves - 1) / kQueryWaves, (long)cus * per_cu));
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * kQueryWaves), 0, stream, P, d_rays, d_r2, nray, d_tri, d_out10, stats);
     return;
   }
-  const long blocks = (nray + 255) / 256;
-  const dim3 grid((unsigned)(blocks < 4096 ? (blocks > 0 ? blocks : 1) : 4096));
   const bool big = P.n > kLdsMaxTriangles;
+  const Kernel kernel = shadow ? (big ? &rt_query_flat<true, true> : &rt_query_flat<true, false>)
+                               : (big ? &rt_query_flat<false, true> : &rt_query_flat<false, false>);
   const size_t lds = big ? 0 : (size_t)P.n * kLdsRecords * sizeof(float4);
-  if (shadow) {
-    if (big) hipLaunchKernelGGL((rt_query_flat<true, true>), grid, dim3(256), 0, stream, P, d_rays, d_r2, nray, d_tri, d_out10, stats);
-    else hipLaunchKernelGGL((rt_query_flat<true, false>), grid, dim3(256), lds, stream, P, d_rays, d_r2, nray, d_tri, d_out10, stats);
-  } else {
-    if (big) hipLaunchKernelGGL((rt_query_flat<false, true>), grid, dim3(256), 0, stream, P, d_rays, d_r2, nray, d_tri, d_out10, stats);
-    else hipLaunchKernelGGL((rt_query_flat<false, false>), grid, dim3(256), lds, stream, P, d_rays, d_r2, nray, d_tri, d_out10, stats);
-  }
+  hipLaunchKernelGGL(kernel, dim3(grid_blocks((nray + 255) / 256, 4096)), dim3(256), lds, stream, P, d_rays, d_r2, nray, d_tri, d_out10, stats);
 }
 
 }  // namespace uobrt

@@ -2,7 +2,8 @@
 // one channel of the reference's direct_light (kernels.cl:313-340) for a point (intersect, intersect_normal) and the
 // global_id that seeds its jitter stream, with the context's shadow_samples and light_spread, bit for bit.
 //
-// Persistent waves pull runs of groups of whole points from a queue head behind the counters (`run` consecutive groups per
+// Persistent waves pull runs of groups of whole points from a queue head behind the counters (queue_pop, rt_tiles.h; the
+// counters leave through flush_counters, the grid is sized by blocks_per_cu and grid_blocks, rt_host.h; `run` consecutive groups per
 // hand-out: a returning atomic on one word serves ~90 waves per microsecond, 2^20 single hand-outs alone would take 12 ms).
 // lane = (point, sample): with S < 64 a wave takes floor(64 / S) points and the lanes beyond them idle (MULTI = false); with
 // S >= 64 a wave holds one point, which takes ceil(S / 64) passes, and the counts accumulate (MULTI = true, held at 5 waves
@@ -68,12 +69,7 @@ void rt_shade(const FrameParams P, const float* __restrict__ points6,
   const ShadePointsIO io{points6, seeds, out_light, out_cnt};
   shade_groups<BOXES, MULTI>(P, io, npoints, stats + SH_SLOTS, run, s_tile[wave], s_jump, lane, w,
                              tests, unculled);
-  const unsigned long long all_tests = wave_sum(tests);
-  if (lane == 0) {
-    w[SH_TRI_TESTS] = all_tests;
-    for (int q = 0; q < SH_SLOTS; ++q)
-      if (w[q]) atomicAdd(&stats[q], w[q]);
-  }
+  flush_counters(stats, w, SH_TRI_TESTS, tests);
 }
 
 template __global__ void rt_shade<false, false>(const FrameParams, const float*, const int*, long, float*, int*, unsigned long long*, int);
@@ -89,12 +85,10 @@ void launch_shade(const FrameParams& P, bool tiled, const float* d_points6, cons
   const bool multi = P.S >= 64;
   const Kernel kernel = tiled ? (multi ? &rt_shade<true, true> : &rt_shade<true, false>)
                               : (multi ? &rt_shade<false, true> : &rt_shade<false, false>);
-  const int per_cu = shade_blocks_per_cu(reinterpret_cast<const void*>(kernel));
   const int ppw = multi ? 1 : 64 / P.S;
   const long ngroups = (npoints + ppw - 1) / ppw;
-  const long want = (ngroups + kShadeWaves - 1) / kShadeWaves;
-  const long full = (long)cus * per_cu;
-  const dim3 grid((unsigned)(want < full ? want : full));
+  const dim3 grid(grid_blocks((ngroups + kShadeWaves - 1) / kShadeWaves,
+                              (long)cus * blocks_per_cu(reinterpret_cast<const void*>(kernel), 64 * kShadeWaves)));
   const int run = shade_run(ngroups, (long)grid.x * kShadeWaves, tiled);
   hipLaunchKernelGGL(kernel, grid, dim3(64 * kShadeWaves), 0, stream, P, d_points6, d_seeds, npoints, d_light, d_cnt, stats, run);
 }

@@ -72,9 +72,7 @@ __device__ __forceinline__ void shade_groups(const FrameParams& P, const IO& io,
   unsigned int* const head = reinterpret_cast<unsigned int*>(queue);
   Work wk;                                    // (the counting slot of shadow_spheres<false>: never written)
   for (;;) {
-    unsigned int g0 = 0u;
-    if (lane == 0) g0 = atomicAdd(head, 1u);
-    g0 = (unsigned int)__builtin_amdgcn_readfirstlane((int)g0);
+    const unsigned int g0 = queue_pop(head, lane);
     if ((long)g0 * run >= ngroups) break;
     for (int gr = 0; gr < run; ++gr) {
       const long g = (long)g0 * run + gr;
@@ -126,14 +124,6 @@ __device__ __forceinline__ void shade_groups(const FrameParams& P, const IO& io,
       }
     }
   }
-}
-
-// Resident workgroups per CU of a shade-shaped kernel (the persistent grid), asked of the current device at every launch:
-// nothing is cached across contexts, devices or threads
-inline int shade_blocks_per_cu(const void* kernel) {
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64 * kShadeWaves, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-  return per_cu;
 }
 
 // Groups per hand-out, up to 32: a wave gets about 16 hand-outs without a tiled copy, where the groups cost much the same,

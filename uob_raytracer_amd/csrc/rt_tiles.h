@@ -1,5 +1,9 @@
-// rt_tiles.h — the exact tile certificate and the closest-hit tie rule of the tiled mesh copy, shared by the mesh kernel
-// (rt_kernel_mesh.hip, bounce rays), the ray queries (rt_ray_query.hip), rt_shade_points (rt_shade.hip) and the AOV pass (rt_aov.hip).  Include after rt_wave_common.h.
+// rt_tiles.h — what the kernels share of the tiled mesh copy (rt_scene.hip upload_tiled_scene).  The exact tile certificate and the
+// closest-hit tie rule: the mesh kernel (rt_kernel_mesh.hip, bounce rays) and every kernel of the calls beside the frame.
+// For those kernels — the ray queries (rt_ray_query.hip), rt_shade_points (rt_shade.hip, rt_shade_body.h), rt_radiance_rays
+// (rt_radiance.hip) and the AOV pass (rt_aov.hip) — also the ONE tiled walk (tile_walk; where a pass's candidate tiles come
+// from is a policy), the hit finisher (finish_hit), the pop of a persistent kernel's queue (queue_pop) and the flush of a
+// wave's work counters (flush_counters).  Include after rt_wave_common.h.
 #pragma once
 #include "rt_wave_common.h"
 
@@ -23,7 +27,7 @@ namespace {
 //   det(A) = sum W_i and, for in-plane g, sum W_i g.(v_i - o) = det(A0) g.d.  Per tile the normals lie in a cone (unit axis a,
 //   chord chi = max |n_T -+ a|), so theta >= max(|a . d| / |d|, |a . (o - v)| / bmax) - chi, bounded over the bundle and the box.
 //   Certified clear iff  gap > 0  and  theta >= 150 eps (4 + 6 rad / gap) (bmax + emax) eta   (factor of safety 2 included),
-//   eta = max |e| / |e1 x e2| and emax = max |e| over the tile's triangles (rt_api.hip upload_tiled_scene).
+//   eta = max |e| / |e1 x e2| and emax = max |e| over the tile's triangles (rt_tile_sort.hip tile_data_host, uploaded by rt_scene.hip upload_tiled_scene).
 // Bundle: origins s0 +- es, directions D0 +- ed per component, |d|_2 <= dmax2.  Conservative in every term; `false` = visit.
 __device__ __forceinline__ bool tile_clear_for_bundle(const float4* __restrict__ tb, f3 s0, f3 D0, float es, float ed, float dmax2) {
   const float4 lo4 = tb[0], hi4 = tb[1], ax4 = tb[2];
@@ -66,7 +70,7 @@ __device__ __forceinline__ bool closer(float t, int orig, const TileHit& h) {
   return t < h.t || (t == h.t && h.best >= 0 && orig < h.orig);
 }
 
-// ---- shared by the ray queries (rt_ray_query.hip) and the AOV pass (rt_aov.hip) -----------------------------------------
+// ---- shared by the kernels of the calls beside the frame: ray queries, shade, radiance, AOV ---------------------------------
 // The domain over which the exact certificates hold: finite, |start| <= 2^16, 2^-20 <= max |direction component| <= 2^16
 __device__ __forceinline__ bool in_query_domain(f3 o, f3 d) {
   const bool fin = fabsf(o.x) <= kMaxCoordinate && fabsf(o.y) <= kMaxCoordinate && fabsf(o.z) <= kMaxCoordinate &&
@@ -79,28 +83,76 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
   return v;
 }
 
-// ---- the tiled walk of caller rays, shared by the ray queries (rt_ray_query.hip) and rt_shade_points (rt_shade.hip) ----
-constexpr int kQTile = 64;                  // triangles per tile of the tiled copy (rt_kernel_mesh.hip kTile)
+// A persistent wave takes the next ticket of its kernel's queue: one returning atomic by lane 0, the ticket wave-uniform.
+// What a ticket stands for (a group, a run of groups) and where the queue ends is the caller's.
+__device__ __forceinline__ unsigned int queue_pop(unsigned int* head, int lane) {
+  unsigned int g = 0u;
+  if (lane == 0) g = atomicAdd(head, 1u);
+  return (unsigned int)__builtin_amdgcn_readfirstlane((int)g);
+}
+
+// A wave's work counters into the call's, at the wave's exit (all lanes active): w holds the wave-uniform slots, slot
+// `tests_slot` is the sum of the lanes' own triangle tests; one atomic add per non-zero slot, by lane 0
+template <int SLOTS>
+__device__ __forceinline__ void flush_counters(unsigned long long* stats, const unsigned long long (&w)[SLOTS], int tests_slot,
+                                               unsigned long long lane_tests) {
+  const unsigned long long tests = wave_sum(lane_tests);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < SLOTS; ++q) {
+      const unsigned long long v = q == tests_slot ? tests : w[q];
+      if (v) atomicAdd(&stats[q], v);
+    }
+  }
+}
+
+// The walk's closest hit h into the ray: set_hit (kernels.cl:198-201) on the arrays the walk read (P = the tiled copy, or the
+// scene itself where the walk ran with BOXES = false).  No hit: the ray is left as it is.
+__device__ __forceinline__ void finish_hit(const FrameParams& P, const TileHit& h, Ray& ray) {
+  if (h.best < 0) return;
+  const int j = h.best;
+  const f3 v0 = xyz(P.verts[3 * j]), e1 = xyz(P.verts[3 * j + 1]) - v0, e2 = xyz(P.verts[3 * j + 2]) - v0;
+  ray.tri = h.orig;
+  ray.P = (v0 + h.u * e1) + h.v * e2;
+  ray.N = xyz(P.normals[j]);
+  ray.col = P.colors[j];
+}
+
+// ---- the tiled walk ----------------------------------------------------------------------------------------------------
+constexpr int kQTile = 64;                  // triangles per tile of the tiled copy, for every kernel beside the frame's
+                                            // (the mesh kernel keeps its own kTile: the same 64, the same copy)
+
+// Step 1 of the walk, where the candidate tiles of a 64-tile pass come from, is a policy with one call:
+//   cand_of(base, lane, ntiles, clear) -> 64-bit mask, the same in every lane: bit b = tile base + b is to be visited
+// (clear(t): the walk's own bundle certificate says no ray of the wave can hit tile t; false where there is none.)
+// The default asks it lane = tile.  The AOV pass (rt_aov.hip) brings the view's screen-cell masks instead.
+struct BundleCandidates {
+  template <class CLEAR>
+  __device__ __forceinline__ unsigned long long operator()(int base, int lane, int ntiles, const CLEAR& clear) const {
+    const int t = base + lane;
+    return ballot(t < ntiles && !clear(t));
+  }
+};
 
 // One lane = one ray (start o, direction d; SHADOW: radius_sq rsq) of a wave's 64, `act` = the lane has one; call with all
 // 64 lanes.  P = the tiled copy (use_tiled_scene), tile = 4 * kQTile float4 of LDS that belong to this wave.
-//   1. lane = tile, 64 tiles per pass: the wave's rays bounded as one bundle (bounce_bundle) against each tile's box,
-//      normal cone and sliver measure (tile_clear_for_bundle) -> the candidate tiles of the pass;
+//   1. 64 tiles per pass, the candidate tiles of the pass from the policy `cand_of`.  BundleCandidates: the wave's rays bounded as one
+//      bundle (bounce_bundle) against each tile's box, normal cone and sliver measure (tile_clear_for_bundle), lane = tile;
 //   2. per candidate tile, the same certificate for each lane's own ray (es = ed = 0), ballot: no lane -> next tile;
 //   3. the tile's records v0|material, e1|original index, e2, c = cof(e1, e2) are built into the wave's LDS from the tiled
 //      copy, lane = triangle bounds the bundle (task_bound) and lane = ray tests the survivors with the reference's
 //      arithmetic: closest hit carried across tiles in h with the original-order tie rule (closer), or (SHADOW) any-hit
 //      into `blocked` with an early exit per lane and per wave.
-// A ray outside in_query_domain takes every tile and every triangle.  The spheres are the caller's.
+// A ray outside in_query_domain takes every candidate tile and every triangle of it.  The spheres are the caller's.
 // BOXES = false: P is a scene WITHOUT a tiled copy (n <= 64, RT_FLAG_GENERIC_KERNEL) — its triangles in their own order cut into
 // runs of 64, no tile data: steps 1 and 2 pass every run, step 3 is the same.
-// Counters (added to): rays outside the domain, (wave, tile) pairs left by the bundle test, pairs whose triangles were tested
-// (all three wave-uniform), and this LANE's triangle tests (the caller sums them over the wave).
-template <bool SHADOW, bool BOXES = true>
+// Counters (added to): rays outside the domain, (wave, tile) pairs that step 1 left, pairs whose triangles were tested
+// (all three wave-uniform), and this LANE's triangle tests (the caller sums them over the wave: flush_counters).
+template <bool SHADOW, bool BOXES = true, class CAND = BundleCandidates>
 __device__ __forceinline__ void tile_walk(const FrameParams& P, float4* tile, int lane, bool act, f3 o, f3 d, float rsq,
                                           TileHit& h, bool& blocked, unsigned long long& n_unculled,
                                           unsigned long long& n_bundle_tiles, unsigned long long& n_tested_tiles,
-                                          unsigned long long& lane_tests) {
+                                          unsigned long long& lane_tests, const CAND& cand_of = CAND()) {
   float4* const tv0 = tile;                     // v0 | material
   float4* const te1 = tv0 + kQTile;             // e1 | original index
   float4* const te2 = tv0 + 2 * kQTile;         // e2
@@ -118,10 +170,9 @@ __device__ __forceinline__ void tile_walk(const FrameParams& P, float4* tile, in
   const f3 nd = -d;
   bool done = false;                            // SHADOW: every lane of the wave has found its blocker
   for (int base = 0; base < ntiles && !done; base += 64) {
-    const int t = base + lane;
-    bool need = t < ntiles;
-    if (BOXES && need && bundle_ok) need = !tile_clear_for_bundle(P.tile_box + (size_t)3 * t, bnd.s0, bnd.D0, bnd.es, bnd.ed, d2);
-    const unsigned long long cand = ballot(need);
+    const unsigned long long cand = cand_of(base, lane, ntiles, [&](int t) {
+      return BOXES && bundle_ok && tile_clear_for_bundle(P.tile_box + (size_t)3 * t, bnd.s0, bnd.D0, bnd.es, bnd.ed, d2);
+    });
     n_bundle_tiles += __popcll(cand);
     for (unsigned long long m = uniform64(cand); m != 0ull; m &= m - 1ull) {
       const int tt = base + __builtin_ctzll(m);
