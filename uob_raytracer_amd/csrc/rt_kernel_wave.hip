@@ -366,7 +366,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
   float4* scbase = reinterpret_cast<float4*>(sidx + ((st + 3) & ~3));
   for (int kq = tid; kq < ns; kq += 64 * kWavesPerBlock) {
     const int ti = sidx[kq];
-    scbase[kq] = lds[ti]; scbase[sst + kq] = lds[st + ti]; scbase[2 * sst + kq] = lds[2 * st + ti]; scbase[3 * sst + kq] = lds[3 * st + ti];
+    scbase[kq] = lds[ti]; scbase[sst + kq] = lds[st + ti]; scbase[2 * sst + kq] = lds[2 * st + ti];
+    // c.w (the primary rays' det(A0), which no shadow ray uses) gives way to |c|_1, which level 2 wants per caster and point
+    const float4 c4 = lds[3 * st + ti];
+    scbase[3 * sst + kq] = make_float4(c4.x, c4.y, c4.z, norm1(xyz(c4)));
   }
   __syncthreads();
   const ShadowCasters SC{scbase, scbase + sst, scbase + 2 * sst, scbase + 3 * sst};
@@ -499,6 +502,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
   f3 jk_D0 = mk(0.f, 0.f, 0.f);
   float jk_ed = 0.0f;
   unsigned long long jk_K = 0ull;
+  // ... and the same set without the casters that plane_slab_tneg settles for points on triangle jk_h (-1: none)
+  using kh_t = typename std::conditional<STRIDE == 32, uint32_t, unsigned long long>::type;
+  kh_t jk_Kh = (kh_t)0;
+  int jk_h = -1;
   // Triangles a primary ray of this job may hit, bounded once for the job's 64 x 1 pixels (all AA samples): the
   // rays leave the camera through a sub-pixel rectangle, see primary_clear.  (Per task the rectangle is 8x
   // narrower and a triangle or so fewer survives, but the bound itself costs more than that triangle's tests.)
@@ -621,8 +628,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
           const f3 dj = dir - jk_D0;
           reuse = wave_max_pos(slit ? norm_inf(dj) : 0.0f) <= jk_ed;
         }
+        int h = -1;                                 // the triangle Kh was certified for
+        unsigned long long Kh = 0ull;
         if (reuse) {
-          K = jk_K; task_sph = jk_sph; task_blocked = jk_blocked;
+          K = jk_K; task_sph = jk_sph; task_blocked = jk_blocked; Kh = (unsigned long long)jk_Kh; h = jk_h;
         } else {
         const int jr = 63 - __builtin_clzll(work);
         const f3 s0 = mk(rl(start.x, jr), rl(start.y, jr), rl(start.z, jr));
@@ -653,10 +662,35 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
           const Bound tb = light_bundle_bound(T1, light, s0, es, D0, ed, hh_task, dlen_min, dlen_max, P.light_inf + dlen_max + norm1(T1.v0));
           K = tri_lanes & ~ballot(tb.clear);
           task_blocked = (tri_lanes & ballot(tb.all_blocked)) != 0ull;
+          // Points on ONE triangle h (the reference lane's; a sphere hit is -2): the casters in whose plane h lies — h itself,
+          // its face partner, whatever else is coplanar — have t < 0 for every sample of every such point, which the box of
+          // start points above cannot show (det(A0) changes sign over it) and level 2 then finds per point, per caster and
+          // per task.  Certified here once, lane = caster, for the same direction set, and reused with the rest of level 1.
+          h = __builtin_amdgcn_readlane(ray.tri, jr);
+          Kh = K;
+          // (only where at least two tasks of the job are still to come and may reuse it, and a job has at least eight tasks —
+          // a 64-pixel job has as many tasks as a pixel has AA samples: the clause costs about what it saves two tasks, and the
+          // short jobs of the 2x2-AA configurations ran 1-4 % slower with it, in their specialised instantiations also for its
+          // registers; there the condition is a constant and the clause is not compiled in)
+          if (left < 2.0f || aa < 8) h = -1;
+          if (h >= 0) {
+            // (after the bound above, not among its registers: the caster's two records are read again)
+            __builtin_amdgcn_sched_barrier(0);
+            const int lnH = opaque(lane);
+            const float4 kc = SC.c[lnH < ns ? lnH : 0];
+            TriLane Tk;
+            Tk.v0 = xyz(SC.v0[lnH < ns ? lnH : 0]); Tk.c = xyz(kc); Tk.c1 = kc.w;
+            const f3 hv0 = xyz(S.v0[h]), he1 = xyz(S.e1[h]), he2 = xyz(S.e2[h]);       // LDS broadcasts
+            const float Mh = norm_inf(hv0) + norm_inf(he1) + norm_inf(he2);
+            Kh = K & ~ballot(plane_slab_tneg(Tk, hv0, he1, he2, D0, ed, hh_task, Mh + P.light_inf + dlen_max + norm1(Tk.v0)));
+          }
+          jk_Kh = (kh_t)Kh; jk_h = h;
           // what the next tasks compare with: directions within 0.9999 ed of D0 (the bound itself allows 1.001 ed and more)
           jk_valid = true; jk_D0 = D0; jk_ed = uniform(ed * 0.9999f); jk_K = K; jk_sph = task_sph; jk_blocked = task_blocked;
         }
         }
+        // the smaller set for a task whose lit points all lie on h (level 3 is handed the set level 2 walks: `need` indexes it)
+        if (h >= 0 && ballot(slit && ray.tri != h) == 0ull) K = Kh;
       }
       if (task_sph && !task_blocked && sane) sb = spheres_point(P, start, dir, dlen, hh);
       sphmask = ballot(slit && P.nsph > 0 && (sb.maybe || !sane));
@@ -673,14 +707,16 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
         int pos = 0;
         for (unsigned long long kk = K; kk != 0ull; kk &= kk - 1ull, ++pos) {
           const int kq = __builtin_ctzll(kk);
-          // two thirds of the pairs that reach level 2 are a surface against its own plane: t < 0 for every
-          // sample, by the signs of det(A0) (exact) and det(A) alone — the first clause of point_bound
-          const f3 c_ = xyz(SC.c[kq]);
-          const float nA0_ = detc(start - xyz(SC.v0[kq]), c_), D0_ = detc(-dir, c_), Dl_ = hh * norm1(c_);
+          // t < 0 for every sample, by the signs of det(A0) (exact) and det(A) alone — the first clause of point_bound.  (Two
+          // thirds of the pairs that reached level 2 were a surface against its own plane; level 1 now settles those per job
+          // where the task's points share a triangle, and what is left of them arrives here: tasks across a diagonal or edge.)
+          const float4 c4_ = SC.c[kq];              // w: |c|_1, staged with the record
+          const f3 c_ = xyz(c4_);
+          const float nA0_ = detc(start - xyz(SC.v0[kq]), c_), D0_ = detc(-dir, c_), Dl_ = hh * c4_.w;
           const bool tneg = sane && ((D0_ - Dl_ > 0.0f && nA0_ < -1e-18f) || (D0_ + Dl_ < 0.0f && nA0_ > 1e-18f));
           if (ballot(slit && !tneg) == 0ull) continue;
-          const Bound pb = point_bound(start, dir, hh, dlen, cc.dminlen, cc.dk, xyz(SC.v0[kq]), xyz(SC.e1[kq]), xyz(SC.e2[kq]),
-                                       xyz(SC.c[kq]), slit && !tneg && !blocked);
+          const Bound pb = point_bound_c1<true>(start, dir, hh, dlen, cc.dminlen, cc.dk, xyz(SC.v0[kq]), xyz(SC.e1[kq]), xyz(SC.e2[kq]),
+                                       c_, c4_.w, slit && !tneg && !blocked);
           if (!pb.clear || !sane) need |= (need_t)((need_t)1 << pos);
           blocked = blocked || (sane && pb.all_blocked);
         }
