@@ -420,6 +420,22 @@ int rt_debug_world_masks(rt_ctx* ctx, uint64_t* out, int64_t cap, int32_t* grid,
  * RT_E_UNSUPPORTED when the context keeps no tiled copy (n <= 64, RT_FLAG_GENERIC_KERNEL).                              */
 int rt_debug_tile_data(rt_ctx* ctx, int32_t* orig, float* tiles, int32_t cap_tiles);
 
+/* Diagnostic: the scene the context holds after its latest edit (rt_update_scene*, rt_replace_scene*, rt_pose_objects*), read
+ * back from the device; a pending device edit is waited for.  Every output is nullable (NULL: not copied):
+ *   vertices4 [3n][4], normals4 [n][4], colors4 [n][4]         the scene in the caller's original order, rt_init's layout;
+ *   vertices4_m [3n][4], normals4_m [n][4], colors4_m [n][4]   the mesh kernel's tiled copy: entry j is the original
+ *                                                              triangle orig[j] of rt_debug_tile_data;
+ *   n_shadow                    the triangles that cast shadows (colour w != -1), as the scene's check counted them;
+ *   vbox_lo[3], vbox_hi[3]      the vertices' box as the scene's check reduced it.  Only a context with tile masks
+ *                               (n > 1024, no RT_FLAG_NO_TILE_BINS / NO_CULL / GENERIC_KERNEL) keeps it; others give zeros.
+ * cap_triangles = the triangles every non-NULL array has room for; 0 asks for the count only.  Returns the triangle
+ * count n; RT_E_INVALID for a NULL ctx, a negative capacity and 0 < cap_triangles < n; RT_E_UNSUPPORTED when a tiled
+ * array is asked of a context that keeps no tiled copy (n <= 64, RT_FLAG_GENERIC_KERNEL).  A multi-device context
+ * answers for devices[0].                                                                                              */
+int rt_debug_scene_data(rt_ctx* ctx, float* vertices4, float* normals4, float* colors4, float* vertices4_m,
+                        float* normals4_m, float* colors4_m, int32_t* n_shadow, float vbox_lo[3], float vbox_hi[3],
+                        int32_t cap_triangles);
+
 /* Optional: let the device write the frame STRAIGHT into the caller's host framebuffer (screen->buffer,
  * SDLauxiliary.h:105) instead of rendering into device memory and copying 4 bytes per pixel back after the kernel
  * (clEnqueueReadBuffer, skeleton.cpp:179-180): the pixels cross PCIe while the frame is still being rendered.

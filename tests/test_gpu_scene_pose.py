@@ -105,6 +105,32 @@ def test_mesh_objects(n_lon, n_lat, flags, pose_flags, scene, oracle, tmp_path):
         tr.close()
 
 
+@pytest.mark.parametrize("n_lon,n_lat", [(10, 8), (40, 30)])
+@pytest.mark.parametrize("pose_flags", [0, abi.RT_UPDATE_DEVICE_TILES])
+def test_posed_values_are_the_hosts(n_lon, n_lat, pose_flags, scene, tmp_path):
+    """Value by value, not through pixels: the scene the device posed is Scene.posed (rt_scene_transform), every vertex and
+    every normal of every triangle bit for bit; the colours and the triangles in no object are the rest scene's."""
+    both, nf = su._mesh_scene(scene, tmp_path, n_lon, n_lat)
+    cfg = abi.make_config(width=64, height=48, aa_x=1, aa_y=1, shadow_samples=3)
+    rest = both.packed()
+    for ranges, xf in _layouts(both, nf):
+        want = both.posed(ranges, xf).packed()
+        tr = rt.RayTracer(cfg, both)
+        tr.set_objects(ranges)
+        tr.pose_objects(xf, **FLAG_KW[pose_flags])
+        d = tr.scene_data()
+        assert np.array_equal(d["vertices"].view(np.uint32), want[0].view(np.uint32))
+        assert np.array_equal(d["normals"].view(np.uint32), want[1].view(np.uint32))
+        assert np.array_equal(d["colors"].view(np.uint32), rest[2].view(np.uint32))
+        assert not np.array_equal(d["vertices"], rest[0])
+        static = np.ones(len(both), bool)
+        for first, count in rt._object_ranges(ranges, len(both)):
+            static[first:first + count] = False
+        assert static.any() and np.array_equal(d["normals"].view(np.uint32)[static], rest[1].view(np.uint32)[static])
+        assert np.array_equal(d["vertices"].view(np.uint32).reshape(-1, 12)[static], rest[0].view(np.uint32).reshape(-1, 12)[static])
+        tr.close()
+
+
 @pytest.fixture(scope="module")
 def small(scene, tmp_path_factory):
     """Box + the 140-triangle sphere, its mesh as one object."""

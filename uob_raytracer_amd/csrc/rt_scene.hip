@@ -664,4 +664,37 @@ int rt_debug_tile_data(rt_ctx* c, int32_t* orig, float* tiles, int32_t cap_tiles
   return ntiles;
 }
 
+int rt_debug_scene_data(rt_ctx* c, float* vertices4, float* normals4, float* colors4, float* vertices4_m, float* normals4_m,
+                        float* colors4_m, int32_t* n_shadow, float* vbox_lo, float* vbox_hi, int32_t cap_triangles) {
+  if (cap_triangles < 0) { set_error("rt_debug_scene_data: capacity %d is negative", cap_triangles); return RT_E_INVALID; }
+  if (!c) { set_error("rt_debug_scene_data: NULL context"); return RT_E_INVALID; }
+  c = lead_ctx(c);
+  const int n = c->n;
+  if (cap_triangles == 0) return n;
+  if (cap_triangles < n) { set_error("rt_debug_scene_data: room for %d triangles, %d needed", cap_triangles, n); return RT_E_INVALID; }
+  if ((vertices4_m || normals4_m || colors4_m) && !c->d_verts_m) {
+    set_error("rt_debug_scene_data: this context keeps no tiled copy of the scene"); return RT_E_UNSUPPORTED;
+  }
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(wait_scene(c, c->stream));
+  const size_t nb = (size_t)n * sizeof(float4);
+  auto fetch = [&](float* dst, const float4* src, size_t bytes) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+  };
+  HIP_TRY(fetch(vertices4, c->d_verts, 3 * nb));
+  HIP_TRY(fetch(normals4, c->d_normals, nb));
+  HIP_TRY(fetch(colors4, c->d_colors, nb));
+  HIP_TRY(fetch(vertices4_m, c->d_verts_m, 3 * nb));
+  HIP_TRY(fetch(normals4_m, c->d_normals_m, nb));
+  HIP_TRY(fetch(colors4_m, c->d_colors_m, nb));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (n_shadow) *n_shadow = c->n_shadow;
+  for (int k = 0; k < 3; ++k) {
+    if (vbox_lo) vbox_lo[k] = c->vbox_lo[k];
+    if (vbox_hi) vbox_hi[k] = c->vbox_hi[k];
+  }
+  return n;
+}
+
 }  // extern "C"

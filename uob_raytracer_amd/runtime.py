@@ -34,6 +34,7 @@ EXPORTS = (
     "rt_radiance_rays", "rt_radiance_rays_device", "rt_debug_radiance_stats",
     "rt_replace_scene", "rt_replace_scene_device", "rt_update_spheres", "rt_debug_scene_capacity",
     "rt_scene_transform", "rt_set_objects", "rt_pose_objects", "rt_pose_objects_device", "rt_debug_object_count",
+    "rt_debug_scene_data",
 )
 
 # rt_debug_trace_stats slots (include/uob_rt.h)
@@ -74,6 +75,7 @@ def lib():
         L.rt_update_scene.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_uint32]
         L.rt_update_scene_device.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint32, vp]
         L.rt_debug_tile_data.argtypes = [vp, C.POINTER(C.c_int32), fp, C.c_int32]
+        L.rt_debug_scene_data.argtypes = [vp, fp, fp, fp, fp, fp, fp, C.POINTER(C.c_int32), fp, fp, C.c_int32]
         L.rt_replace_scene.argtypes = [vp, fp, fp, fp, C.c_int32, C.c_uint32]
         L.rt_replace_scene_device.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint32, vp]
         L.rt_update_spheres.argtypes = [vp, C.POINTER(abi.RtSphere), C.c_int32]
@@ -423,6 +425,23 @@ class RayTracer:
         tiles = np.zeros((nt, 12), np.float32)
         _check(lib().rt_debug_tile_data(self._h, orig.ctypes.data_as(C.POINTER(C.c_int32)), _fp(tiles), nt))
         return orig, tiles
+
+    def scene_data(self, tiled=False):
+        """The scene the context holds, read back from the device (rt_debug_scene_data): dict with "vertices" [3n,4],
+        "normals" [n,4], "colors" [n,4] in original order, "n_shadow" and the vertices' box "vbox_lo" / "vbox_hi" as the
+        scene's check left them; with tiled=True also the mesh kernel's tiled copy "vertices_m", "normals_m", "colors_m"."""
+        n = _check(lib().rt_debug_scene_data(self._h, None, None, None, None, None, None, None, None, None, 0))
+        out = {"vertices": np.zeros((3 * n, 4), np.float32), "normals": np.zeros((n, 4), np.float32),
+               "colors": np.zeros((n, 4), np.float32)}
+        if tiled:
+            out.update(vertices_m=np.zeros((3 * n, 4), np.float32), normals_m=np.zeros((n, 4), np.float32),
+                       colors_m=np.zeros((n, 4), np.float32))
+        n_shadow, lo, hi = C.c_int32(), np.zeros(3, np.float32), np.zeros(3, np.float32)
+        tiled_ptrs = [_fp(out[k]) if tiled else None for k in ("vertices_m", "normals_m", "colors_m")]
+        _check(lib().rt_debug_scene_data(self._h, _fp(out["vertices"]), _fp(out["normals"]), _fp(out["colors"]), *tiled_ptrs,
+                                         C.byref(n_shadow), _fp(lo), _fp(hi), n))
+        out.update(n_shadow=int(n_shadow.value), vbox_lo=lo, vbox_hi=hi)
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
