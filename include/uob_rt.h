@@ -206,6 +206,49 @@ int rt_pose_objects_device(rt_ctx* ctx, const void* d_xforms12, uint32_t flags, 
 /* Diagnostic: objects in the context's table (0: none).                                                              */
 int rt_debug_object_count(rt_ctx* ctx, int32_t* out);
 
+/* ---- skinned meshes: blend bone matrices per vertex on the device (rt_scene_pose.hip) ------------------
+ * A SKIN is a range [first, first + count) of the context's triangles, in the caller's original order, with FOUR INFLUENCES
+ * (bone j_k, weight w_k; k = 0..3) for each of its 3 * count corners: one row of bone_index [3*count][4] and of weights
+ * [3*count][4] per corner, in the order corner 0, 1, 2 of triangle first, then of first + 1, and so on.  A POSE is one xform12
+ * per bone (the layout of the rigid objects' xform12).  Skinning the rest scene R with the bones B gives the scene S(R, B),
+ * rt_scene_skin's arithmetic (below): for every corner v of the range
+ *   p_k   = the rigid pose of v by bone j_k, rt_scene_transform's expression: ((v.x*m_r0 + v.y*m_r1) + v.z*m_r2) + t_r per row r;
+ *   v'_c  = ((w_0*p_0.c + w_1*p_1.c) + w_2*p_2.c) + w_3*p_3.c per component c;
+ *   FP32 without contraction, in this operation order.  All four influences are always evaluated, also at weight 0: 0 * inf
+ *   is a NaN, and the check of the posed scene rejects it.  Weights are not normalised: a sum below 1 pulls the vertex toward
+ *   the origin.
+ *   The normal of every triangle of the range is recomputed as rt_triangle_compute_normal does, always;
+ *   triangles outside the range, and all colours, are the rest scene's, bit for bit.
+ * After RT_OK every later operation of the context — frames, AOV passes, ray queries, shade and radiance calls, the counting
+ * passes — gives exactly the bits that rt_update_scene(ctx, pack(S(R, B)), flags) would have given.  A pose always starts
+ * from R, never from the previous pose: nothing drifts.
+ *
+ * rt_set_skin snapshots the context's current scene as the rest pose R exactly as rt_set_objects does (same buffers, same
+ * waiting; blocking) and uploads the influence table, 24 bytes per corner.  Checked on the host before any device work: the
+ * range is non-empty and inside [0, n); nbones in 1 .. 65535; every index < nbones; every weight finite and in [0, 1].
+ * Anything else is RT_E_INVALID with a message that names the corner or the argument, and the previous table (skin or
+ * objects) survives.  count == 0 drops the skin and frees its memory.  A context holds EITHER an object table OR a skin (they
+ * share the rest pose): a successful rt_set_skin drops the objects, a successful rt_set_objects with nobj > 0 drops the skin.
+ * rt_update_scene* and rt_replace_scene* drop the skin as they drop the objects; rt_update_spheres does not touch it.  A
+ * context that never calls rt_set_skin allocates nothing for it.  rt_pose_skin* without a skin is RT_E_INVALID ("no skin"),
+ * as rt_pose_objects* with only a skin is ("no object table").                                                             */
+int rt_set_skin(rt_ctx* ctx, int32_t first, int32_t count, const uint16_t* bone_index, const float* weights, int32_t nbones);
+
+/* Pose the skin: bones12 = float32 [nbones][12] in host memory; nbones * 48 bytes are uploaded and nothing else.  In every
+ * other respect rt_pose_objects: the posed scene is written on the device and goes through rt_update_scene_device's path
+ * (flags 0, RT_UPDATE_DEVICE_TILES or RT_UPDATE_REORDER, with the same meaning and the same exclusion); validation is that of
+ * the posed scene (finite, |x| <= 2^16), and on any failure the context keeps its previous scene, whole, and its rest pose.
+ * Blocking.                                                                                                              */
+int rt_pose_skin(rt_ctx* ctx, const float* bones12, uint32_t flags);
+
+/* Same, with the bones in device memory on the context's device (devices[0]), stream-ordered exactly like
+ * rt_pose_objects_device / rt_update_scene_device: d_bones12 may change once hip_stream has passed the call.  A multi-device
+ * context poses on devices[0]; the other devices receive the posed scene by peer copy.                                  */
+int rt_pose_skin_device(rt_ctx* ctx, const void* d_bones12, uint32_t flags, void* hip_stream);
+
+/* Diagnostic: the skinned range and the bone count of the context's skin (zeros: none).                              */
+int rt_debug_skin_info(rt_ctx* ctx, int32_t* first, int32_t* count, int32_t* nbones);
+
 /* Render one frame and read it back: rot = 3 rows x (x,y,z,pad) exactly as rot_matrix[12] at
  * skeleton.cpp:149-151; cam/light = first 12 bytes of camera_position / light_position (:162,:164);
  * focal = focal_length (:166), in units of AA sub-pixels along x.  out_argb receives
@@ -420,8 +463,8 @@ int rt_debug_world_masks(rt_ctx* ctx, uint64_t* out, int64_t cap, int32_t* grid,
  * RT_E_UNSUPPORTED when the context keeps no tiled copy (n <= 64, RT_FLAG_GENERIC_KERNEL).                              */
 int rt_debug_tile_data(rt_ctx* ctx, int32_t* orig, float* tiles, int32_t cap_tiles);
 
-/* Diagnostic: the scene the context holds after its latest edit (rt_update_scene*, rt_replace_scene*, rt_pose_objects*), read
- * back from the device; a pending device edit is waited for.  Every output is nullable (NULL: not copied):
+/* Diagnostic: the scene the context holds after its latest edit (rt_update_scene*, rt_replace_scene*, rt_pose_objects*,
+ * rt_pose_skin*), read back from the device; a pending device edit is waited for.  Every output is nullable (NULL: not copied):
  *   vertices4 [3n][4], normals4 [n][4], colors4 [n][4]         the scene in the caller's original order, rt_init's layout;
  *   vertices4_m [3n][4], normals4_m [n][4], colors4_m [n][4]   the mesh kernel's tiled copy: entry j is the original
  *                                                              triangle orig[j] of rt_debug_tile_data;
@@ -521,6 +564,12 @@ void rt_triangle_compute_normal(rt_triangle* t);
  * contraction (w stays), and their normals recomputed by rt_triangle_compute_normal.  A range that is not inside [0, n)
  * changes nothing.                                                                                                   */
 void rt_scene_transform(rt_triangle* tris, int32_t n, int32_t first, int32_t count, const float xform12[12]);
+/* The skin arithmetic on the host (CPU only), "skinned meshes" above: the triangles [first, first + count) of tris[0 .. n)
+ * get every corner replaced by the blend of its four rigid poses (bone_index, weights: [3*count][4], one row per corner;
+ * bones12: [nbones][12]; w of the vertex stays), and their normals recomputed by rt_triangle_compute_normal.  A range that is
+ * not inside [0, n), or an index >= nbones anywhere in the table, changes nothing.                                      */
+void rt_scene_skin(rt_triangle* tris, int32_t n, int32_t first, int32_t count, const uint16_t* bone_index,
+                   const float* weights, const float* bones12, int32_t nbones);
 /* AoS -> the three packed float4 arrays (skeleton.cpp:474-484).                                      */
 void rt_scene_pack(const rt_triangle* tris, int32_t n, float* vertices4, float* normals4, float* colors4);
 /* Rotation matrix from yaw/pitch exactly as skeleton.cpp:149-151 (float cos/sin).                    */

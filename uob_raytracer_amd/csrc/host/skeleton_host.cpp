@@ -16,6 +16,11 @@
 //                 [--spin RAD]                with --obj: the mesh is one rigid object (rt_set_objects); frame f = 1, 2, ... poses
 //                                             it by a rotation of f * RAD about the vertical axis through the centre of
 //                                             its rest bounding box (rt_pose_objects: 48 bytes per frame cross the bus)
+//                 [--bend RAD]                with --obj: the mesh is skinned to two bones (rt_set_skin), bone 1 weighted by
+//                                             (y - ymin) / (ymax - ymin) of the rest vertex and bone 0 by the rest; frame
+//                                             f = 1, 2, ... keeps bone 0 and turns bone 1 by f * RAD about the vertical axis
+//                                             through the centre of the rest mesh's bounding box, as --spin turns the
+//                                             mesh (rt_pose_skin: 96 bytes per frame cross the bus)
 //                 [--bounce-sphere]           sphere 0 follows a parabola, frame by frame (rt_update_spheres)
 //                 [--gpus N | --devices a,b,..]  render every frame on several GPUs inside the one context
 //                 [--copy-back]                  device buffer + blocking read-back instead of rt_register_output
@@ -51,8 +56,9 @@ static size_t g_obj_first = 0;                                 // --move: the lo
 static bool g_move = false;
 static float g_move_by[3] = {0.0f, 0.0f, 0.0f};
 static bool g_spin = false;                                    // --spin: the loaded mesh turns as one rigid object
-static float g_spin_rad = 0.0f;
-static float g_spin_centre[3] = {0.0f, 0.0f, 0.0f};            // centre of the rest mesh's bounding box
+static float g_turn_rad = 0.0f;                               // --spin / --bend: the angle per frame
+static float g_turn_centre[3] = {0.0f, 0.0f, 0.0f};            // centre of the rest mesh's bounding box
+static bool g_bend = false;                                    // --bend: the loaded mesh bends between two bones
 static bool g_bounce = false;                                  // --bounce-sphere: sphere 0 follows a parabola, frame by frame
 static rt_sphere g_spheres[RT_MAX_SPHERES];
 static int g_num_spheres = 0;
@@ -77,26 +83,64 @@ void update_scene() {
   if (rt_update_scene(g_rt, v.data(), nr.data(), col.data(), n, 0) != RT_OK) die("rt_update_scene");
 }
 
-// The mesh becomes the context's one object; its rest pose is the scene as uploaded
-void spin_begin() {
-  float lo[3], hi[3];
+// The bounding box of the loaded mesh as it stands, and its centre into g_turn_centre
+static void mesh_box(float lo[3], float hi[3]) {
   for (int k = 0; k < 3; ++k) lo[k] = hi[k] = triangles[g_obj_first].v0[k];
   for (size_t t = g_obj_first; t < triangles.size(); ++t)
     for (const float* p : {triangles[t].v0, triangles[t].v1, triangles[t].v2})
       for (int k = 0; k < 3; ++k) { if (p[k] < lo[k]) lo[k] = p[k]; if (p[k] > hi[k]) hi[k] = p[k]; }
-  for (int k = 0; k < 3; ++k) g_spin_centre[k] = (lo[k] + hi[k]) * 0.5f;
+  for (int k = 0; k < 3; ++k) g_turn_centre[k] = (lo[k] + hi[k]) * 0.5f;
+}
+
+// The mesh becomes the context's one object; its rest pose is the scene as uploaded
+void spin_begin() {
+  float lo[3], hi[3];
+  mesh_box(lo, hi);
   const int32_t first = (int32_t)g_obj_first, count = (int32_t)(triangles.size() - g_obj_first);
   if (rt_set_objects(g_rt, &first, &count, 1) != RT_OK) die("rt_set_objects");
 }
 
-// The mesh of frame f = 1, 2, ...: the rest pose turned by f * RAD about the vertical axis through the centre c,
-// v' = M v + (c - M c), M as rt_rotation_matrix builds it (float cos / sin); to the device before the frame
+// The rest pose turned by f * RAD about the vertical axis through the centre c: v' = M v + (c - M c), M as
+// rt_rotation_matrix builds it (float cos / sin)
+static void turn_about_centre(int f, float x[12]) {
+  rt_rotation_matrix((float)f * g_turn_rad, 0.0f, x);
+  const float* c = g_turn_centre;
+  for (int r = 0; r < 3; ++r) x[4 * r + 3] = c[r] - ((c[0] * x[4 * r] + c[1] * x[4 * r + 1]) + c[2] * x[4 * r + 2]);
+}
+
+// The mesh of frame f = 1, 2, ...: turned as one rigid object; to the device before the frame
 void spin_mesh(int f) {
   float x[12];
-  rt_rotation_matrix((float)f * g_spin_rad, 0.0f, x);
-  const float* c = g_spin_centre;
-  for (int r = 0; r < 3; ++r) x[4 * r + 3] = c[r] - ((c[0] * x[4 * r] + c[1] * x[4 * r + 1]) + c[2] * x[4 * r + 2]);
+  turn_about_centre(f, x);
   if (rt_pose_objects(g_rt, x, 0) != RT_OK) die("rt_pose_objects");
+}
+
+// The mesh is skinned to two bones by the height of its rest vertices: bone 1 weighs (y - ymin) / (ymax - ymin), clamped to
+// [0, 1], bone 0 the rest; its rest pose is the scene as uploaded
+void bend_begin() {
+  float lo[3], hi[3];
+  mesh_box(lo, hi);
+  const size_t count = triangles.size() - g_obj_first;
+  vector<uint16_t> index(12 * count, 0);
+  vector<float> weights(12 * count, 0.0f);
+  const float height = hi[1] - lo[1];
+  size_t corner = 0;
+  for (size_t t = g_obj_first; t < triangles.size(); ++t)
+    for (const float* p : {triangles[t].v0, triangles[t].v1, triangles[t].v2}) {
+      float w = height > 0.0f ? (p[1] - lo[1]) / height : 0.0f;
+      w = w < 0.0f ? 0.0f : (w > 1.0f ? 1.0f : w);
+      index[4 * corner + 1] = 1;
+      weights[4 * corner] = 1.0f - w; weights[4 * corner + 1] = w;
+      ++corner;
+    }
+  if (rt_set_skin(g_rt, (int32_t)g_obj_first, (int32_t)count, index.data(), weights.data(), 2) != RT_OK) die("rt_set_skin");
+}
+
+// The mesh of frame f = 1, 2, ...: bone 0 stays, bone 1 turns as --spin turns the mesh; to the device before the frame
+void bend_mesh(int f) {
+  float bones[24] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f};
+  turn_about_centre(f, bones + 12);
+  if (rt_pose_skin(g_rt, bones, 0) != RT_OK) die("rt_pose_skin");
 }
 
 // Sphere 0 of frame f = 1, 2, ... on a fixed parabola (one bounce in eight frames), to the device before the frame
@@ -174,7 +218,8 @@ int main(int argc, char* argv[]) {
       if (sscanf(argv[++i], "%f,%f,%f", &g_move_by[0], &g_move_by[1], &g_move_by[2]) != 3) { fprintf(stderr, "--move DX,DY,DZ\n"); return 2; }
       g_move = true;
     }
-    else if (a == "--spin" && i + 1 < argc) { g_spin_rad = (float)atof(argv[++i]); g_spin = true; }
+    else if (a == "--spin" && i + 1 < argc) { g_turn_rad = (float)atof(argv[++i]); g_spin = true; }
+    else if (a == "--bend" && i + 1 < argc) { g_turn_rad = (float)atof(argv[++i]); g_bend = true; }
     else if (a == "--bounce-sphere") g_bounce = true;
     else if (a == "--copy-back") direct_out = false;           // render into device memory + blocking copy, as the reference reads back
     else if (a == "--gpus" && i + 1 < argc) {
@@ -199,6 +244,8 @@ int main(int argc, char* argv[]) {
   if (g_move && !obj) { fprintf(stderr, "--move needs --obj\n"); return 2; }
   if (g_spin && !obj) { fprintf(stderr, "--spin needs --obj\n"); return 2; }
   if (g_spin && g_move) { fprintf(stderr, "--spin and --move exclude each other (--move replaces the scene behind the rest pose)\n"); return 2; }
+  if (g_bend && !obj) { fprintf(stderr, "--bend needs --obj\n"); return 2; }
+  if (g_bend && (g_spin || g_move)) { fprintf(stderr, "--bend excludes --spin and --move (one rest pose, one table)\n"); return 2; }
   g_num_spheres = cfg.num_spheres;
   for (int i = 0; i < RT_MAX_SPHERES; ++i) g_spheres[i] = cfg.spheres[i];
   if (obj) {                                                                   // load_obj + insert, :102-103
@@ -210,6 +257,7 @@ int main(int argc, char* argv[]) {
   printf("Triangles Length size %lu\n", triangles.size());                    // :104
   opencl_initialise(cfg);                                                      // :106
   if (g_spin && triangles.size() > g_obj_first) spin_begin();
+  if (g_bend && triangles.size() > g_obj_first) bend_begin();
   // the device(s) write finished pixels straight into screen->buffer (no read-back after the kernel)
   if (direct_out &&
       rt_register_output(g_rt, screen->buffer, (size_t)SCREEN_WIDTH * SCREEN_HEIGHT * sizeof(uint32_t)) != RT_OK)
@@ -221,6 +269,7 @@ int main(int argc, char* argv[]) {
     update();
     if (g_move) update_scene();
     if (g_spin && triangles.size() > g_obj_first) spin_mesh(f + 1);
+    if (g_bend && triangles.size() > g_obj_first) bend_mesh(f + 1);
     if (g_bounce) bounce_sphere(f + 1);
     auto start = high_resolution_clock::now();
     offload_rendering(screen);

@@ -188,7 +188,7 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
   if (n < 0 || (n > 0 && (!vertices4 || !normals4 || !colors4))) { set_error("scene arrays missing"); return RT_E_INVALID; }
   rc = validate_vertices(vertices4, n);
   if (rc != RT_OK) return rc;
-  if (n > 4000000) { set_error("triangle list of %d exceeds the supported maximum of 4000000", n); return RT_E_UNSUPPORTED; }
+  if (n > kMaxTriangles) { set_error("triangle list of %d exceeds the supported maximum of %d", n, kMaxTriangles); return RT_E_UNSUPPORTED; }
   DeviceGuard guard;
   if (cfg->num_devices > 1) return init_parent(cfg, vertices4, normals4, colors4, n, out_ctx);
   int ndev = 0;
@@ -893,6 +893,7 @@ void rt_destroy(rt_ctx* c) {
   hipFree(o.verts_m); hipFree(o.normals_m); hipFree(o.colors_m); hipFree(o.orig); hipFree(o.tile_box);
   hipFree(c->d_check); hipFree(c->tile_scratch.p);
   hipFree(c->d_rest_verts); hipFree(c->d_rest_normals); hipFree(c->d_object_of);
+  hipFree(c->d_skin_index); hipFree(c->d_skin_weights);
   hipFree(c->pose_verts.p); hipFree(c->pose_normals.p); hipFree(c->pose_xforms.p);
   delete c;
 }

@@ -29,6 +29,7 @@ struct KeepError {
   ~KeepError();
 };
 
+constexpr int kMaxTriangles = 4000000;     // the largest scene rt_init, an update or a replace accepts
 constexpr int kWorldGrid = 32;             // world cells per axis of the mesh kernel's shadow-ray tile masks
 
 // rt_kernel_generic.hip
@@ -58,6 +59,9 @@ void launch_scene_refit(const float4* v, const float4* nrm, const float4* col, c
 constexpr unsigned int kPoseStatic = 0xffffu;   // object_of[i] of a triangle in no object (so at most 65535 objects)
 void launch_pose(const float4* rest_v, const float4* rest_n, const unsigned short* object_of, const float* d_xforms12, int n,
                  float4* out_v, float4* out_n, hipStream_t stream);
+// the rest pose and one xform12 per bone, blended by the influence table of the triangles [first, first + count)
+void launch_skin(const float4* rest_v, const float4* rest_n, const ushort4* index, const float4* weights, const float* d_bones12,
+                 int n, int first, int count, float4* out_v, float4* out_n, hipStream_t stream);
 // rt_tile_build.hip: the tiled order of tiled_order(.., morton = true), on the device
 size_t tile_build_scratch_bytes(int n);
 int launch_tile_build(const float4* v, int n, const float lo[3], const float hi[3], int* orig, void* scratch, hipStream_t stream);
@@ -204,6 +208,12 @@ struct rt_ctx {
   float4 *d_rest_verts = nullptr, *d_rest_normals = nullptr;
   unsigned short* d_object_of = nullptr;
   uobrt::DevBuffer pose_verts, pose_normals, pose_xforms;
+  // A skin (rt_set_skin / rt_pose_skin*) shares the rest pose, the staging scene and the host entry's matrices with the
+  // objects, so a context holds one or the other.  The influence table exists while skin_count > 0: per corner of the
+  // triangles [skin_first, skin_first + skin_count) four bone indices (8 bytes) and four weights (16 bytes)
+  int skin_first = 0, skin_count = 0, skin_nbones = 0;
+  ushort4* d_skin_index = nullptr;
+  float4* d_skin_weights = nullptr;
   // The scene's readers — ray queries (rt_ray_query.hip), shade calls (rt_shade.hip), radiance calls (rt_radiance.hip): they
   // read only the scene, so frames need not wait for them; later readers (they share the counters and staging of their
   // family) and scene updates do

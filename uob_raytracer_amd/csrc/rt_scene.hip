@@ -1,8 +1,9 @@
 // rt_scene.hip — the scene of a context, first and later: rt_init's first scene (scene_first), same-count updates
-// (rt_update_scene*), replacements of any count (rt_replace_scene*), rigid objects posed from a rest pose (rt_set_objects,
-// rt_pose_objects*) and the sphere table (rt_update_spheres).  Every triangle edit is one SceneEdit applied by scene_apply;
-// a new kind of edit adds a source and an entry, not another copy of the flag logic.  No kernel lives here: the device work
-// is rt_scene_update.hip (check, refit), rt_scene_pose.hip and rt_tile_build.hip; the host's tile sort is rt_tile_sort.hip.
+// (rt_update_scene*), replacements of any count (rt_replace_scene*), rigid objects and skins posed from a rest pose
+// (rt_set_objects, rt_pose_objects*, rt_set_skin, rt_pose_skin*) and the sphere table (rt_update_spheres).  Every triangle
+// edit is one SceneEdit applied by scene_apply; a new kind of edit adds a source and an entry, not another copy of the flag
+// logic.  No kernel lives here: the device work is rt_scene_update.hip (check, refit), rt_scene_pose.hip and
+// rt_tile_build.hip; the host's tile sort is rt_tile_sort.hip.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -424,7 +425,7 @@ static int check_scene_args(const rt_ctx* c, const void* v, const void* nr, cons
   }
   const int rc = check_scene_flags(flags, fn);
   if (rc != RT_OK) return rc;
-  if (n > 4000000) { set_error("triangle list of %d exceeds the supported maximum of 4000000", n); return RT_E_UNSUPPORTED; }
+  if (n > kMaxTriangles) { set_error("triangle list of %d exceeds the supported maximum of %d", n, kMaxTriangles); return RT_E_UNSUPPORTED; }
   return RT_OK;
 }
 
@@ -452,33 +453,76 @@ static int device_check(rt_ctx* c, const void* dv, const void* dc, int n, hipStr
   return RT_OK;
 }
 
-// ---- rigid objects (rt_set_objects / rt_pose_objects*): DESIGN.md 4.2b -------------------------------------------------
-// The table and the rest pose live on the context that poses (lead_ctx).  Nothing here runs for a context without a table.
+// ---- rigid objects (rt_set_objects / rt_pose_objects*) and skins (rt_set_skin / rt_pose_skin*): DESIGN.md 4.2b, 4.2d --------
+// The tables and the rest pose live on the context that poses (lead_ctx); a context holds an object table or a skin, which
+// share the rest pose.  Nothing here runs for a context without either.
+// (hipFree waits for a pose still reading what it frees)
+static void free_tables(rt_ctx* L, bool objects, bool skin) {
+  const bool rest = L->nobj == 0 && L->skin_count == 0 && (L->d_rest_verts || L->d_rest_normals);   // no table holds it any more
+  objects = objects && L->d_object_of;
+  skin = skin && (L->d_skin_index || L->d_skin_weights);
+  if (!objects && !skin && !rest) return;
+  DeviceGuard guard;
+  hipSetDevice(L->device);
+  if (objects) { hipFree(L->d_object_of); L->d_object_of = nullptr; }
+  if (skin) { hipFree(L->d_skin_index); hipFree(L->d_skin_weights); L->d_skin_index = nullptr; L->d_skin_weights = nullptr; }
+  if (rest) { hipFree(L->d_rest_verts); hipFree(L->d_rest_normals); L->d_rest_verts = L->d_rest_normals = nullptr; }
+}
+
 static void drop_objects(rt_ctx* c) {
   rt_ctx* L = lead_ctx(c);
   L->nobj = 0;
-  if (!L->d_rest_verts && !L->d_rest_normals && !L->d_object_of) return;
-  DeviceGuard guard;
-  hipSetDevice(L->device);
-  hipFree(L->d_rest_verts); hipFree(L->d_rest_normals); hipFree(L->d_object_of);   // (hipFree waits for a pose still reading them)
-  L->d_rest_verts = L->d_rest_normals = nullptr; L->d_object_of = nullptr;
+  free_tables(L, true, false);
 }
 
-static int check_pose_args(rt_ctx* c, const void* xforms, uint32_t flags, const char* fn) {
+static void drop_skin(rt_ctx* c) {
+  rt_ctx* L = lead_ctx(c);
+  L->skin_first = L->skin_count = L->skin_nbones = 0;
+  free_tables(L, false, true);
+}
+
+// The scene behind the rest pose changes: whichever table the context holds goes
+static void drop_poses(rt_ctx* c) { drop_objects(c); drop_skin(c); }
+
+// The context's current scene becomes the rest pose (the buffers are made on first use and hold n triangles: whatever changes
+// n drops both tables), on L's stream.  The snapshot waits for whatever still writes the scene, and for a pose still reading
+// the old rest pose and the old table (an update's event): the caller's table upload follows on the same stream.
+static int snapshot_rest(rt_ctx* L, const char* fn) {
+  HIP_TRY(hipSetDevice(L->device));
+  const size_t nb = (size_t)L->n * sizeof(float4);
+  if ((!L->d_rest_verts && hipMalloc(&L->d_rest_verts, 3 * nb) != hipSuccess) ||
+      (!L->d_rest_normals && hipMalloc(&L->d_rest_normals, nb) != hipSuccess)) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
+  }
+  const int rc = update_begin(L, L->stream);
+  if (rc != RT_OK) return rc;
+  if (hipMemcpyAsync(L->d_rest_verts, L->d_verts, 3 * nb, hipMemcpyDeviceToDevice, L->stream) != hipSuccess ||
+      hipMemcpyAsync(L->d_rest_normals, L->d_normals, nb, hipMemcpyDeviceToDevice, L->stream) != hipSuccess) {
+    set_error("%s: snapshot failed: %s", fn, hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
+  }
+  return RT_OK;
+}
+
+static int check_pose_args(rt_ctx* c, const void* xforms, uint32_t flags, bool skin, const char* fn) {
   if (!c) { set_error("%s: NULL context", fn); return RT_E_INVALID; }
   if (!xforms) { set_error("%s: the matrices are missing (NULL)", fn); return RT_E_INVALID; }
   const int rc = check_scene_flags(flags, fn);
   if (rc != RT_OK) return rc;
-  if (lead_ctx(c)->nobj == 0) {
+  if (!skin && lead_ctx(c)->nobj == 0) {
     set_error("%s: the context has no object table (rt_set_objects first; a scene update or replace drops it)", fn);
+    return RT_E_INVALID;
+  }
+  if (skin && lead_ctx(c)->skin_count == 0) {
+    set_error("%s: the context has no skin (rt_set_skin first; a scene update or replace drops it)", fn);
     return RT_E_INVALID;
   }
   return RT_OK;
 }
 
-// The rest pose posed by the matrices at d_xforms12 (device memory of the lead device) into the staging scene, on s, and
-// from there into the context as a device edit: the check runs on the staging scene, before anything live is written
-static int pose_from_device(rt_ctx* c, const void* d_xforms12, uint32_t flags, hipStream_t s) {
+// The rest pose posed by the matrices at d_xforms12 (device memory of the lead device: one per object, or one per bone of the
+// skin) into the staging scene, on s, and from there into the context as a device edit: the check runs on the staging scene,
+// before anything live is written
+static int pose_from_device(rt_ctx* c, const void* d_xforms12, uint32_t flags, bool skin, hipStream_t s) {
   rt_ctx* L = lead_ctx(c);
   HIP_TRY(hipSetDevice(L->device));
   const size_t nb = (size_t)L->cap * sizeof(float4);
@@ -487,13 +531,34 @@ static int pose_from_device(rt_ctx* c, const void* d_xforms12, uint32_t flags, h
   if (rc != RT_OK) return rc;
   // the staging scene may still be the source of the previous pose's copies, on whichever streams they run
   for (rt_ctx* k : device_ctxs(c)) HIP_TRY(wait_scene(k, s));
-  launch_pose(L->d_rest_verts, L->d_rest_normals, L->d_object_of, (const float*)d_xforms12, L->n, (float4*)L->pose_verts.p,
-              (float4*)L->pose_normals.p, s);
+  if (skin)
+    launch_skin(L->d_rest_verts, L->d_rest_normals, L->d_skin_index, L->d_skin_weights, (const float*)d_xforms12, L->n,
+                L->skin_first, L->skin_count, (float4*)L->pose_verts.p, (float4*)L->pose_normals.p, s);
+  else
+    launch_pose(L->d_rest_verts, L->d_rest_normals, L->d_object_of, (const float*)d_xforms12, L->n, (float4*)L->pose_verts.p,
+                (float4*)L->pose_normals.p, s);
   HIP_TRY(hipGetLastError());
   SceneEdit e = {L->pose_verts.p, L->pose_normals.p, nullptr, true, L->n, false, false, flags, s, SceneSummary()};
   rc = device_check(c, e.v, L->d_colors, e.n, s, &e.sum);
   if (rc != RT_OK) return rc;
   return scene_apply(c, e);
+}
+
+// rt_pose_objects and rt_pose_skin: the matrices (one per object / per bone) are uploaded, 48 bytes each; blocking
+static int pose_from_host(rt_ctx* c, const float* xforms12, uint32_t flags, bool skin, const char* fn) {
+  int rc = check_pose_args(c, xforms12, flags, skin, fn);
+  if (rc != RT_OK) return rc;
+  rt_ctx* L = lead_ctx(c);
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(L->device));
+  const size_t bytes = (size_t)(skin ? L->skin_nbones : L->nobj) * 12 * sizeof(float);
+  rc = ensure_bytes(&L->pose_xforms, bytes);     // (only the blocking entries use the buffer: nothing can still be reading it)
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(L->pose_xforms.p, xforms12, bytes, hipMemcpyHostToDevice, c->stream));
+  rc = pose_from_device(c, L->pose_xforms.p, flags, skin, c->stream);
+  if (rc != RT_OK) { KeepError keep; hipStreamSynchronize(c->stream); (void)hipGetLastError(); return rc; }
+  HIP_TRY(hipStreamSynchronize(c->stream));      // (the stream of a multi-device handle has waited for every device)
+  return RT_OK;
 }
 
 // rt_update_scene and rt_replace_scene: the arrays are checked once, before any device is touched
@@ -505,12 +570,12 @@ static int edit_from_host(rt_ctx* c, const float* v4, const float* n4, const flo
   e.sum.n_shadow = count_shadow_casters(c4, n);
   vertex_box(v4, n, e.sum.lo, e.sum.hi);
   DeviceGuard guard;
-  drop_objects(c);                             // the scene behind the rest pose changes
+  drop_poses(c);                               // the scene behind the rest pose changes
   return scene_apply(c, e);
 }
 
 // rt_update_scene_device and rt_replace_scene_device: a first pass checks the bound and reduces n_shadow and the box; the
-// live buffers and the object table stay untouched until it has passed
+// live buffers, the object table and the skin stay untouched until it has passed
 static int edit_from_device(rt_ctx* c, const void* dv, const void* dn, const void* dc, int32_t n, uint32_t flags, void* hip_stream,
                             bool replace) {
   int rc = check_scene_args(c, dv, dn, dc, n, flags, replace ? "rt_replace_scene" : "rt_update_scene", replace);
@@ -519,7 +584,7 @@ static int edit_from_device(rt_ctx* c, const void* dv, const void* dn, const voi
   SceneEdit e = {dv, dn, dc, true, n, replace, false, flags, (hipStream_t)hip_stream, SceneSummary()};
   rc = device_check(c, dv, dc, n, e.s, &e.sum);
   if (rc != RT_OK) return rc;
-  drop_objects(c);
+  drop_poses(c);
   return scene_apply(c, e);
 }
 
@@ -547,50 +612,105 @@ int rt_set_objects(rt_ctx* c, const int32_t* first, const int32_t* count, int32_
     }
   }
   DeviceGuard guard;
-  HIP_TRY(hipSetDevice(L->device));
-  const size_t nb = (size_t)n * sizeof(float4);
-  if (!L->d_rest_verts &&      // (a table in force has buffers of this n: whatever changes n drops the table)
-      (hipMalloc(&L->d_rest_verts, 3 * nb) != hipSuccess || hipMalloc(&L->d_rest_normals, nb) != hipSuccess ||
-       hipMalloc(&L->d_object_of, (size_t)n * sizeof(unsigned short)) != hipSuccess)) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
-    drop_objects(c);
-    return RT_E_NOMEM;
+  int rc = snapshot_rest(L, "rt_set_objects");
+  if (rc == RT_OK && !L->d_object_of && hipMalloc(&L->d_object_of, (size_t)n * sizeof(unsigned short)) != hipSuccess) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); rc = RT_E_NOMEM;
   }
-  // the snapshot waits for whatever still writes the scene, and a pose still reading the old rest pose (an update's event)
-  int rc = update_begin(L, L->stream);
   if (rc == RT_OK &&
-      (hipMemcpyAsync(L->d_rest_verts, L->d_verts, 3 * nb, hipMemcpyDeviceToDevice, L->stream) != hipSuccess ||
-       hipMemcpyAsync(L->d_rest_normals, L->d_normals, nb, hipMemcpyDeviceToDevice, L->stream) != hipSuccess ||
-       hipMemcpyAsync(L->d_object_of, object_of.data(), (size_t)n * sizeof(unsigned short), hipMemcpyHostToDevice, L->stream) != hipSuccess ||
+      (hipMemcpyAsync(L->d_object_of, object_of.data(), (size_t)n * sizeof(unsigned short), hipMemcpyHostToDevice, L->stream) != hipSuccess ||
        hipStreamSynchronize(L->stream) != hipSuccess)) {
     set_error("rt_set_objects: snapshot failed: %s", hipGetErrorString(hipGetLastError())); rc = RT_E_DEVICE;
   }
-  if (rc != RT_OK) { KeepError keep; drop_objects(c); return rc; }
+  if (rc != RT_OK) { KeepError keep; drop_poses(c); return rc; }
   L->nobj = nobj;
+  drop_skin(c);                                  // (the rest pose stays: the objects hold it now)
   return RT_OK;
 }
 
 int rt_pose_objects(rt_ctx* c, const float* xforms12, uint32_t flags) {
-  int rc = check_pose_args(c, xforms12, flags, "rt_pose_objects");
-  if (rc != RT_OK) return rc;
-  rt_ctx* L = lead_ctx(c);
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(L->device));
-  const size_t bytes = (size_t)L->nobj * 12 * sizeof(float);
-  rc = ensure_bytes(&L->pose_xforms, bytes);     // (only this blocking entry uses the buffer: nothing can still be reading it)
-  if (rc != RT_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(L->pose_xforms.p, xforms12, bytes, hipMemcpyHostToDevice, c->stream));
-  rc = pose_from_device(c, L->pose_xforms.p, flags, c->stream);
-  if (rc != RT_OK) { KeepError keep; hipStreamSynchronize(c->stream); (void)hipGetLastError(); return rc; }
-  HIP_TRY(hipStreamSynchronize(c->stream));      // (the stream of a multi-device handle has waited for every device)
-  return RT_OK;
+  return pose_from_host(c, xforms12, flags, false, "rt_pose_objects");
 }
 
 int rt_pose_objects_device(rt_ctx* c, const void* d_xforms12, uint32_t flags, void* hip_stream) {
-  const int rc = check_pose_args(c, d_xforms12, flags, "rt_pose_objects_device");
+  const int rc = check_pose_args(c, d_xforms12, flags, false, "rt_pose_objects_device");
   if (rc != RT_OK) return rc;
   DeviceGuard guard;
-  return pose_from_device(c, d_xforms12, flags, (hipStream_t)hip_stream);
+  return pose_from_device(c, d_xforms12, flags, false, (hipStream_t)hip_stream);
+}
+
+int rt_set_skin(rt_ctx* c, int32_t first, int32_t count, const uint16_t* bone_index, const float* weights, int32_t nbones) {
+  if (!c) { set_error("rt_set_skin: NULL context"); return RT_E_INVALID; }
+  if (count == 0) { drop_skin(c); return RT_OK; }
+  if (!bone_index || !weights) { set_error("rt_set_skin: bone_index / weights is NULL"); return RT_E_INVALID; }
+  if (nbones < 1 || nbones > 65535) { set_error("rt_set_skin: nbones = %d outside [1, 65535]", nbones); return RT_E_INVALID; }
+  rt_ctx* L = lead_ctx(c);
+  const int n = L->n;
+  // (the sign and the library's limit of the range first: they bound what the table checks read; then the table, then the
+  // range against the context's scene)
+  if (first < 0 || count < 0 || count > kMaxTriangles) {
+    set_error("rt_set_skin: range [%d, %d + %d) is not a range of triangles (first >= 0, 0 <= count <= %d)", first, first, count,
+              kMaxTriangles);
+    return RT_E_INVALID;
+  }
+  const size_t corners = 3 * (size_t)count;
+  for (size_t k = 0; k < corners; ++k)
+    for (int j = 0; j < 4; ++j) {
+      if ((int32_t)bone_index[4 * k + j] >= nbones) {
+        set_error("rt_set_skin: corner %zu (triangle %zu): bone index %d is not below nbones = %d", k, (size_t)first + k / 3,
+                  (int)bone_index[4 * k + j], nbones);
+        return RT_E_INVALID;
+      }
+      if (!(weights[4 * k + j] >= 0.0f && weights[4 * k + j] <= 1.0f)) {
+        set_error("rt_set_skin: corner %zu (triangle %zu): weight %g is not in [0, 1]", k, (size_t)first + k / 3,
+                  (double)weights[4 * k + j]);
+        return RT_E_INVALID;
+      }
+    }
+  if (first >= n || count > n - first) {
+    set_error("rt_set_skin: range [%d, %d + %d) is not inside the context's %d triangles", first, first, count, n);
+    return RT_E_INVALID;
+  }
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(L->device));
+  ushort4* index = nullptr;                      // the new table: the old one stays in force until everything has succeeded
+  float4* wts = nullptr;
+  if (hipMalloc(&index, corners * sizeof(ushort4)) != hipSuccess || hipMalloc(&wts, corners * sizeof(float4)) != hipSuccess) {
+    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
+    KeepError keep;
+    hipFree(index); hipFree(wts);                // (nothing of the context has been touched: its table and rest pose stay)
+    return RT_E_NOMEM;
+  }
+  int rc = snapshot_rest(L, "rt_set_skin");
+  if (rc == RT_OK &&
+      (hipMemcpyAsync(index, bone_index, corners * sizeof(ushort4), hipMemcpyHostToDevice, L->stream) != hipSuccess ||
+       hipMemcpyAsync(wts, weights, corners * sizeof(float4), hipMemcpyHostToDevice, L->stream) != hipSuccess ||
+       hipStreamSynchronize(L->stream) != hipSuccess)) {
+    set_error("rt_set_skin: upload failed: %s", hipGetErrorString(hipGetLastError())); rc = RT_E_DEVICE;
+  }
+  if (rc != RT_OK) { KeepError keep; hipFree(index); hipFree(wts); drop_poses(c); return rc; }   // (the snapshot has begun: the rest pose may be half written)
+  hipFree(L->d_skin_index); hipFree(L->d_skin_weights);
+  L->d_skin_index = index; L->d_skin_weights = wts;
+  L->skin_first = first; L->skin_count = count; L->skin_nbones = nbones;
+  drop_objects(c);                               // (the rest pose stays: the skin holds it now)
+  return RT_OK;
+}
+
+int rt_pose_skin(rt_ctx* c, const float* bones12, uint32_t flags) {
+  return pose_from_host(c, bones12, flags, true, "rt_pose_skin");
+}
+
+int rt_pose_skin_device(rt_ctx* c, const void* d_bones12, uint32_t flags, void* hip_stream) {
+  const int rc = check_pose_args(c, d_bones12, flags, true, "rt_pose_skin_device");
+  if (rc != RT_OK) return rc;
+  DeviceGuard guard;
+  return pose_from_device(c, d_bones12, flags, true, (hipStream_t)hip_stream);
+}
+
+int rt_debug_skin_info(rt_ctx* c, int32_t* first, int32_t* count, int32_t* nbones) {
+  if (!c || !first || !count || !nbones) { set_error("rt_debug_skin_info: NULL argument"); return RT_E_INVALID; }
+  const rt_ctx* L = lead_ctx(c);
+  *first = L->skin_first; *count = L->skin_count; *nbones = L->skin_nbones;
+  return RT_OK;
 }
 
 int rt_debug_object_count(rt_ctx* c, int32_t* out) {

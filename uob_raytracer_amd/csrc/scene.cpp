@@ -99,6 +99,34 @@ void rt_scene_transform(rt_triangle* tris, int32_t n, int32_t first, int32_t cou
   }
 }
 
+// The skin arithmetic (include/uob_rt.h "skinned meshes"): what rt_scene_pose.hip rt_skin_triangles computes on the device,
+// term by term.  All four influences of a corner are evaluated, whatever their weights.
+void rt_scene_skin(rt_triangle* tris, int32_t n, int32_t first, int32_t count, const uint16_t* bone_index, const float* weights,
+                   const float* bones12, int32_t nbones) {
+  if (!tris || !bone_index || !weights || !bones12 || first < 0 || count < 0 || first > n || count > n - first) return;
+  for (size_t k = 0; k < (size_t)count * 12; ++k)
+    if ((int32_t)bone_index[k] >= nbones) return;
+  for (int i = first; i < first + count; ++i) {
+    rt_triangle& t = tris[i];
+    int corner = 3 * (i - first);
+    for (float* v : {t.v0, t.v1, t.v2}) {
+      const uint16_t* j = bone_index + 4 * (size_t)corner;
+      const float* w = weights + 4 * (size_t)corner;
+      const float x = v[0], y = v[1], z = v[2];
+      for (int r = 0; r < 3; ++r) {
+        float p[4];
+        for (int k = 0; k < 4; ++k) {
+          const float* m = bones12 + 12 * (size_t)j[k] + 4 * r;
+          p[k] = ((x * m[0] + y * m[1]) + z * m[2]) + m[3];
+        }
+        v[r] = ((w[0] * p[0] + w[1] * p[1]) + w[2] * p[2]) + w[3] * p[3];
+      }
+      ++corner;
+    }
+    rt_triangle_compute_normal(&t);
+  }
+}
+
 int rt_scene_cornell_box(rt_triangle* out, int32_t cap) {
   if (!out || cap < 0) { uobrt::set_error("rt_scene_cornell_box: bad arguments"); return RT_E_INVALID; }
   const float L = 555;   // side of the Cornell Box, TestModelH.h:69

@@ -35,6 +35,7 @@ EXPORTS = (
     "rt_replace_scene", "rt_replace_scene_device", "rt_update_spheres", "rt_debug_scene_capacity",
     "rt_scene_transform", "rt_set_objects", "rt_pose_objects", "rt_pose_objects_device", "rt_debug_object_count",
     "rt_debug_scene_data",
+    "rt_scene_skin", "rt_set_skin", "rt_pose_skin", "rt_pose_skin_device", "rt_debug_skin_info",
 )
 
 # rt_debug_trace_stats slots (include/uob_rt.h)
@@ -86,6 +87,13 @@ def lib():
         L.rt_pose_objects.argtypes = [vp, fp, C.c_uint32]
         L.rt_pose_objects_device.argtypes = [vp, vp, C.c_uint32, vp]
         L.rt_debug_object_count.argtypes = [vp, C.POINTER(C.c_int32)]
+        L.rt_scene_skin.argtypes = [C.POINTER(abi.RtTriangle), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), fp, fp,
+                                    C.c_int32]
+        L.rt_scene_skin.restype = None
+        L.rt_set_skin.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), fp, C.c_int32]
+        L.rt_pose_skin.argtypes = [vp, fp, C.c_uint32]
+        L.rt_pose_skin_device.argtypes = [vp, vp, C.c_uint32, vp]
+        L.rt_debug_skin_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.rt_render.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(C.c_uint32), fp]
         L.rt_render_device.argtypes = [vp, fp, fp, fp, C.c_float, vp, vp, vp]
         L.rt_count_work.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(abi.RtWork)]
@@ -212,6 +220,19 @@ def _object_ranges(ranges, n):
     return out
 
 
+def _skin_table(count, bone_index, weights):
+    """The influence table of set_skin / Scene.skinned as (uint16 [3*count,4], float32 [3*count,4]), C-contiguous."""
+    idx = np.asarray(bone_index)
+    if idx.shape != (3 * count, 4) or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError("bone_index must be an integer array of shape [%d, 4]" % (3 * count))
+    if idx.size and (idx.min() < 0 or idx.max() > 0xFFFF):
+        raise ValueError("bone indices must be in 0 .. 65535")
+    w = np.ascontiguousarray(weights, np.float32)
+    if w.shape != (3 * count, 4):
+        raise ValueError("weights must have shape [%d, 4]" % (3 * count))
+    return np.ascontiguousarray(idx, np.uint16), w
+
+
 class Scene:
     """Triangle list in the reference's AoS format (TestModelH.h:11-38): array [n,5,4] = v0,v1,v2,normal,color."""
 
@@ -272,6 +293,20 @@ class Scene:
             lib().rt_scene_transform(tris, len(self), first, count, _fp(np.ascontiguousarray(x)))
         return Scene(aos)
 
+    def skinned(self, first, count, bone_index, weights, bones):
+        """The scene S(self, bones) of include/uob_rt.h "skinned meshes": the triangles [first, first + count) blended from
+        bones ([nbones,3,4]: matrix | translation) by the influence table (bone_index, weights: [3*count,4], one row per
+        corner) with rt_scene_skin, the host restatement of RayTracer.pose_skin."""
+        first, count = int(first), int(count)
+        idx, w = _skin_table(count, bone_index, weights)
+        b = np.ascontiguousarray(bones, np.float32)
+        if b.ndim != 3 or b.shape[1:] != (3, 4):
+            raise ValueError("bones must have shape [nbones, 3, 4]")
+        aos = self.aos.copy()
+        lib().rt_scene_skin(aos.ctypes.data_as(C.POINTER(abi.RtTriangle)), len(self), first, count,
+                            idx.ctypes.data_as(C.POINTER(C.c_uint16)), _fp(w), _fp(b), b.shape[0])
+        return Scene(aos)
+
     def packed(self):
         """The three float4 arrays uploaded at skeleton.cpp:474-496."""
         n = len(self)
@@ -298,6 +333,7 @@ class RayTracer:
         self.n_triangles = len(scene)
         self.rows = lib().rt_config_owned_rows(C.byref(cfg))
         self.objects = None         # the (first, count) ranges of set_objects; a scene update or replace forgets them
+        self.skin = None            # (first, count, nbones) of set_skin; forgotten likewise, and by set_objects
         # the device the context's queries run on (devices[0]; None: the device that was current at rt_init)
         self.device = cfg.devices[0] if cfg.num_devices >= 1 else (cfg.device if cfg.device >= 0 else None)
 
@@ -312,14 +348,14 @@ class RayTracer:
         _check(lib().rt_update_scene(self._h, _fp(v), _fp(nr), _fp(c), len(scene), self._update_flags(reorder, device_tiles)))
         self.scene = scene
         self._keep = (v, nr, c)
-        self.objects = None
+        self.objects = self.skin = None
 
     def update_scene_device(self, v_ptr, n_ptr, c_ptr, n, stream=None, reorder=False, device_tiles=False):
         """The same from device memory (raw pointers, e.g. torch .data_ptr() of float32 [3n,4] / [n,4] / [n,4]), enqueued
         on `stream` (rt_update_scene_device).  The source buffers must stay unchanged until the stream has passed it."""
         _check(lib().rt_update_scene_device(self._h, C.c_void_p(v_ptr), C.c_void_p(n_ptr), C.c_void_p(c_ptr), n,
                                             self._update_flags(reorder, device_tiles), C.c_void_p(stream or 0)))
-        self.objects = None
+        self.objects = self.skin = None
 
     def replace_scene(self, scene, device_tiles=False):
         """Replace the context's triangles by a scene of any count (rt_replace_scene), blocking.  scene: a Scene, or the three
@@ -337,7 +373,7 @@ class RayTracer:
         self.scene = scene
         self._keep = (v, nr, c)
         self.n_triangles = n
-        self.objects = None
+        self.objects = self.skin = None
 
     def replace_scene_device(self, vertices, normals, colors, stream=None, reorder=False):
         """The same from torch tensors on the context's device (float32 [3n,4] / [n,4] / [n,4]), enqueued on `stream` (a torch
@@ -357,7 +393,7 @@ class RayTracer:
                                              C.c_void_p(raw)))
         self.scene = None
         self.n_triangles = n
-        self.objects = None
+        self.objects = self.skin = None
 
     def set_objects(self, ranges):
         """Make the context's current scene the rest pose of rigid objects (rt_set_objects): ranges = a list of
@@ -368,6 +404,8 @@ class RayTracer:
         ip = C.POINTER(C.c_int32)
         _check(lib().rt_set_objects(self._h, first.ctypes.data_as(ip), count.ctypes.data_as(ip), len(ranges)))
         self.objects = ranges or None
+        if ranges:
+            self.skin = None
 
     def object_count(self):
         """Objects in the context's table (rt_debug_object_count)."""
@@ -394,6 +432,50 @@ class RayTracer:
         raw = self._raw_stream(stream, dev)
         _check(lib().rt_pose_objects_device(self._h, C.c_void_p(xforms.data_ptr()), self._update_flags(reorder, device_tiles),
                                             C.c_void_p(raw)))
+        self.scene = None
+
+    def set_skin(self, first, count, bone_index, weights, nbones):
+        """Make the context's current scene the rest pose of a skin (rt_set_skin): the triangles [first, first + count) with
+        four influences per corner, bone_index (integers < nbones) and weights (in [0, 1]) of shape [3*count, 4], one row per
+        corner in the order corner 0, 1, 2 of triangle first, then of first + 1, ...  Drops the objects; count = 0 drops
+        the skin."""
+        first, count, nbones = int(first), int(count), int(nbones)
+        if count > 0:
+            idx, w = _skin_table(count, bone_index, weights)
+        else:                           # (count = 0 drops the skin; a negative count is the library's to reject)
+            idx, w = np.zeros((1, 4), np.uint16), np.zeros((1, 4), np.float32)
+        _check(lib().rt_set_skin(self._h, first, count, idx.ctypes.data_as(C.POINTER(C.c_uint16)), _fp(w), nbones))
+        if count == 0:
+            self.skin = None
+        else:
+            self.objects, self.skin = None, (first, count, nbones)
+
+    def skin_info(self):
+        """(first, count, nbones) of the context's skin, zeros without one (rt_debug_skin_info)."""
+        out = [C.c_int32() for _ in range(3)]
+        _check(lib().rt_debug_skin_info(self._h, *[C.byref(x) for x in out]))
+        return tuple(int(x.value) for x in out)
+
+    def pose_skin(self, bones, reorder=False, device_tiles=False):
+        """Pose the skin from the rest pose (rt_pose_skin), blocking: bones = array [nbones, 3, 4], per bone the matrix and, in
+        the last column, the translation.  The tiles are refitted, or made again with reorder / device_tiles as in
+        update_scene.  The context then holds Scene.skinned(first, count, bone_index, weights, bones) of the rest scene."""
+        b = np.ascontiguousarray(bones, np.float32)
+        if self.skin and b.shape != (self.skin[2], 3, 4):       # (without a skin the library says so)
+            raise ValueError("bones must have shape [%d, 3, 4]" % self.skin[2])
+        _check(lib().rt_pose_skin(self._h, _fp(b), self._update_flags(reorder, device_tiles)))
+        self.scene = None
+
+    def pose_skin_device(self, bones, stream=None, device_tiles=False, reorder=False):
+        """The same with the bones in a torch tensor float32 [nbones, 3, 4] on the context's device, enqueued on `stream` (a
+        torch stream or a raw hipStream_t; default: torch's current stream) (rt_pose_skin_device).  The tensor must stay
+        unchanged until the stream has passed the call."""
+        dev = self._torch_device()
+        if self.skin:
+            _need("bones", bones, _torch.float32, (self.skin[2], 3, 4), dev)
+        raw = self._raw_stream(stream, dev)
+        _check(lib().rt_pose_skin_device(self._h, C.c_void_p(bones.data_ptr()), self._update_flags(reorder, device_tiles),
+                                         C.c_void_p(raw)))
         self.scene = None
 
     def update_spheres(self, spheres):
