@@ -531,7 +531,15 @@ int rt_selftest_rcp(uint64_t out[64]);
  * out[0] mismatches of (a), out[1] mismatches of (b), out[2] pairs checked by (b), out[3] / out[4] a mismatching pattern each. */
 int rt_selftest_normalize(uint64_t out[8], uint32_t b_stride);
 
+/* Releases everything the context holds: it waits for the context's streams and side calls, then frees its device memory,
+ * events and streams (and those of every device of a multi-device context), and unregisters a registered output.   */
 void rt_destroy(rt_ctx* ctx);
+
+/* Diagnostic: the device objects the library holds at this moment in this process, over all contexts: out[0] device
+ * allocations, out[1] their bytes, out[2] events, out[3] streams.  A process without a context reports zeros, and so does one
+ * whose every context has been destroyed; calls documented to allocate nothing leave the figures unchanged.  Takes no
+ * context and needs no device.                                                                                          */
+int rt_debug_live_device_objects(int64_t out[4]);
 /* Message of the last failure on the calling thread.  After an RT_OK from rt_init / rt_render_device of a multi-device
  * context it may instead hold a line that starts with "warning:" — a device without peer access to the root device
  * works, through slower copies (band by band), and says so here.                                                      */

@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -131,7 +132,7 @@ static int init_parent(const rt_config* cfg, const float* vertices4, const float
     if (cfg->devices[d] < 0 || cfg->devices[d] >= ndev) {
       set_error("devices[%d] = %d, but %d HIP device(s) are present", d, cfg->devices[d], ndev); return RT_E_INVALID;
     }
-  rt_ctx* p = new (std::nothrow) rt_ctx();
+  std::unique_ptr<rt_ctx> p(new (std::nothrow) rt_ctx());   // a failure below deletes it, its children included
   if (!p) { set_error("out of host memory"); return RT_E_NOMEM; }
   std::string downgrade;                     // devices that will copy band by band (reported through rt_last_error)
   p->cfg = *cfg;
@@ -146,10 +147,10 @@ static int init_parent(const rt_config* cfg, const float* vertices4, const float
     kc.band_rows = dbr; kc.band_index = d; kc.band_count = cfg->num_devices;
     rt_ctx* k = nullptr;
     const int rc = rt_init(&kc, vertices4, normals4, colors4, n, &k);
-    if (rc != RT_OK) { rt_destroy(p); return rc; }
+    if (rc != RT_OK) return rc;
     p->kids.push_back(k);
-    if (hipSetDevice(k->device) != hipSuccess || hipEventCreateWithFlags(&k->ev_done, hipEventDisableTiming) != hipSuccess) {
-      set_error("event creation failed on device %d", k->device); rt_destroy(p); return RT_E_DEVICE;
+    if (hipSetDevice(k->device) != hipSuccess || k->ev_done.create(hipEventDisableTiming) != hipSuccess) {
+      set_error("event creation failed on device %d", k->device); return RT_E_DEVICE;
     }
     if (k->device != p->device) {           // let the copy engines of this device write the root's memory directly
       int can = 0;
@@ -169,13 +170,13 @@ static int init_parent(const rt_config* cfg, const float* vertices4, const float
       }
     }
   }
-  if (hipSetDevice(p->device) != hipSuccess || hipEventCreateWithFlags(&p->ev_go, hipEventDisableTiming) != hipSuccess ||
-      hipStreamCreate(&p->stream) != hipSuccess || hipEventCreate(&p->ev0) != hipSuccess || hipEventCreate(&p->ev1) != hipSuccess) {
-    set_error("stream/event creation failed on device %d", p->device); rt_destroy(p); return RT_E_DEVICE;
+  if (hipSetDevice(p->device) != hipSuccess || p->ev_go.create(hipEventDisableTiming) != hipSuccess ||
+      p->stream.create() != hipSuccess || p->ev0.create() != hipSuccess || p->ev1.create() != hipSuccess) {
+    set_error("stream/event creation failed on device %d", p->device); return RT_E_DEVICE;
   }
   // RT_OK with a "warning: ..." line in rt_last_error(): the context works, through the slower copies
   if (!downgrade.empty()) set_error("%s: their bands are copied band by band (hipMemcpyPeerAsync)", downgrade.c_str());
-  *out_ctx = p;
+  *out_ctx = p.release();
   return RT_OK;
 }
 
@@ -194,23 +195,20 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (ndev < 1) { set_error("no HIP device present"); return RT_E_DEVICE; }
-  rt_ctx* c = new (std::nothrow) rt_ctx();
+  std::unique_ptr<rt_ctx> c(new (std::nothrow) rt_ctx());   // a failure below deletes it (declared after the guard)
   if (!c) { set_error("out of host memory"); return RT_E_NOMEM; }
   c->cfg = *cfg;
   c->tune = read_tuning(*cfg);
   if (cfg->num_devices == 1) c->device = cfg->devices[0];
   else if (cfg->device >= 0) c->device = cfg->device;
   else hipGetDevice(&c->device);
-  auto fail = [&](int code) { rt_destroy(c); return code; };
-  if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", c->device); return fail(RT_E_DEVICE); }
+  if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", c->device); return RT_E_DEVICE; }
   c->owned_rows = rt_config_owned_rows(cfg);
   if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || c->cus < 1) c->cus = 256;
   const size_t px = (size_t)(c->owned_rows > 0 ? c->owned_rows : 1) * cfg->width;
-  if (hipMalloc(&c->d_argb, px * 4) != hipSuccess || hipMalloc(&c->d_counters, sizeof(rt_work)) != hipSuccess ||
-      hipMalloc(&c->d_jobctr, (2 * kJobHeads + 2) * kJobHeadStride * sizeof(unsigned int)) != hipSuccess ||
-      hipMalloc(&c->d_spheres, RT_MAX_SPHERES * sizeof(DevSphere)) != hipSuccess) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return fail(RT_E_NOMEM);
-  }
+  if (c->d_argb.alloc(px) != hipSuccess || c->d_counters.alloc(sizeof(rt_work) / sizeof(unsigned long long)) != hipSuccess ||
+      c->d_jobctr.alloc((2 * kJobHeads + 2) * kJobHeadStride) != hipSuccess || c->d_spheres.alloc(RT_MAX_SPHERES) != hipSuccess)
+    return alloc_failed();
   {   // wave kernel: lists of last frame's expensive jobs (sized for the smallest job, one 64-ray task)
     const int aa = cfg->aa_x * cfg->aa_y;
     const int pt = (aa >= 1 && aa <= 64) ? 64 / aa : 16;        // smallest job: one task; more than 64 AA samples: 16 pixels
@@ -218,15 +216,15 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
     c->heavy_cap = (int)(jobs_max / 3 > 64 ? jobs_max / 3 : 64);
     c->heavy_jobs_max = jobs_max;
   }
-  if (hipStreamCreate(&c->stream) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
-    set_error("stream/event creation failed"); return fail(RT_E_DEVICE);
+  if (c->stream.create() != hipSuccess || c->ev0.create() != hipSuccess || c->ev1.create() != hipSuccess) {
+    set_error("stream/event creation failed"); return RT_E_DEVICE;
   }
-  rc = upload_spheres(c);
-  if (rc != RT_OK) return fail(rc);
+  rc = upload_spheres(c.get());
+  if (rc != RT_OK) return rc;
   // the scene: buffers by n, upload, tiles, n_shadow, scene box, kernel family — the routine every later edit goes through (rt_scene.hip)
-  rc = scene_first(c, vertices4, normals4, colors4, n);
-  if (rc != RT_OK) return fail(rc);
-  *out_ctx = c;
+  rc = scene_first(c.get(), vertices4, normals4, colors4, n);
+  if (rc != RT_OK) return rc;
+  *out_ctx = c.release();
   return RT_OK;
 }
 
@@ -400,12 +398,12 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
     if (c->tune.timeline) {                 // diagnostic: the shipped kernel, with its per-wave start / end stamps
       const size_t waves = (size_t)P.wave_blocks * 4;
       if (!c->d_timeline) {
-        if (hipMalloc(&c->d_timeline, waves * 3 * sizeof(uint64_t)) != hipSuccess) { set_error("hipMalloc failed (timeline)"); return RT_E_NOMEM; }
+        if (c->d_timeline.alloc(waves * 3) != hipSuccess) { set_error("hipMalloc failed (timeline)"); return RT_E_NOMEM; }
         c->timeline_waves = waves;
       }
       if (c->timeline_waves >= waves) {
         HIP_TRY(hipMemsetAsync(c->d_timeline, 0, c->timeline_waves * 3 * sizeof(uint64_t), stream));
-        P.counters = reinterpret_cast<unsigned long long*>(c->d_timeline);
+        P.counters = reinterpret_cast<unsigned long long*>(c->d_timeline.p);
         c->timeline_valid = true;
       }
     }
@@ -526,7 +524,7 @@ static int parent_render(rt_ctx* p, const float rot[12], const float cam[3], con
     rt_ctx* c = p->kids[k];
     if (c->owned_rows == 0) continue;
     if (hipSetDevice(c->device) != hipSuccess) { set_error("hipSetDevice(%d) failed", c->device); return fail(RT_E_DEVICE); }
-    if (want_rgb && !c->d_rgb && hipMalloc(&c->d_rgb, (size_t)c->owned_rows * W * sizeof(float4)) != hipSuccess) {
+    if (want_rgb && !c->d_rgb && c->d_rgb.alloc((size_t)c->owned_rows * W) != hipSuccess) {
       set_error("hipMalloc failed (float tap, device %d)", c->device); return fail(RT_E_NOMEM);
     }
     if (!to_host && hipStreamWaitEvent(c->stream, p->ev_go, 0) != hipSuccess) { set_error("hipStreamWaitEvent failed"); return fail(RT_E_DEVICE); }
@@ -592,7 +590,7 @@ int rt_render(rt_ctx* c, const float rot[12], const float cam[3], const float li
   const size_t px = (size_t)c->owned_rows * c->cfg.width;
   if (out_rgb_f32 && !c->d_rgb) {
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMalloc(&c->d_rgb, (px ? px : 1) * sizeof(float4)));
+    HIP_TRY(c->d_rgb.alloc(px));
   }
   if (c->reg_host && !out_rgb_f32 && px != 0 && (char*)out_argb >= c->reg_host &&
       (char*)out_argb + px * 4 <= c->reg_host + c->reg_bytes) {
@@ -763,34 +761,25 @@ int rt_debug_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float
   const float zero3[3] = {0.f, 0.f, 0.f};
   FrameParams P;
   scene_params(c, zero3, false, &P);
-  float *d_rays = nullptr, *d_r2 = nullptr, *d_out = nullptr;
-  int* d_tri = nullptr;
-  int rc = RT_OK;
-  if (hipMalloc(&d_rays, (size_t)nray * 24) != hipSuccess || hipMalloc(&d_tri, (size_t)nray * 4) != hipSuccess ||
-      (radius_sq && hipMalloc(&d_r2, (size_t)nray * 4) != hipSuccess) || (out10 && hipMalloc(&d_out, (size_t)nray * 40) != hipSuccess)) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); rc = RT_E_NOMEM;
-  }
-  auto ok = [&](hipError_t e, const char* opn) {
-    if (rc == RT_OK && e != hipSuccess) { set_error("%s failed: %s", opn, hipGetErrorString(e)); rc = RT_E_DEVICE; }
-  };
-  if (rc == RT_OK) {
-    if (c->timed) ok(hipStreamWaitEvent(c->stream, c->ev1, 0), "hipStreamWaitEvent");
-    ok(wait_aov(c, c->stream), "hipStreamWaitEvent");
-    ok(wait_scene(c, c->stream), "hipStreamWaitEvent");
-    ok(hipMemcpyAsync(d_rays, rays6, (size_t)nray * 24, hipMemcpyHostToDevice, c->stream), "ray upload");
-    if (radius_sq) ok(hipMemcpyAsync(d_r2, radius_sq, (size_t)nray * 4, hipMemcpyHostToDevice, c->stream), "ray upload");
-    if (d_out) ok(hipMemsetAsync(d_out, 0, (size_t)nray * 40, c->stream), "hipMemsetAsync");
-    if (rc == RT_OK) {
-      if (generic_needs_records(c->n)) launch_stage_records(P, c->stream);
-      launch_trace_rays(P, what, d_rays, d_r2, (long)nray, d_tri, d_out, c->stream);
-      ok(hipGetLastError(), "trace kernel launch");
-    }
-    ok(hipMemcpyAsync(out_tri, d_tri, (size_t)nray * 4, hipMemcpyDeviceToHost, c->stream), "read-back");
-    if (out10 && what == RT_TRACE_CLOSEST_HIT) ok(hipMemcpyAsync(out10, d_out, (size_t)nray * 40, hipMemcpyDeviceToHost, c->stream), "read-back");
-    ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
-  }
-  hipFree(d_rays); hipFree(d_r2); hipFree(d_out); hipFree(d_tri);
-  return rc;
+  DevMem<float> d_rays, d_r2, d_out;           // (after the guard: freed while the context's device is current)
+  DevMem<int> d_tri;
+  const size_t n = (size_t)nray;
+  if (d_rays.alloc(n * 6) != hipSuccess || d_tri.alloc(n) != hipSuccess || (radius_sq && d_r2.alloc(n) != hipSuccess) ||
+      (out10 && d_out.alloc(n * 10) != hipSuccess))
+    return alloc_failed();
+  if (c->timed) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev1, 0));
+  HIP_TRY(wait_aov(c, c->stream));
+  HIP_TRY(wait_scene(c, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_rays, rays6, n * 24, hipMemcpyHostToDevice, c->stream));
+  if (radius_sq) HIP_TRY(hipMemcpyAsync(d_r2, radius_sq, n * 4, hipMemcpyHostToDevice, c->stream));
+  if (d_out) HIP_TRY(hipMemsetAsync(d_out, 0, n * 40, c->stream));
+  if (generic_needs_records(c->n)) launch_stage_records(P, c->stream);
+  launch_trace_rays(P, what, d_rays, d_r2, (long)nray, d_tri, d_out, c->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_tri, d_tri, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (out10 && what == RT_TRACE_CLOSEST_HIT) HIP_TRY(hipMemcpyAsync(out10, d_out, n * 40, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));    // (on an earlier failure the owners' hipFree waits for what was enqueued)
+  return RT_OK;
 }
 
 int rt_debug_band_copy_plan(int32_t num_devices, int32_t k, int32_t device_band_rows, int32_t width, int32_t height,
@@ -863,39 +852,28 @@ int rt_last_kernel_ms(rt_ctx* c, float* out_ms) {
   return RT_OK;
 }
 
+int rt_debug_live_device_objects(int64_t out[4]) {
+  if (!out) { set_error("rt_debug_live_device_objects: NULL argument"); return RT_E_INVALID; }
+  for (int k = 0; k < 4; ++k) out[k] = g_live[k].load(std::memory_order_relaxed);
+  return RT_OK;
+}
+
 void rt_destroy(rt_ctx* c) {
   if (!c) return;
   DeviceGuard guard;
-  for (rt_ctx* k : c->kids) rt_destroy(k);
-  hipSetDevice(c->device);
-  if (c->stream) { hipStreamSynchronize(c->stream); hipStreamDestroy(c->stream); }
-  if (c->ev0) hipEventDestroy(c->ev0);
-  if (c->ev1) hipEventDestroy(c->ev1);
-  if (c->aux_stream) { hipStreamSynchronize(c->aux_stream); hipStreamDestroy(c->aux_stream); }
-  if (c->ev_fork) hipEventDestroy(c->ev_fork);
-  if (c->ev_join) hipEventDestroy(c->ev_join);
-  if (c->ev_go) hipEventDestroy(c->ev_go);
-  if (c->ev_done) hipEventDestroy(c->ev_done);
-  if (c->ev_upd) hipEventDestroy(c->ev_upd);
-  for (SideCall* k : {&c->query, &c->shade, &c->rad, &c->aov}) {     // no call of any family may still be running
-    if (k->ev) { hipEventSynchronize(k->ev); hipEventDestroy(k->ev); }
-    hipFree(k->d_stats); hipFree(k->io.p);
-  }
-  hipFree(c->d_qrecords); hipFree(c->rrec.p);
-  hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);
-  hipFree(c->d_argb); hipFree(c->d_rgb); hipFree(c->d_counters); hipFree(c->d_jobctr);
-  // (what a replaced scene may drop and regain is owned by the store; the working pointers are aliases)
-  const SceneStore& o = c->own;
-  hipFree(o.records); hipFree(o.screen_masks); hipFree(o.world_masks); hipFree(o.world_occ);
-  if (c->reg_host && c->reg_owner) hipHostUnregister(c->reg_host);
-  hipFree(o.heavy[0]); hipFree(o.heavy[1]); hipFree(o.heavy_flags); hipFree(c->d_timeline);
-  hipFree(o.mesh_cost); hipFree(o.mesh_order); hipFree(c->d_spheres);
-  hipFree(o.verts_m); hipFree(o.normals_m); hipFree(o.colors_m); hipFree(o.orig); hipFree(o.tile_box);
-  hipFree(c->d_check); hipFree(c->tile_scratch.p);
-  hipFree(c->d_rest_verts); hipFree(c->d_rest_normals); hipFree(c->d_object_of);
-  hipFree(c->d_skin_index); hipFree(c->d_skin_weights);
-  hipFree(c->pose_verts.p); hipFree(c->pose_normals.p); hipFree(c->pose_xforms.p);
   delete c;
 }
 
 }  // extern "C"
+
+// What only the context can do before its members release themselves: the children first, then its own device current and
+// nothing of it still running
+rt_ctx::~rt_ctx() {
+  for (rt_ctx* k : kids) delete k;
+  hipSetDevice(device);
+  if (stream) hipStreamSynchronize(stream);
+  if (aux_stream) hipStreamSynchronize(aux_stream);
+  for (SideCall* k : {&query, &shade, &rad, &aov})     // no call of any family may still be running
+    if (k->ev) hipEventSynchronize(k->ev);
+  if (reg_host && reg_owner) hipHostUnregister(reg_host);
+}

@@ -15,21 +15,16 @@ using namespace uobrt;
 // whatever still uses the old buffer has finished before it goes.
 int uobrt::ensure_bytes(DevBuffer* b, size_t bytes) {
   if (bytes <= b->bytes) return RT_OK;
-  hipFree(b->p);
-  b->p = nullptr; b->bytes = 0;
-  if (hipMalloc(&b->p, bytes) != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
-  b->bytes = bytes;
-  return RT_OK;
+  b->reset();
+  return b->alloc(bytes) == hipSuccess ? RT_OK : alloc_failed();
 }
 
 // ---- around a call -------------------------------------------------------------------------------------------------------
 // Before anything of a call is enqueued: the device, and the family's event and counters on first use
-static int call_prepare(rt_ctx* c, SideCall* k, size_t stats_bytes) {
+static int call_prepare(rt_ctx* c, SideCall* k, int stats_words) {
   HIP_TRY(hipSetDevice(c->device));
-  if (!k->ev) HIP_TRY(hipEventCreateWithFlags(&k->ev, hipEventDisableTiming));
-  if (!k->d_stats && hipMalloc(&k->d_stats, stats_bytes) != hipSuccess) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
-  }
+  if (!k->ev) HIP_TRY(k->ev.create(hipEventDisableTiming));
+  if (!k->d_stats && k->d_stats.alloc((size_t)stats_words) != hipSuccess) return alloc_failed();
   return RT_OK;
 }
 
@@ -37,7 +32,7 @@ static int call_prepare(rt_ctx* c, SideCall* k, size_t stats_bytes) {
 // counters zeroed
 static int reader_begin(rt_ctx* c, SideCall* k, int stats_words, hipStream_t s) {
   const size_t stats_bytes = (size_t)stats_words * sizeof(unsigned long long);
-  const int rc = call_prepare(c, k, stats_bytes);
+  const int rc = call_prepare(c, k, stats_words);
   if (rc != RT_OK) return rc;
   HIP_TRY(wait_scene(c, s));
   if (wait_scene_readers(c, s) != RT_OK) return RT_E_DEVICE;
@@ -127,9 +122,7 @@ static int enqueue_query(rt_ctx* c, int32_t what, const float* d_rays, const flo
   const bool records = !tiled && generic_needs_records(c->n);
   const int rc = reader_begin(c, &c->query, query_stats_words(), s);
   if (rc != RT_OK) return rc;
-  if (records && !c->d_qrecords && hipMalloc(&c->d_qrecords, (size_t)c->cap * kRecordsPerTriangle * sizeof(float4)) != hipSuccess) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
-  }
+  if (records && !c->d_qrecords && c->d_qrecords.alloc((size_t)c->cap * kRecordsPerTriangle) != hipSuccess) return alloc_failed();
   const float zero3[3] = {0.f, 0.f, 0.f};
   FrameParams P;
   scene_params(c, zero3, tiled, &P);
@@ -204,7 +197,7 @@ static int enqueue_aov(rt_ctx* c, const float rot[12], const float cam[3], float
   const int rows = whole ? c->cfg.height : c->owned_rows;
   if (rows == 0) return RT_OK;
   const size_t stats_bytes = (size_t)aov_stats_words() * sizeof(unsigned long long);
-  const int rc = call_prepare(c, &c->aov, stats_bytes);
+  const int rc = call_prepare(c, &c->aov, aov_stats_words());
   if (rc != RT_OK) return rc;
   const float zero3[3] = {0.f, 0.f, 0.f};
   FrameParams P;

@@ -4,7 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rt_device.h"
@@ -115,38 +117,91 @@ struct Tuning {
   bool tile_morton = false;   // UOB_RT_TILE_ORDER=morton: the mesh kernel's tiles in plain Morton order (tiled_order)
 };
 
-// A device buffer that only ever grows (ensure_bytes, rt_calls.hip)
-struct DevBuffer {
-  char* p = nullptr;
+// ---- owners of device objects: move-only, and no device is stored — whoever frees on a given device sets
+// it first, and a local owner is declared after the function's DeviceGuard.  g_live is what the owners of this process hold
+// right now: allocations, their bytes, events, streams (rt_debug_live_device_objects)
+inline std::atomic<int64_t> g_live[4];
+inline void live_add(int slot, int64_t d) { g_live[slot].fetch_add(d, std::memory_order_relaxed); }
+
+// A device array of T.  reset() is a plain hipFree: it waits for whatever still uses the memory.
+template <class T>
+struct DevMem {
+  T* p = nullptr;
   size_t bytes = 0;
+  DevMem() = default;
+  DevMem(DevMem&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+  DevMem& operator=(DevMem&& o) noexcept {     // frees what it held
+    if (this != &o) { reset(); p = std::exchange(o.p, nullptr); bytes = std::exchange(o.bytes, 0); }
+    return *this;
+  }
+  ~DevMem() { reset(); }
+  hipError_t alloc(size_t count) {             // count elements; none: one byte, so that the pointer is never null
+    reset();
+    const size_t want = count ? count * sizeof(T) : 1;
+    const hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    bytes = want; live_add(0, 1); live_add(1, (int64_t)want);
+    return hipSuccess;
+  }
+  void reset() {
+    if (p) { hipFree(p); live_add(0, -1); live_add(1, -(int64_t)bytes); }
+    p = nullptr; bytes = 0;
+  }
+  operator T*() const { return p; }
 };
+// What every failed alloc answers
+inline int alloc_failed() { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM; }
+// A byte buffer that only ever grows (ensure_bytes, rt_calls.hip)
+using DevBuffer = DevMem<char>;
 int ensure_bytes(DevBuffer* b, size_t bytes);
+
+// An event or a stream, created with the flags of hipEventCreateWithFlags / hipStreamCreateWithFlags (none: hipEventCreate's)
+template <class H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H), int Slot>
+struct Handle {
+  H h = nullptr;
+  Handle() = default;
+  Handle(Handle&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+  Handle& operator=(Handle&& o) noexcept { if (this != &o) { reset(); h = std::exchange(o.h, nullptr); } return *this; }
+  ~Handle() { reset(); }
+  hipError_t create(unsigned flags = 0) {
+    reset();
+    const hipError_t e = Create(&h, flags);
+    if (e != hipSuccess) h = nullptr; else live_add(Slot, 1);
+    return e;
+  }
+  void reset() { if (h) { Destroy(h); live_add(Slot, -1); h = nullptr; } }
+  operator H() const { return h; }
+};
+using Event = Handle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy, 2>;
+using Stream = Handle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy, 3>;
 
 // What a context owns of the buffers that depend on the scene's size or kernel family.  The context's working pointers
 // (rt_ctx::d_verts_m, d_records, d_screen_masks, d_heavy, d_mesh_cost, ...) are these or nullptr: "is there a tiled copy",
 // "are there tile masks" are asked of the working pointers everywhere, so a scene replaced by one of another family
 // (rt_replace_scene) switches them and keeps the memory.  Everything sized by n holds rt_ctx::cap triangles.
 struct SceneStore {
-  float4 *verts_m = nullptr, *normals_m = nullptr, *colors_m = nullptr, *tile_box = nullptr, *records = nullptr;
-  int* orig = nullptr;
-  unsigned long long *screen_masks = nullptr, *world_masks = nullptr;
-  unsigned int* world_occ = nullptr;
-  unsigned int *heavy[2] = {nullptr, nullptr}, *heavy_flags = nullptr, *mesh_cost = nullptr, *mesh_order = nullptr;
+  DevMem<float4> verts_m, normals_m, colors_m, tile_box, records;
+  DevMem<int> orig;
+  DevMem<unsigned long long> screen_masks, world_masks;
+  DevMem<unsigned int> world_occ;
+  DevMem<unsigned int> heavy[2], heavy_flags, mesh_cost, mesh_order;
 };
 
 // One family of calls beside the frame (rt_calls.hip): ray queries, shade calls, radiance calls, AOV passes.
 // Who waits for whose event is DESIGN.md 4.9; wait_scene_readers and wait_aov below are the only places that say it.
 struct SideCall {
-  hipEvent_t ev = nullptr;                 // recorded behind the latest call, created on first use
+  Event ev;                                // recorded behind the latest call, created on first use
   bool pending = false;                    // a call has been enqueued: ev is worth waiting for
-  unsigned long long* d_stats = nullptr;   // the latest call's work counters (+ its kernels' queue heads)
+  DevMem<unsigned long long> d_stats;      // the latest call's work counters (+ its kernels' queue heads)
   int tiles = 0;                           // tiles of the latest call's scene (0: no tiled copy)
   DevBuffer io;                            // the blocking host entry: device copies of the caller's host arrays
 };
 
 }  // namespace uobrt
 
+// What a context holds of the device is held by owners and goes with it; the raw device pointers are aliases of the store
 struct rt_ctx {
+  ~rt_ctx();                       // rt_api.hip: the children, the device, no work of the context still running
   rt_config cfg;
   uobrt::Tuning tune;
   int device = 0;
@@ -155,11 +210,11 @@ struct rt_ctx {
   uobrt::SceneStore own;           // the owner of what a replaced scene may drop and regain
   uobrt::DevBuffer tile_scratch;   // rt_tile_build.hip: keys, indices and the digit table of the device tile build
   int owned_rows = 0;
-  float4 *d_verts = nullptr, *d_normals = nullptr, *d_colors = nullptr;
-  uint32_t* d_argb = nullptr;      // internal framebuffer (stripe) for rt_render
-  float4* d_rgb = nullptr;         // lazily allocated float tap
-  unsigned long long* d_counters = nullptr;
-  unsigned int* d_jobctr = nullptr; // wave kernel's job queue heads
+  uobrt::DevMem<float4> d_verts, d_normals, d_colors;
+  uobrt::DevMem<uint32_t> d_argb;  // internal framebuffer (stripe) for rt_render
+  uobrt::DevMem<float4> d_rgb;     // lazily allocated float tap
+  uobrt::DevMem<unsigned long long> d_counters;
+  uobrt::DevMem<unsigned int> d_jobctr; // wave kernel's job queue heads
   int cus = 256;                    // compute units of the device
   // wave kernel: last frame's expensive jobs go first (rt_device.h FrameParams::heavy_*); two lists, used in turn
   unsigned int *d_heavy[2] = {nullptr, nullptr}, *d_heavy_flags = nullptr;
@@ -169,7 +224,7 @@ struct rt_ctx {
   char* reg_host = nullptr; char* reg_dev = nullptr; size_t reg_bytes = 0;
   bool reg_owner = false;        // this context called hipHostRegister (a child of a multi-device context only holds its device's alias)
   bool timeline_valid = false;   // the last frame left one (start, end, jobs) record per wave in d_timeline
-  uint64_t* d_timeline = nullptr;
+  uobrt::DevMem<uint64_t> d_timeline;
   size_t timeline_waves = 0;
   uint32_t heavy_gen = 0;
   float4* d_records = nullptr;     // staged records in HBM for meshes beyond one LDS stage
@@ -177,7 +232,7 @@ struct rt_ctx {
   // triangles first, then Morton order of the centroids), the original index of each triangle, and the tiles' boxes
   float4 *d_verts_m = nullptr, *d_normals_m = nullptr, *d_colors_m = nullptr, *d_tile_box = nullptr;
   int* d_orig = nullptr;
-  uobrt::DevSphere* d_spheres = nullptr;  // the sphere table in device memory (the wave-mapped kernels stage it into LDS)
+  uobrt::DevMem<uobrt::DevSphere> d_spheres;  // the sphere table in device memory (the wave-mapped kernels stage it into LDS)
   unsigned int *d_mesh_cost = nullptr, *d_mesh_order = nullptr;   // per 16x16-pixel block: last frame's cost, this frame's order
   bool mesh_order_valid = false;
   // mesh kernel: per-frame candidate-tile masks (rt_kernel_mesh.hip) and the scene's bounding box for its world grid
@@ -186,44 +241,44 @@ struct rt_ctx {
   int nwords = 0, scx = 0, scy = 0;
   float box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
   float vbox_lo[3] = {0, 0, 0}, vbox_hi[3] = {0, 0, 0};   // the vertices' part of it (rt_update_spheres adds the new spheres)
-  hipStream_t stream = nullptr;
-  hipStream_t aux_stream = nullptr;             // mesh kernel: the primary-ray masks are built beside the shadow-ray masks
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  uobrt::Stream stream;
+  uobrt::Stream aux_stream;                     // mesh kernel: the primary-ray masks are built beside the shadow-ray masks
+  uobrt::Event ev_fork, ev_join;
+  uobrt::Event ev0, ev1;
   bool timed = false;
   hipStream_t last_stream = nullptr;
   // several devices: one child context per entry of cfg.devices (then this context owns no device memory)
   std::vector<rt_ctx*> kids;
-  hipEvent_t ev_go = nullptr;       // parent: "the caller's stream has reached this frame"
-  hipEvent_t ev_done = nullptr;     // child: "this device's bands have been delivered"
+  uobrt::Event ev_go;               // parent: "the caller's stream has reached this frame"
+  uobrt::Event ev_done;             // child: "this device's bands have been delivered"
   bool peer_ok = true;              // child: its device can copy 2-D into the destination device directly
   // rt_update_scene_device: the latest update, enqueued on the caller's stream; later frames (any stream) wait for it
-  hipEvent_t ev_upd = nullptr;
+  uobrt::Event ev_upd;
   bool upd_pending = false;
-  unsigned int* d_check = nullptr;  // rt_scene_check's result block (rt_scene_update.hip)
+  uobrt::DevMem<unsigned int> d_check;  // rt_scene_check's result block (rt_scene_update.hip)
   // Rigid objects (rt_set_objects / rt_pose_objects*, rt_scene_pose.hip), on the context that poses (lead_ctx): the rest pose
   // and the per-triangle object table exist while nobj > 0; the staging scene (sized by cap) and the host entry's matrices
   // are kept once made
   int nobj = 0;
-  float4 *d_rest_verts = nullptr, *d_rest_normals = nullptr;
-  unsigned short* d_object_of = nullptr;
+  uobrt::DevMem<float4> d_rest_verts, d_rest_normals;
+  uobrt::DevMem<unsigned short> d_object_of;
   uobrt::DevBuffer pose_verts, pose_normals, pose_xforms;
   // A skin (rt_set_skin / rt_pose_skin*) shares the rest pose, the staging scene and the host entry's matrices with the
   // objects, so a context holds one or the other.  The influence table exists while skin_count > 0: per corner of the
   // triangles [skin_first, skin_first + skin_count) four bone indices (8 bytes) and four weights (16 bytes)
   int skin_first = 0, skin_count = 0, skin_nbones = 0;
-  ushort4* d_skin_index = nullptr;
-  float4* d_skin_weights = nullptr;
+  uobrt::DevMem<ushort4> d_skin_index;
+  uobrt::DevMem<float4> d_skin_weights;
   // The scene's readers — ray queries (rt_ray_query.hip), shade calls (rt_shade.hip), radiance calls (rt_radiance.hip): they
   // read only the scene, so frames need not wait for them; later readers (they share the counters and staging of their
   // family) and scene updates do
   uobrt::SideCall query, shade, rad;
-  float4* d_qrecords = nullptr;     // queries, no tiled copy, beyond one LDS stage: their own records (d_records is the frames')
+  uobrt::DevMem<float4> d_qrecords; // queries, no tiled copy, beyond one LDS stage: their own records (d_records is the frames')
   uobrt::DevBuffer rrec;                  // radiance calls: the records their first stage leaves for their second (both entries)
   // AOV passes (rt_aov.hip): frame-like — they use the frames' records and screen masks, so frames, updates and later
   // passes wait for the latest one; they touch none of the scheduling state above
   uobrt::SideCall aov;
-  hipStream_t aov_stream = nullptr;
+  hipStream_t aov_stream = nullptr;   // (the caller's: not owned)
 };
 
 namespace uobrt {

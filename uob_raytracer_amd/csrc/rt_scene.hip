@@ -144,16 +144,9 @@ static SceneNeeds scene_needs(const rt_ctx* c, int n) {
 // allocation of every device has succeeded
 struct SceneGrowth {
   int cap = 0;                                               // 0: the scene fits, nothing to replace
-  float4 *verts = nullptr, *normals = nullptr, *colors = nullptr;
+  DevMem<float4> verts, normals, colors;
   SceneStore t;
 };
-
-static void free_growth(SceneGrowth* g) {
-  hipFree(g->verts); hipFree(g->normals); hipFree(g->colors); hipFree(g->t.records);
-  hipFree(g->t.verts_m); hipFree(g->t.normals_m); hipFree(g->t.colors_m); hipFree(g->t.orig); hipFree(g->t.tile_box);
-  hipFree(g->t.screen_masks); hipFree(g->t.world_masks);
-  *g = SceneGrowth();
-}
 
 // Everything a scene of n triangles needs that the context does not hold yet.  Nothing the context renders from is touched:
 // what outgrows the capacity goes into *g; what the context meets for the first time (the buffers of a kernel family it has
@@ -164,72 +157,68 @@ static int scene_reserve(rt_ctx* c, int n, bool device_tiles, SceneGrowth* g) {
   const SceneNeeds q = scene_needs(c, n);
   const rt_config& cfg = c->cfg;
   SceneStore& o = c->own;
+  SceneGrowth fresh;                           // reaches *g when everything has succeeded; a failure frees it on this device
   bool ok = true;
-  auto get = [&](auto** p, size_t bytes) { if (ok && hipMalloc(p, bytes ? bytes : 1) != hipSuccess) ok = false; };
-  auto tiled_set = [&](SceneStore* t, int cap) {
-    const size_t nb = (size_t)cap * sizeof(float4);
-    get(&t->verts_m, 3 * nb); get(&t->normals_m, nb); get(&t->colors_m, nb); get(&t->orig, (size_t)cap * sizeof(int));
-    get(&t->tile_box, (size_t)mesh_tiles(cap) * 3 * sizeof(float4));
+  auto get = [&](auto& m, size_t count) { if (ok && m.alloc(count) != hipSuccess) ok = false; };
+  auto tiled_set = [&](SceneStore* t, size_t cap) {
+    get(t->verts_m, 3 * cap); get(t->normals_m, cap); get(t->colors_m, cap); get(t->orig, cap);
+    get(t->tile_box, (size_t)mesh_tiles((int)cap) * 3);
   };
-  auto mask_set = [&](SceneStore* t, int cap) {
-    const size_t nwords = (size_t)((mesh_tiles(cap) + 63) / 64), g3 = (size_t)kWorldGrid * kWorldGrid * kWorldGrid;
-    get(&t->screen_masks, (size_t)mesh_screen_cells(cfg.width) * mesh_screen_cells(cfg.height) * nwords * 8);
-    get(&t->world_masks, g3 * nwords * 8);
+  auto mask_set = [&](SceneStore* t, size_t cap) {
+    const size_t nwords = (size_t)((mesh_tiles((int)cap) + 63) / 64), g3 = (size_t)kWorldGrid * kWorldGrid * kWorldGrid;
+    get(t->screen_masks, (size_t)mesh_screen_cells(cfg.width) * mesh_screen_cells(cfg.height) * nwords);
+    get(t->world_masks, g3 * nwords);
   };
   const bool grow = n > c->cap || !c->d_verts;
-  const int cap = grow ? (n > 0 ? n : 1) : c->cap;
+  const size_t cap = grow ? (n > 0 ? n : 1) : c->cap;
   if (grow) {    // (what the context already keeps for another family grows too: a later replace within capacity allocates nothing)
-    const size_t nb = (size_t)cap * sizeof(float4);
-    g->cap = cap;
-    get(&g->verts, 3 * nb); get(&g->normals, nb); get(&g->colors, nb);
-    if (q.records || o.records) get(&g->t.records, (size_t)cap * kRecordsPerTriangle * sizeof(float4));
-    if (q.tiled || o.verts_m) tiled_set(&g->t, cap);
-    if (q.masks || o.screen_masks) mask_set(&g->t, cap);
+    fresh.cap = (int)cap;
+    get(fresh.verts, 3 * cap); get(fresh.normals, cap); get(fresh.colors, cap);
+    if (q.records || o.records) get(fresh.t.records, cap * kRecordsPerTriangle);
+    if (q.tiled || o.verts_m) tiled_set(&fresh.t, cap);
+    if (q.masks || o.screen_masks) mask_set(&fresh.t, cap);
   } else {
-    if (q.records && !o.records) get(&o.records, (size_t)cap * kRecordsPerTriangle * sizeof(float4));
+    if (q.records && !o.records) get(o.records, cap * kRecordsPerTriangle);
     if (q.tiled && !o.verts_m) tiled_set(&o, cap);
     if (q.masks && !o.screen_masks) mask_set(&o, cap);
   }
-  if (q.masks && !o.world_occ) get(&o.world_occ, (size_t)mesh_occ_words(kWorldGrid) * sizeof(unsigned int));
+  if (q.masks && !o.world_occ) get(o.world_occ, (size_t)mesh_occ_words(kWorldGrid));
   if (q.heavy && !o.heavy_flags) {
-    get(&o.heavy[0], (size_t)c->heavy_cap * 4); get(&o.heavy[1], (size_t)c->heavy_cap * 4); get(&o.heavy_flags, 2 * c->heavy_jobs_max * 4);
+    get(o.heavy[0], (size_t)c->heavy_cap); get(o.heavy[1], (size_t)c->heavy_cap); get(o.heavy_flags, 2 * c->heavy_jobs_max);
   }
   if (q.mesh_sched && !o.mesh_cost) {
     const size_t jobs = (size_t)((cfg.width + 15) / 16) * (size_t)((c->owned_rows + 15) / 16);
     // order list: up to four entries per block, + its length in the word behind it
-    get(&o.mesh_cost, (jobs ? jobs : 1) * 4); get(&o.mesh_order, (4 * (jobs ? jobs : 1) + 1) * 4);
+    get(o.mesh_cost, jobs ? jobs : 1); get(o.mesh_order, 4 * (jobs ? jobs : 1) + 1);
   }
-  if (!ok) { set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); free_growth(g); return RT_E_NOMEM; }
+  if (!ok) return alloc_failed();
   if (device_tiles && q.tiled) {
-    const int rc = ensure_bytes(&c->tile_scratch, tile_build_scratch_bytes(cap));
-    if (rc != RT_OK) { free_growth(g); return rc; }
+    const int rc = ensure_bytes(&c->tile_scratch, tile_build_scratch_bytes((int)cap));
+    if (rc != RT_OK) return rc;
   }
   if (q.masks && !c->aux_stream &&
-      (hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess ||
-       hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-       hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess)) {
-    set_error("stream/event creation failed"); free_growth(g); return RT_E_DEVICE;
+      (c->aux_stream.create(hipStreamNonBlocking) != hipSuccess || c->ev_fork.create(hipEventDisableTiming) != hipSuccess ||
+       c->ev_join.create(hipEventDisableTiming) != hipSuccess)) {
+    set_error("stream/event creation failed"); return RT_E_DEVICE;
   }
+  *g = std::move(fresh);
   return RT_OK;
 }
 
-// The grown buffers take the place of the old ones.  hipFree waits for whatever still uses what it frees.  From here to
-// scene_select the context's working pointers are stale: the caller installs the new scene next, and nothing in between fails
-// for a reason the caller could have (validation and allocation are behind it).
+// The grown buffers take the place of the old ones: every move assignment frees what the context held, and hipFree waits for
+// whatever still uses what it frees.  From here to scene_select the context's working pointers are stale: the caller installs
+// the new scene next, and nothing in between fails for a reason the caller could have (validation and allocation are behind it).
 static void scene_commit(rt_ctx* c, SceneGrowth* g) {
   if (!g->cap) return;
   hipSetDevice(c->device);
-  SceneStore& o = c->own;
-  hipFree(c->d_verts); hipFree(c->d_normals); hipFree(c->d_colors);
-  hipFree(o.records); hipFree(o.verts_m); hipFree(o.normals_m); hipFree(o.colors_m); hipFree(o.orig); hipFree(o.tile_box);
-  hipFree(o.screen_masks); hipFree(o.world_masks);
-  hipFree(c->d_qrecords); c->d_qrecords = nullptr;           // (the queries make theirs on demand, for the capacity)
-  c->d_verts = g->verts; c->d_normals = g->normals; c->d_colors = g->colors;
-  o.records = g->t.records;
-  o.verts_m = g->t.verts_m; o.normals_m = g->t.normals_m; o.colors_m = g->t.colors_m; o.orig = g->t.orig; o.tile_box = g->t.tile_box;
-  o.screen_masks = g->t.screen_masks; o.world_masks = g->t.world_masks;
+  SceneStore &o = c->own, &t = g->t;
+  c->d_verts = std::move(g->verts); c->d_normals = std::move(g->normals); c->d_colors = std::move(g->colors);
+  o.records = std::move(t.records);
+  o.verts_m = std::move(t.verts_m); o.normals_m = std::move(t.normals_m); o.colors_m = std::move(t.colors_m);
+  o.orig = std::move(t.orig); o.tile_box = std::move(t.tile_box);
+  o.screen_masks = std::move(t.screen_masks); o.world_masks = std::move(t.world_masks);
+  c->d_qrecords.reset();                                     // (the queries make theirs on demand, for the capacity)
   c->cap = g->cap;
-  *g = SceneGrowth();
 }
 
 // The single-device contexts behind a handle
@@ -243,7 +232,7 @@ static int scene_reserve_all(rt_ctx* c, int n, bool device_tiles_wanted) {
     const int rc = scene_reserve(ks[i], n, device_tiles_wanted, &grown[i]);
     if (rc != RT_OK) {
       KeepError keep;
-      for (size_t j = 0; j < i; ++j) { hipSetDevice(ks[j]->device); free_growth(&grown[j]); }
+      for (size_t j = 0; j < i; ++j) { hipSetDevice(ks[j]->device); grown[j] = SceneGrowth(); }   // each freed on its device
       return rc;
     }
   }
@@ -321,7 +310,7 @@ static Tiling choose_tiling(bool on_device, bool replace, uint32_t flags) {
 static int scene_install_one(rt_ctx* c, const SceneEdit& e, Tiling tiling, int src_dev, hipStream_t s) {
   int rc = update_begin(c, s);
   if (rc != RT_OK) return rc;
-  if (e.on_device && !c->ev_upd) HIP_TRY(hipEventCreateWithFlags(&c->ev_upd, hipEventDisableTiming));
+  if (e.on_device && !c->ev_upd) HIP_TRY(c->ev_upd.create(hipEventDisableTiming));
   if (e.replace) { rc = scene_switch(c, e.n, e.first, s); if (rc != RT_OK) return rc; }
   auto copy = [&](float4* dst, const void* src, size_t bytes) {
     if (!src || !bytes) return hipSuccess;
@@ -440,7 +429,7 @@ static float key_to_float(unsigned int k) {   // inverse of rt_scene_update.hip 
 // result has been read back (this synchronises s); the context's buffers are untouched.
 static int device_check(rt_ctx* c, const void* dv, const void* dc, int n, hipStream_t s, SceneSummary* sum) {
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->d_check) HIP_TRY(hipMalloc(&c->d_check, 8 * sizeof(unsigned int)));
+  if (!c->d_check) HIP_TRY(c->d_check.alloc(8));
   if (launch_scene_check((const float4*)dv, (const float4*)dc, n, c->d_check, s) != 0) {
     set_error("scene check launch failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_DEVICE;
   }
@@ -457,32 +446,23 @@ static int device_check(rt_ctx* c, const void* dv, const void* dc, int n, hipStr
 // The tables and the rest pose live on the context that poses (lead_ctx); a context holds an object table or a skin, which
 // share the rest pose.  Nothing here runs for a context without either.
 // (hipFree waits for a pose still reading what it frees)
-static void free_tables(rt_ctx* L, bool objects, bool skin) {
-  const bool rest = L->nobj == 0 && L->skin_count == 0 && (L->d_rest_verts || L->d_rest_normals);   // no table holds it any more
-  objects = objects && L->d_object_of;
-  skin = skin && (L->d_skin_index || L->d_skin_weights);
-  if (!objects && !skin && !rest) return;
+static void drop_tables(rt_ctx* c, bool objects, bool skin) {
+  rt_ctx* L = lead_ctx(c);
+  if (objects) L->nobj = 0;
+  if (skin) L->skin_first = L->skin_count = L->skin_nbones = 0;
+  const bool rest = L->nobj == 0 && L->skin_count == 0;     // no table holds the rest pose any more
+  if (!(objects && L->d_object_of) && !(skin && (L->d_skin_index || L->d_skin_weights)) &&
+      !(rest && (L->d_rest_verts || L->d_rest_normals))) return;   // nothing to free: no HIP call
   DeviceGuard guard;
   hipSetDevice(L->device);
-  if (objects) { hipFree(L->d_object_of); L->d_object_of = nullptr; }
-  if (skin) { hipFree(L->d_skin_index); hipFree(L->d_skin_weights); L->d_skin_index = nullptr; L->d_skin_weights = nullptr; }
-  if (rest) { hipFree(L->d_rest_verts); hipFree(L->d_rest_normals); L->d_rest_verts = L->d_rest_normals = nullptr; }
+  if (objects) L->d_object_of.reset();
+  if (skin) { L->d_skin_index.reset(); L->d_skin_weights.reset(); }
+  if (rest) { L->d_rest_verts.reset(); L->d_rest_normals.reset(); }
 }
-
-static void drop_objects(rt_ctx* c) {
-  rt_ctx* L = lead_ctx(c);
-  L->nobj = 0;
-  free_tables(L, true, false);
-}
-
-static void drop_skin(rt_ctx* c) {
-  rt_ctx* L = lead_ctx(c);
-  L->skin_first = L->skin_count = L->skin_nbones = 0;
-  free_tables(L, false, true);
-}
-
+static void drop_objects(rt_ctx* c) { drop_tables(c, true, false); }
+static void drop_skin(rt_ctx* c) { drop_tables(c, false, true); }
 // The scene behind the rest pose changes: whichever table the context holds goes
-static void drop_poses(rt_ctx* c) { drop_objects(c); drop_skin(c); }
+static void drop_poses(rt_ctx* c) { drop_tables(c, true, true); }
 
 // The context's current scene becomes the rest pose (the buffers are made on first use and hold n triangles: whatever changes
 // n drops both tables), on L's stream.  The snapshot waits for whatever still writes the scene, and for a pose still reading
@@ -490,10 +470,9 @@ static void drop_poses(rt_ctx* c) { drop_objects(c); drop_skin(c); }
 static int snapshot_rest(rt_ctx* L, const char* fn) {
   HIP_TRY(hipSetDevice(L->device));
   const size_t nb = (size_t)L->n * sizeof(float4);
-  if ((!L->d_rest_verts && hipMalloc(&L->d_rest_verts, 3 * nb) != hipSuccess) ||
-      (!L->d_rest_normals && hipMalloc(&L->d_rest_normals, nb) != hipSuccess)) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); return RT_E_NOMEM;
-  }
+  if ((!L->d_rest_verts && L->d_rest_verts.alloc(3 * (size_t)L->n) != hipSuccess) ||
+      (!L->d_rest_normals && L->d_rest_normals.alloc((size_t)L->n) != hipSuccess))
+    return alloc_failed();
   const int rc = update_begin(L, L->stream);
   if (rc != RT_OK) return rc;
   if (hipMemcpyAsync(L->d_rest_verts, L->d_verts, 3 * nb, hipMemcpyDeviceToDevice, L->stream) != hipSuccess ||
@@ -613,9 +592,7 @@ int rt_set_objects(rt_ctx* c, const int32_t* first, const int32_t* count, int32_
   }
   DeviceGuard guard;
   int rc = snapshot_rest(L, "rt_set_objects");
-  if (rc == RT_OK && !L->d_object_of && hipMalloc(&L->d_object_of, (size_t)n * sizeof(unsigned short)) != hipSuccess) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError())); rc = RT_E_NOMEM;
-  }
+  if (rc == RT_OK && !L->d_object_of && L->d_object_of.alloc((size_t)n) != hipSuccess) rc = alloc_failed();
   if (rc == RT_OK &&
       (hipMemcpyAsync(L->d_object_of, object_of.data(), (size_t)n * sizeof(unsigned short), hipMemcpyHostToDevice, L->stream) != hipSuccess ||
        hipStreamSynchronize(L->stream) != hipSuccess)) {
@@ -672,14 +649,10 @@ int rt_set_skin(rt_ctx* c, int32_t first, int32_t count, const uint16_t* bone_in
   }
   DeviceGuard guard;
   HIP_TRY(hipSetDevice(L->device));
-  ushort4* index = nullptr;                      // the new table: the old one stays in force until everything has succeeded
-  float4* wts = nullptr;
-  if (hipMalloc(&index, corners * sizeof(ushort4)) != hipSuccess || hipMalloc(&wts, corners * sizeof(float4)) != hipSuccess) {
-    set_error("hipMalloc failed: %s", hipGetErrorString(hipGetLastError()));
-    KeepError keep;
-    hipFree(index); hipFree(wts);                // (nothing of the context has been touched: its table and rest pose stay)
-    return RT_E_NOMEM;
-  }
+  DevMem<ushort4> index;                         // the new table: the old one stays in force until everything has succeeded
+  DevMem<float4> wts;
+  if (index.alloc(corners) != hipSuccess || wts.alloc(corners) != hipSuccess)
+    return alloc_failed();                       // (nothing of the context has been touched: its table and rest pose stay)
   int rc = snapshot_rest(L, "rt_set_skin");
   if (rc == RT_OK &&
       (hipMemcpyAsync(index, bone_index, corners * sizeof(ushort4), hipMemcpyHostToDevice, L->stream) != hipSuccess ||
@@ -687,9 +660,8 @@ int rt_set_skin(rt_ctx* c, int32_t first, int32_t count, const uint16_t* bone_in
        hipStreamSynchronize(L->stream) != hipSuccess)) {
     set_error("rt_set_skin: upload failed: %s", hipGetErrorString(hipGetLastError())); rc = RT_E_DEVICE;
   }
-  if (rc != RT_OK) { KeepError keep; hipFree(index); hipFree(wts); drop_poses(c); return rc; }   // (the snapshot has begun: the rest pose may be half written)
-  hipFree(L->d_skin_index); hipFree(L->d_skin_weights);
-  L->d_skin_index = index; L->d_skin_weights = wts;
+  if (rc != RT_OK) { KeepError keep; drop_poses(c); return rc; }   // (the snapshot has begun: the rest pose may be half written)
+  L->d_skin_index = std::move(index); L->d_skin_weights = std::move(wts);   // (hipFree waits for a pose still reading the old table)
   L->skin_first = first; L->skin_count = count; L->skin_nbones = nbones;
   drop_objects(c);                               // (the rest pose stays: the skin holds it now)
   return RT_OK;

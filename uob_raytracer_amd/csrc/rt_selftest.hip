@@ -73,14 +73,13 @@ __global__ __launch_bounds__(256) void k_selftest_div(unsigned long long* out, u
 extern "C" int rt_selftest_normalize(uint64_t out[8], uint32_t b_stride) {
   using namespace uobrt;
   if (!out || b_stride == 0 || b_stride > (1u << 23)) { set_error("rt_selftest_normalize: NULL argument or stride outside 1 .. 2^23"); return RT_E_INVALID; }
-  unsigned long long* d = nullptr;
-  if (hipMalloc(&d, 8 * 8) != hipSuccess) { set_error("hipMalloc failed (no device?)"); return RT_E_DEVICE; }
+  DevMem<unsigned long long> d;
+  if (d.alloc(8) != hipSuccess) { set_error("hipMalloc failed (no device?)"); return RT_E_DEVICE; }
   hipMemset(d, 0, 8 * 8);
   const unsigned int count = ((1u << 23) + b_stride - 1) / b_stride;
-  hipLaunchKernelGGL(k_selftest_sqrt, dim3(16384), dim3(256), 0, 0, d);
-  hipLaunchKernelGGL(k_selftest_div, dim3((count + 255) / 256), dim3(256), 0, 0, d, b_stride, count);
+  hipLaunchKernelGGL(k_selftest_sqrt, dim3(16384), dim3(256), 0, 0, d.p);
+  hipLaunchKernelGGL(k_selftest_div, dim3((count + 255) / 256), dim3(256), 0, 0, d.p, b_stride, count);
   const hipError_t e = hipMemcpy(out, d, 8 * 8, hipMemcpyDeviceToHost);
-  hipFree(d);
   if (e != hipSuccess) { set_error("rt_selftest_normalize: %s", hipGetErrorString(e)); return RT_E_DEVICE; }
   out[2] = (uint64_t)count << 23;
   return RT_OK;
@@ -89,12 +88,11 @@ extern "C" int rt_selftest_normalize(uint64_t out[8], uint32_t b_stride) {
 extern "C" int rt_selftest_rcp(uint64_t out[64]) {
   using namespace uobrt;
   if (!out) { set_error("NULL argument"); return RT_E_INVALID; }
-  unsigned long long* d = nullptr;
-  if (hipMalloc(&d, 64 * 8) != hipSuccess) { set_error("hipMalloc failed (no device?)"); return RT_E_DEVICE; }
+  DevMem<unsigned long long> d;
+  if (d.alloc(64) != hipSuccess) { set_error("hipMalloc failed (no device?)"); return RT_E_DEVICE; }
   hipMemset(d, 0, 64 * 8);
-  hipLaunchKernelGGL(k_selftest_rcp, dim3(16384), dim3(256), 0, 0, d);
+  hipLaunchKernelGGL(k_selftest_rcp, dim3(16384), dim3(256), 0, 0, d.p);
   const hipError_t e = hipMemcpy(out, d, 64 * 8, hipMemcpyDeviceToHost);
-  hipFree(d);
   if (e != hipSuccess) { set_error("rt_selftest_rcp: %s", hipGetErrorString(e)); return RT_E_DEVICE; }
   return RT_OK;
 }

@@ -36,7 +36,11 @@ EXPORTS = (
     "rt_scene_transform", "rt_set_objects", "rt_pose_objects", "rt_pose_objects_device", "rt_debug_object_count",
     "rt_debug_scene_data",
     "rt_scene_skin", "rt_set_skin", "rt_pose_skin", "rt_pose_skin_device", "rt_debug_skin_info",
+    "rt_debug_live_device_objects",
 )
+
+# rt_debug_live_device_objects slots
+LIVE_OBJECT_KEYS = ("allocations", "bytes", "events", "streams")
 
 # rt_debug_trace_stats slots (include/uob_rt.h)
 TRACE_STATS_KEYS = ("rays", "waves", "tiles", "bundle_tiles", "tested_tiles", "triangle_tests", "unculled_rays", "reserved")
@@ -94,6 +98,7 @@ def lib():
         L.rt_pose_skin.argtypes = [vp, fp, C.c_uint32]
         L.rt_pose_skin_device.argtypes = [vp, vp, C.c_uint32, vp]
         L.rt_debug_skin_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.rt_debug_live_device_objects.argtypes = [C.POINTER(C.c_int64)]
         L.rt_render.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(C.c_uint32), fp]
         L.rt_render_device.argtypes = [vp, fp, fp, fp, C.c_float, vp, vp, vp]
         L.rt_count_work.argtypes = [vp, fp, fp, fp, C.c_float, C.POINTER(abi.RtWork)]
@@ -172,6 +177,13 @@ def band_copy_plan(num_devices, k, device_band_rows, width, height, elem_bytes, 
     _check(lib().rt_debug_band_copy_plan(num_devices, k, device_band_rows, width, height, elem_bytes, int(dev_to_dev),
                                          int(peer_ok), int(same_device), buf, n))
     return [{f: int(getattr(buf[i], f)) for f, _ in abi.RtBandCopy._fields_ if f != "reserved"} for i in range(n)]
+
+
+def live_device_objects():
+    """Device objects the library holds in this process right now (rt_debug_live_device_objects): dict of LIVE_OBJECT_KEYS."""
+    out = (C.c_int64 * 4)()
+    _check(lib().rt_debug_live_device_objects(out))
+    return {key: int(out[i]) for i, key in enumerate(LIVE_OBJECT_KEYS)}
 
 
 def selftest_rcp():
