@@ -445,6 +445,72 @@ int rt_render_aov_device(rt_ctx* ctx, const float rot[12], const float cam[3], f
  * out[6..7] 0.                                                                                                          */
 int rt_debug_aov_stats(rt_ctx* ctx, uint64_t out[8]);
 
+/* ---- edge-stopping a-trous filter of per-pixel planes (rt_filter.hip) ----------------------------------
+ * A geometry-guided reconstruction filter for a noisy per-pixel estimate (e.g. the visibility of a few shadow samples), run
+ * over planes the library already produces.  It reads no scene data.  With binary edge stops, dyadic tap weights and a fixed
+ * summation order it is a pure FP32 function of its inputs; every implementation (the device kernels, rt_filter_plane_host)
+ * gives the same bits.
+ * Planes of `height` rows x `width` pixels, row-major:
+ *   value      float32 [h][w]      the plane to filter;
+ *   position4  float32 [h][w][4]   the guides, in the layouts of rt_render_aov's position4 / normal4 planes.  A pixel is
+ *   normal4    float32 [h][w][4]   VALID iff position4.w > 0 (a miss of the AOV pass has w = 0; a NaN is invalid).
+ * V_0 = value.  For pass i = 0 .. passes-1 the tap spacing is s = 2^i, and for every pixel p = (x, y):
+ *   - p not valid: V_{i+1}[p] = V_i[p] (its bits).
+ *   - otherwise the 25 taps (dx, dy) in {-2..2}^2 are visited with dy outer and dx inner, both ascending; the tap pixel is
+ *     q = (x + dx*s, y + dy*s) and the tap weight w = h[|dx|] * h[|dy|] with h = (3/8, 1/4, 1/16) (every product exact).
+ *     The centre tap is always accepted.  Any other tap is accepted iff all of these hold, with P / N the xyz of position4 /
+ *     normal4:
+ *       1. q lies inside the plane and is valid;
+ *       2. (Np.x*Nq.x + Np.y*Nq.y) + Np.z*Nq.z >= normal_min_dot;
+ *       3. with d = Pq - Pp component-wise, fabsf((Np.x*d.x + Np.y*d.y) + Np.z*d.z) <= plane_eps;
+ *       4. fabsf(V_i[q] - V_i[p]) <= value_max_diff * 2^-i (one product by the exact power of two; +INFINITY stays).
+ *     All arithmetic is FP32 without contraction.  A comparison with a NaN operand is false, so a NaN tap is always rejected,
+ *     also at value_max_diff = +INFINITY.
+ *     Over the accepted taps in visiting order: num = num + w * V_i[q] (one multiply, one add) and den = den + w, both from
+ *     +0 (den is exact in any order: every partial sum is a multiple of 1/256 not above 1).
+ *     V_{i+1}[p] = V_i[p] (its bits) if only the centre was accepted (den == 9/64); otherwise num / den, correctly rounded,
+ *     and when that quotient is a NaN (infinities of both signs among the accepted taps) the quiet NaN 0x7FC00000.
+ * The output is V_passes.  The guides are those of the centre pixel and do not change between passes.
+ * What follows exactly: a region of valid pixels whose values are all 1.0f (or all 0.0f) keeps them, since num == den
+ * (num == 0); normal_min_dot = 2 with unit normals rejects every tap and returns the input bit for bit.  Equal values other
+ * than those two need not survive bit for bit.                                                                            */
+typedef struct rt_filter_params {
+  int32_t width, height;     /* >= 1; width * height <= 2^31                          */
+  int32_t passes;            /* 1 .. 8                                               */
+  float   normal_min_dot;    /* not NaN                                              */
+  float   plane_eps;         /* >= 0, not NaN                                        */
+  float   value_max_diff;    /* >= 0 or +INFINITY, not NaN                           */
+} rt_filter_params;
+/* 5 passes, normal_min_dot 0.9, plane_eps 0.01, value_max_diff +INFINITY: defaults for a scene of the Cornell box's size
+ * (about 2 units across).  They are stated, not tuned on images.                                                          */
+void rt_filter_params_default(rt_filter_params* params, int32_t width, int32_t height);
+/* out may be the same pointer as value (in place); any other overlap of the planes is the caller's error.  A NULL ctx, params
+ * or plane, and any parameter outside the ranges above, are RT_E_INVALID with a message that names the field, before the
+ * context is looked at and before any device work.  Ordering: a filter call is no reader of the scene — it does not wait
+ * for updates, frames or the calls beside them, and they do not wait for it; it waits only for the context's previous
+ * filter call (they share the scratch), and rt_destroy waits for it.  Ordering with whatever produces its input planes is
+ * the caller's stream.  A multi-device context runs it on devices[0].
+ * rt_filter_plane: host arrays, blocking (staged through device memory the context keeps and grows on demand).
+ * rt_filter_plane_device: planes in device memory on the context's device, the guides 16-byte aligned, enqueued on hip_stream
+ * (NULL = default stream) after the caller's earlier work; returns without synchronising, and no stage waits for the host.
+ * The scratch (40 bytes per pixel: the packed guides and two planes the passes alternate between) belongs to the context and
+ * only grows; only a call larger than any before it allocates, and a context that never filters allocates nothing for it.
+ * Such a growing call (the first one included) is the exception to "does not wait": it frees the smaller scratch and
+ * allocates the larger one before it enqueues anything, and freeing device memory synchronises the whole device, not only
+ * the previous filter call.  A caller that must not stall filters its largest plane once at start-up.
+ * UOB_RT_FILTER_FORM=direct in the environment of rt_init makes every pass take its taps from the caches (measurements).   */
+int rt_filter_plane(rt_ctx* ctx, const rt_filter_params* params, const float* value, const float* position4,
+                    const float* normal4, float* out);
+int rt_filter_plane_device(rt_ctx* ctx, const rt_filter_params* params, const void* d_value, const void* d_position4,
+                           const void* d_normal4, void* d_out, void* hip_stream);
+/* Diagnostic: work counters of the context's most recent filter call (synchronises it; zeros before the first).  out[0] pixels,
+ * out[1] passes, out[2] accepted taps summed over valid centres and passes (the centre included), out[3] valid pixels, out[4]
+ * (valid pixel, pass) pairs that kept their value because only the centre was accepted, out[5..7] 0.                       */
+int rt_debug_filter_stats(rt_ctx* ctx, uint64_t out[8]);
+/* The same filter on the host (CPU only, no context): the statement the device kernels are pinned against.  Same checks. */
+int rt_filter_plane_host(const rt_filter_params* params, const float* value, const float* position4, const float* normal4,
+                         float* out);
+
 /* Diagnostic, mesh kernel (n > 64): the cost of every 16x16-pixel block of the most recent frame in s_memtime ticks
  * (shader cycles) — the scheduling state "last frame's expensive blocks first" is built from it.  Row-major over
  * ceil(owned_rows/16) x ceil(width/16) blocks; writes min(count, cap) values, returns the block count, or
@@ -531,7 +597,7 @@ int rt_selftest_rcp(uint64_t out[64]);
  * out[0] mismatches of (a), out[1] mismatches of (b), out[2] pairs checked by (b), out[3] / out[4] a mismatching pattern each. */
 int rt_selftest_normalize(uint64_t out[8], uint32_t b_stride);
 
-/* Releases everything the context holds: it waits for the context's streams and side calls, then frees its device memory,
+/* Releases everything the context holds: it waits for the context's streams, side calls and filter calls, then frees its device memory,
  * events and streams (and those of every device of a multi-device context), and unregisters a registered output.   */
 void rt_destroy(rt_ctx* ctx);
 

@@ -63,6 +63,15 @@ AOV_PLANES = {"prim": ("prim", 1, True), "depth": ("depth", 1, False), "position
               "normal": ("normal4", 4, False), "albedo": ("albedo4", 4, False), "direction": ("direction4", 4, False)}
 
 
+class RtFilterParams(C.Structure):
+    """rt_filter_params: the plane size, the pass count and the three edge stops of rt_filter_plane."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("passes", C.c_int32), ("normal_min_dot", C.c_float),
+                ("plane_eps", C.c_float), ("value_max_diff", C.c_float)]
+
+
+RT_FILTER_MAX_PASSES = 8
+
+
 class RtTriangle(C.Structure):
     _fields_ = [(k, C.c_float * 4) for k in ("v0", "v1", "v2", "normal", "color")]
 

@@ -92,6 +92,7 @@ static Tuning read_tuning(const rt_config& cfg) {
   t.timeline = getenv("UOB_RT_TIMELINE") != nullptr;
   if (const char* e = getenv("UOB_RT_MASK_DEBUG")) t.mask_debug = atoi(e);
   if (const char* e = getenv("UOB_RT_TILE_ORDER")) t.tile_morton = !strcmp(e, "morton");
+  if (const char* e = getenv("UOB_RT_FILTER_FORM")) t.filter_form = !strcmp(e, "direct") ? kFilterFormDirect : kFilterFormBuiltIn;
   return t;
 }
 
@@ -873,7 +874,7 @@ rt_ctx::~rt_ctx() {
   hipSetDevice(device);
   if (stream) hipStreamSynchronize(stream);
   if (aux_stream) hipStreamSynchronize(aux_stream);
-  for (SideCall* k : {&query, &shade, &rad, &aov})     // no call of any family may still be running
+  for (SideCall* k : {&query, &shade, &rad, &aov, &filter})     // no call of any family may still be running
     if (k->ev) hipEventSynchronize(k->ev);
   if (reg_host && reg_owner) hipHostUnregister(reg_host);
 }

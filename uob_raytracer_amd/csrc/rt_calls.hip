@@ -1,6 +1,6 @@
 // rt_calls.hip — the calls beside the frame, over the C ABI (include/uob_rt.h): ray queries (rt_trace_rays, rt_ray_query.hip),
-// shade calls (rt_shade_points, rt_shade.hip), radiance calls (rt_radiance_rays, rt_radiance.hip) and AOV passes
-// (rt_render_aov, rt_aov.hip).  Each family has an enqueue on the caller's stream (the *_device entry), a blocking entry for
+// shade calls (rt_shade_points, rt_shade.hip), radiance calls (rt_radiance_rays, rt_radiance.hip), AOV passes
+// (rt_render_aov, rt_aov.hip) and filter calls (rt_filter_plane, rt_filter.hip).  Each family has an enqueue on the caller's stream (the *_device entry), a blocking entry for
 // host arrays that stages them through the family's device buffer, and a stats export.  What the families share is written
 // once: the steps around a call (call_prepare / reader_begin / call_end), the blocking entry (run_blocking) and the stats
 // reader (read_stats).  Which operation waits for which is DESIGN.md 4.9 (rt_host.h wait_scene_readers, wait_aov, wait_scene).
@@ -225,7 +225,71 @@ static int enqueue_aov(rt_ctx* c, const float rot[12], const float cam[3], float
   return call_end(c, &c->aov, s);
 }
 
+// ---- filter calls (rt_filter_plane / rt_filter_plane_device, rt_filter.hip) ---------------------------------------------
+// One filter call of a single-device context on stream s (device planes of c->device); arguments checked.  Not a reader of
+// the scene: it waits for the filter call before it, whose scratch it takes over, and for nothing else.
+static int enqueue_filter(rt_ctx* c, const rt_filter_params& p, const float* d_value, const float4* d_pos, const float4* d_nrm,
+                          float* d_out, hipStream_t s) {
+  const size_t count = (size_t)p.width * p.height;
+  const int words = filter_stats_words();
+  int rc = call_prepare(c, &c->filter, words);
+  if (rc != RT_OK) return rc;
+  rc = ensure_bytes(&c->filter_guides, count * 32);   // (a larger call than any before: hipFree waits for the call still using the old one)
+  if (rc == RT_OK) rc = ensure_bytes(&c->filter_planes, count * 8);
+  if (rc != RT_OK) return rc;
+  if (c->filter.pending) HIP_TRY(hipStreamWaitEvent(s, c->filter.ev, 0));
+  HIP_TRY(hipMemsetAsync(c->filter.d_stats, 0, (size_t)words * sizeof(unsigned long long), s));
+  float4* rec = (float4*)c->filter_guides.p;
+  float* plane[2] = {(float*)c->filter_planes.p, (float*)c->filter_planes.p + count};
+  launch_filter_pack(d_pos, d_nrm, (long)count, p.passes, rec, c->filter.d_stats, s);
+  // no pass reads what it writes: the passes alternate between the two planes and the last one writes d_out — through a
+  // plane and a copy when it is also the first and the call is in place
+  const bool bounce = p.passes == 1 && d_out == d_value;
+  const float* src = d_value;
+  for (int i = 0; i < p.passes; ++i) {
+    float* dst = (i == p.passes - 1 && !bounce) ? d_out : plane[i & 1];
+    launch_filter_pass(p, i, c->tune.filter_form, rec, src, dst, c->filter.d_stats, s);
+    src = dst;
+  }
+  launch_filter_counters(c->filter.d_stats, s);
+  if (bounce) HIP_TRY(hipMemcpyAsync(d_out, src, count * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return call_end(c, &c->filter, s);
+}
+
 extern "C" {
+
+int rt_filter_plane_device(rt_ctx* c, const rt_filter_params* p, const void* d_value, const void* d_position4, const void* d_normal4,
+                           void* d_out, void* hip_stream) {
+  if (!c) { set_error("rt_filter_plane_device: ctx is NULL"); return RT_E_INVALID; }
+  const int rc = filter_check(p, d_value, d_position4, d_normal4, d_out, "rt_filter_plane_device");
+  if (rc != RT_OK) return rc;
+  if ((((uintptr_t)d_position4 | (uintptr_t)d_normal4) & 15) != 0) {
+    set_error("rt_filter_plane_device: d_position4 / d_normal4 is not 16-byte aligned"); return RT_E_INVALID;
+  }
+  DeviceGuard guard;
+  return enqueue_filter(lead_ctx(c), *p, (const float*)d_value, (const float4*)d_position4, (const float4*)d_normal4, (float*)d_out,
+                        (hipStream_t)hip_stream);
+}
+
+int rt_filter_plane(rt_ctx* c, const rt_filter_params* p, const float* value, const float* position4, const float* normal4, float* out) {
+  if (!c) { set_error("rt_filter_plane: ctx is NULL"); return RT_E_INVALID; }
+  const int rc = filter_check(p, value, position4, normal4, out, "rt_filter_plane");
+  if (rc != RT_OK) return rc;
+  c = lead_ctx(c);
+  DeviceGuard guard;
+  const size_t n = (size_t)p->width * p->height;
+  // (the guides first: the kernels load them as float4, and the start of the staging buffer is aligned for that)
+  IoSlot io[4] = {{(void*)position4, n * 16, true}, {(void*)normal4, n * 16, true}, {(void*)value, n * 4, true}, {out, n * 4, false}};
+  return run_blocking(c, &c->filter, io, 4, [&] {
+    return enqueue_filter(c, *p, (const float*)io[2].dev, (const float4*)io[0].dev, (const float4*)io[1].dev, (float*)io[3].dev, c->stream);
+  });
+}
+
+int rt_debug_filter_stats(rt_ctx* c, uint64_t out[8]) {
+  const int rc = read_stats(c, &rt_ctx::filter, -1, out);
+  if (rc == RT_OK) out[5] = out[6] = out[7] = 0;
+  return rc;
+}
 
 int rt_trace_rays_device(rt_ctx* c, int32_t what, const void* d_rays6, const void* d_radius_sq, int64_t nray, void* d_out_tri,
                          void* d_out10, void* hip_stream) {

@@ -83,6 +83,20 @@ void launch_radiance(const FrameParams& P, bool tiled, const float* d_rays6, con
 // rt_aov.hip
 int aov_stats_words();
 void launch_aov(const FrameParams& P, bool tiled, const AovPlanes& A, int sample, unsigned long long* stats, int cus, hipStream_t stream);
+// rt_filter.hip: the a-trous filter of per-pixel planes (include/uob_rt.h rt_filter_plane).  A tile is kFilterTX
+// contiguous pixels of kFilterTY rows; passes of spacing <= kFilterMaxTiledSpacing stage their taps in LDS (rows s apart), the
+// others take them from the caches.  form: Tuning::filter_form
+constexpr int kFilterTX = 64, kFilterTY = 4, kFilterMaxTiledSpacing = 32;
+constexpr int kFilterFormBuiltIn = 0, kFilterFormDirect = 1;
+int filter_stats_words();
+void launch_filter_pack(const float4* d_pos, const float4* d_nrm, long count, int passes, float4* d_rec, unsigned long long* stats,
+                        hipStream_t stream);
+void launch_filter_pass(const rt_filter_params& p, int pass, int form, const float4* d_rec, const float* d_src, float* d_dst,
+                        unsigned long long* stats, hipStream_t stream);
+void launch_filter_counters(unsigned long long* stats, hipStream_t stream);
+// filter_host.cpp: the ranges of rt_filter_params and the plane pointers, before anything else is looked at
+int filter_check(const rt_filter_params* p, const void* value, const void* position4, const void* normal4, const void* out,
+                 const char* fn);
 // rt_tile_sort.hip: the vertices' box, and the mesh kernel's tiled order and per-tile data (host arithmetic)
 void vertex_box(const float* vertices4, int n, float lo[3], float hi[3]);
 std::vector<int> tiled_order(const float* v4, int n, bool morton);
@@ -115,6 +129,7 @@ struct Tuning {
   bool timeline = false;      // UOB_RT_TIMELINE: the wave kernel records when its waves start and end (rt_debug_wave_timeline)
   int mask_debug = 0;         // UOB_RT_MASK_DEBUG: mesh kernel, switch single tile-mask stages off (fault isolation)
   bool tile_morton = false;   // UOB_RT_TILE_ORDER=morton: the mesh kernel's tiles in plain Morton order (tiled_order)
+  int filter_form = 0;        // UOB_RT_FILTER_FORM=direct: every filter pass takes its taps from the caches (tools/filter_time.py)
 };
 
 // ---- owners of device objects: move-only, and no device is stored — whoever frees on a given device sets
@@ -279,6 +294,11 @@ struct rt_ctx {
   // passes wait for the latest one; they touch none of the scheduling state above
   uobrt::SideCall aov;
   hipStream_t aov_stream = nullptr;   // (the caller's: not owned)
+  // Filter calls (rt_filter.hip): they read no scene data and none of the buffers above, so they wait only for the filter
+  // call before them (they share the scratch) and nothing but the next filter call and the destructor waits for them.
+  // filter_guides: the packed guide records, 32 bytes per pixel; filter_planes: the two planes the passes alternate between
+  uobrt::SideCall filter;
+  uobrt::DevBuffer filter_guides, filter_planes;
 };
 
 namespace uobrt {

@@ -37,6 +37,7 @@ EXPORTS = (
     "rt_debug_scene_data",
     "rt_scene_skin", "rt_set_skin", "rt_pose_skin", "rt_pose_skin_device", "rt_debug_skin_info",
     "rt_debug_live_device_objects",
+    "rt_filter_params_default", "rt_filter_plane", "rt_filter_plane_device", "rt_debug_filter_stats", "rt_filter_plane_host",
 )
 
 # rt_debug_live_device_objects slots
@@ -53,6 +54,9 @@ SHADE_STATS_KEYS = ("points", "sample_rays", "waves", "tiles", "bundle_tiles", "
 # rt_debug_radiance_stats slots
 RADIANCE_STATS_KEYS = ("rays", "bounce_rays", "shaded_points", "sample_rays", "closest_tested_tiles", "closest_triangle_tests",
                        "shadow_triangle_tests", "unculled_rays")
+
+# rt_debug_filter_stats slots
+FILTER_STATS_KEYS = ("pixels", "passes", "accepted_taps", "valid_pixels", "kept", "reserved5", "reserved6", "reserved7")
 
 _lib = None
 
@@ -122,6 +126,12 @@ def lib():
         L.rt_radiance_rays.argtypes = [vp, fp, C.POINTER(C.c_int32), C.c_int64, fp, fp, C.POINTER(C.c_int32)]
         L.rt_radiance_rays_device.argtypes = [vp, vp, vp, C.c_int64, fp, vp, vp, vp]
         L.rt_debug_radiance_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_filter_params_default.argtypes = [C.POINTER(abi.RtFilterParams), C.c_int32, C.c_int32]
+        L.rt_filter_params_default.restype = None
+        L.rt_filter_plane.argtypes = [vp, C.POINTER(abi.RtFilterParams), fp, fp, fp, fp]
+        L.rt_filter_plane_device.argtypes = [vp, C.POINTER(abi.RtFilterParams), vp, vp, vp, vp, vp]
+        L.rt_debug_filter_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_filter_plane_host.argtypes = [C.POINTER(abi.RtFilterParams), fp, fp, fp, fp]
         L.rt_debug_block_costs.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int32]
         L.rt_debug_world_masks.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.rt_debug_wave_timeline.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -202,6 +212,48 @@ def selftest_normalize(b_stride=64):
     _check(lib().rt_selftest_normalize(out, C.c_uint32(b_stride)))
     v = list(out)
     return {"sqrt_mismatches": v[0], "div_mismatches": v[1], "div_pairs": v[2], "sqrt_example": v[3], "div_example": v[4]}
+
+
+def filter_params(width, height, passes=None, normal_min_dot=None, plane_eps=None, value_max_diff=None):
+    """rt_filter_params of a width x height plane: rt_filter_params_default's values (5 passes, 0.9, 0.01, +inf) unless given."""
+    p = abi.RtFilterParams()
+    lib().rt_filter_params_default(C.byref(p), int(width), int(height))
+    for key, v in (("passes", passes), ("normal_min_dot", normal_min_dot), ("plane_eps", plane_eps), ("value_max_diff", value_max_diff)):
+        if v is not None:
+            setattr(p, key, v)
+    return p
+
+
+def _filter_host_planes(value, position4, normal4, out):
+    """The numpy planes of a blocking filter call: value float32 [h, w], the guides [h, w, 4]; out None, `value` itself (in
+    place) or another C-contiguous float32 [h, w] array."""
+    if not isinstance(value, np.ndarray) or value.ndim != 2:
+        raise ValueError("value must be a numpy array of shape [height, width]")
+    h, w = value.shape
+    if out is value and not (value.dtype == np.float32 and value.flags.c_contiguous and value.flags.writeable):
+        raise ValueError("in place, value must be a writeable C-contiguous float32 array")
+    v = np.ascontiguousarray(value, np.float32)
+    pos = np.ascontiguousarray(position4, np.float32)
+    nrm = np.ascontiguousarray(normal4, np.float32)
+    if pos.shape != (h, w, 4) or nrm.shape != (h, w, 4):
+        raise ValueError("position4 and normal4 must have the shape [%d, %d, 4]" % (h, w))
+    if out is None:
+        out = np.empty((h, w), np.float32)
+    elif out is value:
+        out = v
+    elif not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != (h, w) or not out.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous float32 array of shape (%d, %d)" % (h, w))
+    return h, w, v, pos, nrm, out
+
+
+def filter_plane_host(value, position4, normal4, out=None, **params):
+    """The a-trous filter on the host (rt_filter_plane_host; needs no device): value float32 [h, w], position4 / normal4
+    float32 [h, w, 4] -> float32 [h, w].  params: passes, normal_min_dot, plane_eps, value_max_diff (filter_params).
+    out=value filters in place."""
+    h, w, v, pos, nrm, out = _filter_host_planes(value, position4, normal4, out)
+    p = filter_params(w, h, **params)
+    _check(lib().rt_filter_plane_host(C.byref(p), _fp(v), _fp(pos), _fp(nrm), _fp(out)))
+    return out
 
 
 def default_config():
@@ -815,6 +867,78 @@ class RayTracer:
         p6 = torch.cat([planes["position"][..., :3], planes["normal"][..., :3]], -1).reshape(-1, 6).contiguous()
         out = self.shade_points_device(p6, light, seeds=seeds)
         return torch.where(planes["prim"].reshape(-1) != -1, out, torch.zeros_like(out)).reshape(shape)
+
+    def filter_plane(self, value, position4, normal4, out=None, **params):
+        """The a-trous filter of a per-pixel plane on the device (rt_filter_plane), blocking: numpy planes as
+        runtime.filter_plane_host takes them, and the same bits.  out=value filters in place."""
+        h, w, v, pos, nrm, out = _filter_host_planes(value, position4, normal4, out)
+        p = filter_params(w, h, **params)
+        _check(lib().rt_filter_plane(self._h, C.byref(p), _fp(v), _fp(pos), _fp(nrm), _fp(out)))
+        return out
+
+    def filter_plane_device(self, value, position4, normal4, out=None, stream=None, **params):
+        """Enqueue rt_filter_plane_device on torch tensors of the context's device, without synchronising.  value: float32
+        [h, w]; position4, normal4: float32 [h, w, 4] (the AOV planes); out: float32 [h, w], allocated when None, `value`
+        itself for in-place use.  stream: a torch stream or a raw hipStream_t (default: torch's current stream)."""
+        import torch
+        dev = self._torch_device()
+        if not isinstance(value, torch.Tensor) or value.dim() != 2:
+            raise ValueError("value must be a torch tensor of shape [height, width]")
+        h, w = value.shape
+        _need("value", value, torch.float32, (h, w), dev)
+        _need("position4", position4, torch.float32, (h, w, 4), dev)
+        _need("normal4", normal4, torch.float32, (h, w, 4), dev)
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.float32, device=dev)
+        _need("out", out, torch.float32, (h, w), dev)
+        p = filter_params(w, h, **params)
+        raw = self._raw_stream(stream, dev)
+        _check(lib().rt_filter_plane_device(self._h, C.byref(p), C.c_void_p(value.data_ptr()), C.c_void_p(position4.data_ptr()),
+                                            C.c_void_p(normal4.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(raw)))
+        return out
+
+    def filter_stats(self):
+        """Work counters of the context's most recent filter call (rt_debug_filter_stats): dict of FILTER_STATS_KEYS."""
+        return self._stats("rt_debug_filter_stats", FILTER_STATS_KEYS)
+
+    def render_filtered_light(self, rot, cam, light, focal, sample=0, want_parts=False, **params):
+        """The direct light of every pixel's primary hit with its shadow term reconstructed by the a-trous filter, on the
+        device: an AOV pass (position, normal, prim of AA sample `sample`), a shade call with counts seeded like the frame,
+        the visibility V = counts / shadow_samples filtered under the AOV planes as guides (params: filter_params), and
+        term * V_f with term = 16 * max(dot(dir, N), 0) / (4 pi r^2), dir = light - P, formed in torch -> torch float32
+        [rows, W], 0 where the pixel sees nothing.  Filtering V and not the light leaves fully lit and fully shadowed regions
+        exactly as they were: only penumbrae are noisy.  Float-accurate, not bit-pinned to the frame (the frame sums term per
+        sample).  want_parts: also (term, V, V_f).  Runs on torch's current stream; does not synchronise.  Refuses contexts of
+        row bands (their rows are not neighbours) and, like render_direct_light, frames beyond 2^24 pixels."""
+        import math
+        import torch
+        aa = self.cfg.aa_x * self.cfg.aa_y
+        if sample is None or isinstance(sample, bool) or int(sample) != sample or not 0 <= int(sample) < aa:
+            raise ValueError("sample must be one AA sample index in [0, %d)" % aa)
+        if max(self.cfg.band_count, 1) != 1:
+            raise ValueError("render_filtered_light: a context of row bands does not hold neighbouring rows")
+        if self.cfg.width * self.cfg.height > abi.RT_SHADE_SEED_MAX:
+            raise ValueError("render_filtered_light: %d x %d pixels exceed the seed domain of 2^24 ids" % (self.cfg.width, self.cfg.height))
+        dev = self._torch_device()
+        shape = (self.rows, self.width)
+        planes = {"prim": torch.empty(shape, dtype=torch.int32, device=dev),
+                  "position": torch.empty(shape + (4,), dtype=torch.float32, device=dev),
+                  "normal": torch.empty(shape + (4,), dtype=torch.float32, device=dev)}
+        self.render_aov_device(rot, cam, focal, sample=sample, out=planes)
+        pos, nrm = planes["position"], planes["normal"]
+        seeds = torch.arange(shape[0] * shape[1], dtype=torch.int32, device=dev)
+        p6 = torch.cat([pos[..., :3], nrm[..., :3]], -1).reshape(-1, 6).contiguous()
+        _, counts = self.shade_points_device(p6, light, seeds=seeds, want_counts=True)
+        hit = planes["prim"] != -1
+        zero = torch.zeros(shape, dtype=torch.float32, device=dev)
+        vis = torch.where(hit, counts.reshape(shape).to(torch.float32) / float(self.cfg.shadow_samples), zero)
+        d = torch.tensor(np.ascontiguousarray(light, np.float32)[:3], device=dev) - pos[..., :3]
+        r2 = (d * d).sum(-1)
+        term = 16.0 * (d * nrm[..., :3]).sum(-1).clamp_min(0.0) / (4.0 * math.pi * r2)
+        term = torch.where(hit, term, zero)
+        vis_f = self.filter_plane_device(vis, pos, nrm, **params)
+        out = term * torch.where(hit, vis_f, zero)
+        return (out, term, vis, vis_f) if want_parts else out
 
     def shade_stats(self):
         """Work counters of the context's most recent shade call (rt_debug_shade_stats): dict of SHADE_STATS_KEYS."""
