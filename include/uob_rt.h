@@ -597,6 +597,15 @@ int rt_selftest_rcp(uint64_t out[64]);
  * out[0] mismatches of (a), out[1] mismatches of (b), out[2] pairs checked by (b), out[3] / out[4] a mismatching pattern each. */
 int rt_selftest_normalize(uint64_t out[8], uint32_t b_stride);
 
+/* On-device run of the wave and mesh kernels' shade() (rt_wave_common.h: direct_light's running sum of one AA ray, then its
+ * colour), one wave of 64 lanes per entry of ns[]: lane l of wave w takes lit / secondary / unshadowed [64 w + l] (lit,
+ * secondary: 0 or non-zero; a lit lane's unshadowed lies in 0 .. ns[w]), term[64 w + l] and col[4 (64 w + l) .. + 3], and
+ * out[3 (64 w + l) .. + 2] receives its contribution.  ns[w] in 1 .. 4096 is the wave's sample count.  straight_line != 0 runs
+ * the instantiation specialised on the sample count where ns[w] is one of 1, 5, 10, 16, 64 (straight-line sums for 64), and the
+ * run-time form elsewhere; 0 runs the run-time form everywhere.  All pointers are host memory.                            */
+int rt_selftest_shade(int32_t nwaves, const int32_t* ns, const int32_t* lit, const int32_t* secondary, const int32_t* unshadowed,
+                      const float* term, const float* col, int32_t straight_line, float* out);
+
 /* Releases everything the context holds: it waits for the context's streams, side calls and filter calls, then frees its device memory,
  * events and streams (and those of every device of a multi-device context), and unregisters a registered output.   */
 void rt_destroy(rt_ctx* ctx);

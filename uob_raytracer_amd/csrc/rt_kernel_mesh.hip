@@ -970,7 +970,7 @@ __global__ __launch_bounds__(64 * kMeshWaves, kMeshMinBlocks) void rt_draw_mesh(
     if (blocked || task_blocked) unshadowed = 0;
 
     // ---- phase 4: shading and the AA sum, as in rt_kernel_wave.hip ---------------------------------------
-    const f3 contrib = shade(lit, secondary, unshadowed, NS, term, P.inv_S, ray.col);
+    const f3 contrib = shade(lit, secondary, unshadowed, NS, term, P.inv_S, ray.col, litmask != 0ull);
     const f3 acc = aa_sum(contrib, aa, (p < PT ? p : 0) * aa);
     {   // output lane l owns block pixel (l & 7, l >> 3): take its sum from the task and pixel that cover it
       const int qo = zorder_of(lane & 7, lane >> 3);

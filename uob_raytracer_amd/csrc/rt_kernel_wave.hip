@@ -598,6 +598,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
     // ---- phase 3: shadows of the lit surface points ---------------------------------------------------
     int unshadowed = NS;                        // samples of this lnB's surface point that reach the light
     unsigned long long work = ballot(slit);      // lanes whose samples must really be tested (level 3)
+    const bool sum_needed = work != 0ull;        // shade_sum_needed(lit, term): else every lit lane's light sum is +0
     // need: per surface point, the casters (as positions among K's set bits) whose samples must be tested; with at most 32
     // casters (the static-layout build) it is one register, and one lane read per point in level 3
     using need_t = typename std::conditional<STRIDE == 32, uint32_t, unsigned long long>::type;
@@ -824,7 +825,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
       xw.v[6] += (unsigned)__popcll(work & ballot(lit && unshadowed == NS));
       xw.v[7] += (unsigned)__popcll(work & ballot(lit && unshadowed == 0));
     }
-    const f3 contrib = shade(lit, secondary, unshadowed, NS, term, inv_S, ray.col);
+    const f3 contrib = shade<(SS <= 64 ? SS : 0)>(lit, secondary, unshadowed, NS, term, inv_S, ray.col, sum_needed);
     // sum the AA rays of each pixel in index order (final_color_total +=, :415-425); a ray without a
     // contribution adds +0, which leaves the running sum unchanged bit for bit
     if (BIGAA) {

@@ -1,8 +1,10 @@
-// rt_selftest.hip — on-device self tests of the numerics building blocks (C ABI: rt_selftest_rcp).
+// rt_selftest.hip — on-device self tests of the numerics building blocks (C ABI: rt_selftest_rcp, rt_selftest_normalize,
+// rt_selftest_shade).
 #include <hip/hip_runtime.h>
 
 #include "rt_host.h"
 #include "rt_math.h"
+#include "rt_wave_common.h"
 
 namespace uobrt {
 
@@ -68,7 +70,66 @@ __global__ __launch_bounds__(256) void k_selftest_div(unsigned long long* out, u
   }
   if (bad) atomicAdd(&out[1], bad);
 }
+// shade() (rt_wave_common.h) on caller-given lanes: one wave per block, the wave's sample count from ns[].  SL: the
+// instantiation specialised on the sample count where there is a case for it below.
+template <int SS>
+__device__ __forceinline__ f3 selftest_shade_one(bool lit, bool secondary, int unshadowed, int NS, float term, float4 col) {
+  const float inv_S = (NS & (NS - 1)) == 0 ? 1.0f / (float)NS : 0.0f;           // as the host fills FrameParams::inv_S
+  return shade<SS>(lit, secondary, unshadowed, NS, term, inv_S, col, shade_sum_needed(lit, term));
+}
+template <bool SL>
+__global__ __launch_bounds__(64) void k_selftest_shade(const int* __restrict__ ns, const int* __restrict__ lit,
+                                                       const int* __restrict__ secondary, const int* __restrict__ unshadowed,
+                                                       const float* __restrict__ term, const float4* __restrict__ col,
+                                                       float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const int NS = __builtin_amdgcn_readfirstlane(ns[blockIdx.x]);
+  const bool l = lit[i] != 0, sec = secondary[i] != 0;
+  const int u = unshadowed[i];
+  const float t = term[i];
+  const float4 c = col[i];
+  f3 r;
+  if (SL && NS == 1) r = selftest_shade_one<1>(l, sec, u, 1, t, c);
+  else if (SL && NS == 5) r = selftest_shade_one<5>(l, sec, u, 5, t, c);
+  else if (SL && NS == 10) r = selftest_shade_one<10>(l, sec, u, 10, t, c);
+  else if (SL && NS == 16) r = selftest_shade_one<16>(l, sec, u, 16, t, c);
+  else if (SL && NS == 64) r = selftest_shade_one<64>(l, sec, u, 64, t, c);
+  else r = selftest_shade_one<0>(l, sec, u, NS, t, c);
+  out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
+}
 }  // namespace uobrt
+
+extern "C" int rt_selftest_shade(int32_t nwaves, const int32_t* ns, const int32_t* lit, const int32_t* secondary,
+                                 const int32_t* unshadowed, const float* term, const float* col, int32_t straight_line, float* out) {
+  using namespace uobrt;
+  if (nwaves < 1 || nwaves > (1 << 20) || !ns || !lit || !secondary || !unshadowed || !term || !col || !out) {
+    set_error("rt_selftest_shade: NULL argument or wave count outside 1 .. 2^20"); return RT_E_INVALID;
+  }
+  for (int w = 0; w < nwaves; ++w)
+    if (ns[w] < 1 || ns[w] > 4096) { set_error("rt_selftest_shade: ns[%d] = %d outside 1 .. 4096", w, ns[w]); return RT_E_INVALID; }
+  const size_t n = (size_t)nwaves * 64;
+  DevMem<int> d_ns, d_int;            // d_int: lit, secondary, unshadowed
+  DevMem<float> d_f;                  // term, col, out
+  if (d_ns.alloc((size_t)nwaves) != hipSuccess || d_int.alloc(3 * n) != hipSuccess || d_f.alloc(8 * n) != hipSuccess) {
+    set_error("hipMalloc failed (no device?)"); return RT_E_DEVICE;
+  }
+  hipError_t e = hipMemcpy(d_ns.p, ns, (size_t)nwaves * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_int.p, lit, n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_int.p + n, secondary, n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_int.p + 2 * n, unshadowed, n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_f.p, term, n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_f.p + n, col, n * 16, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { set_error("rt_selftest_shade: %s", hipGetErrorString(e)); return RT_E_DEVICE; }
+  const float4* d_col = reinterpret_cast<const float4*>(d_f.p + n);
+  if (straight_line)
+    hipLaunchKernelGGL(k_selftest_shade<true>, dim3(nwaves), dim3(64), 0, 0, d_ns.p, d_int.p, d_int.p + n, d_int.p + 2 * n, d_f.p, d_col, d_f.p + 5 * n);
+  else
+    hipLaunchKernelGGL(k_selftest_shade<false>, dim3(nwaves), dim3(64), 0, 0, d_ns.p, d_int.p, d_int.p + n, d_int.p + 2 * n, d_f.p, d_col, d_f.p + 5 * n);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(out, d_f.p + 5 * n, n * 12, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) { set_error("rt_selftest_shade: %s", hipGetErrorString(e)); return RT_E_DEVICE; }
+  return RT_OK;
+}
 
 extern "C" int rt_selftest_normalize(uint64_t out[8], uint32_t b_stride) {
   using namespace uobrt;

@@ -26,7 +26,7 @@ EXPORTS = (
     "rt_abi_version", "rt_last_error", "rt_config_default", "rt_config_owned_rows", "rt_init", "rt_render",
     "rt_render_device", "rt_count_work", "rt_count_executed", "rt_last_kernel_ms", "rt_destroy", "rt_scene_cornell_box",
     "rt_scene_load_obj", "rt_scene_load_obj_ex", "rt_triangle_compute_normal", "rt_scene_pack", "rt_rotation_matrix",
-    "rt_selftest_rcp", "rt_selftest_normalize", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_register_output", "rt_unregister_output",
+    "rt_selftest_rcp", "rt_selftest_normalize", "rt_selftest_shade", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_register_output", "rt_unregister_output",
     "rt_debug_band_copy_plan", "rt_update_scene", "rt_update_scene_device", "rt_debug_tile_data",
     "rt_trace_rays", "rt_trace_rays_device", "rt_debug_trace_stats",
     "rt_render_aov", "rt_render_aov_device", "rt_debug_aov_stats",
@@ -212,6 +212,21 @@ def selftest_normalize(b_stride=64):
     _check(lib().rt_selftest_normalize(out, C.c_uint32(b_stride)))
     v = list(out)
     return {"sqrt_mismatches": v[0], "div_mismatches": v[1], "div_pairs": v[2], "sqrt_example": v[3], "div_example": v[4]}
+
+
+def selftest_shade(ns, lit, secondary, unshadowed, term, col, straight_line=False):
+    """The kernels' shade() on caller-given lanes, one wave of 64 per entry of ns (include/uob_rt.h rt_selftest_shade):
+    lit, secondary, unshadowed, term [nwaves, 64], col [nwaves, 64, 4] -> float32 [nwaves, 64, 3]."""
+    ns = np.ascontiguousarray(ns, np.int32).reshape(-1)
+    w = ns.shape[0]
+    ints = [np.ascontiguousarray(a, np.int32).reshape(w, 64) for a in (lit, secondary, unshadowed)]
+    term = np.ascontiguousarray(term, np.float32).reshape(w, 64)
+    col = np.ascontiguousarray(col, np.float32).reshape(w, 64, 4)
+    out = np.zeros((w, 64, 3), np.float32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _check(lib().rt_selftest_shade(w, ip(ns), ip(ints[0]), ip(ints[1]), ip(ints[2]), _fp(term), _fp(col), int(bool(straight_line)),
+                                   _fp(out)))
+    return out
 
 
 def filter_params(width, height, passes=None, normal_min_dot=None, plane_eps=None, value_max_diff=None):
