@@ -115,16 +115,27 @@ def test_registered_output_is_the_same_frame(scene):
         multi.close()
 
 
-def test_listed_jobs_are_the_same_frame(scene):
-    """Last frame's expensive jobs are handed out first; pixels do not depend on it — three frames of one context (the
-    list exists from the second on) equal a fresh context's frame, whole frame and a band rank."""
+def test_listed_jobs_are_the_same_frame(scene, monkeypatch):
+    """Last frame's expensive jobs are handed out first; pixels do not depend on it — three frames of one context equal a
+    fresh context's frame, whole frame and a band rank.  At 1024 x 768 fill_params settles on 2-task jobs, for which
+    launch_frame keeps no list, so the rendering context is made with UOB_RT_JOB_TASKS=8 (64-pixel jobs; read once, in
+    rt_init): its first frame lists nothing (there is no mean cost yet), its second builds the list, and its third starts
+    from it, which UOB_RT_TIMELINE shows.  (Changing views and exact job counts: tests/test_gpu_frame_coverage.py.)"""
     rot, cam, light = rt.rotation_matrix(-0.1, 0.05), [0, 0, -3.2], [0.1, -0.5, -0.7]
     for extra in ({}, {"band_rows": 32, "band_index": 1, "band_count": 3}):
         cfg = abi.make_config(width=1024, height=768, aa_x=4, aa_y=2, shadow_samples=64, **extra)
         plain = rt.RayTracer(cfg, scene)
         ref = plain.render(rot, cam, light, 4400.0)
         plain.close()
+        monkeypatch.setenv("UOB_RT_JOB_TASKS", "8")
+        monkeypatch.setenv("UOB_RT_TIMELINE", "1")
         tr = rt.RayTracer(cfg, scene)
-        for _ in range(3):
+        monkeypatch.delenv("UOB_RT_JOB_TASKS")
+        monkeypatch.delenv("UOB_RT_TIMELINE")
+        njobs = 1024 // 64 * tr.rows
+        for k in range(3):
             assert np.array_equal(tr.render(rot, cam, light, 4400.0), ref)
+            t = tr.wave_timeline()
+            assert t["jobs"] == njobs and t["listed_jobs"] <= njobs // 3
+        assert t["listed_jobs"] > 0, "the third frame did not start from a list"
         tr.close()
