@@ -606,6 +606,13 @@ int rt_selftest_normalize(uint64_t out[8], uint32_t b_stride);
 int rt_selftest_shade(int32_t nwaves, const int32_t* ns, const int32_t* lit, const int32_t* secondary, const int32_t* unshadowed,
                       const float* term, const float* col, int32_t straight_line, float* out);
 
+/* On-device run of the wave kernel's all_within() (rt_wave_common.h: "no lane that takes part holds a value above the
+ * bound", decided by one compare and a ballot) beside the wave reduction it stands for, one wave of 64 lanes per entry of
+ * bound[]: lane l of wave w takes part when in[64 w + l] is non-zero and holds v[64 w + l], which must be >= +0 or NaN;
+ * bound[w] must be >= +0 unless some lane of the wave takes part.  out[2 w] receives all_within's answer (0 or 1) and
+ * out[2 w + 1] that of  max over the lanes of (in ? v : +0), as bit patterns  <=  bound[w].  All pointers are host memory.  */
+int rt_selftest_all_within(int32_t nwaves, const int32_t* in, const float* v, const float* bound, int32_t* out);
+
 /* Releases everything the context holds: it waits for the context's streams, side calls and filter calls, then frees its device memory,
  * events and streams (and those of every device of a multi-device context), and unregisters a registered output.   */
 void rt_destroy(rt_ctx* ctx);

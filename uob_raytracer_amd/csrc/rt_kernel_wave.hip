@@ -498,6 +498,17 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
   const int y = band_global_row_cold(P, lr);
   f3 outc = mk(0.f, 0.f, 0.f);
   // Level 1 of a WIDER point set than the task's, reused by the job's next tasks while their points stay inside it (below)
+  // MASKS: valid, task_sph and task_blocked are bits of ONE scalar register (a wave-uniform bool that lives across the task
+  // loop is kept as a 64-lane mask, a register pair each, and the scalar file is what this kernel spills), and the reuse test
+  // is a compare and a ballot (all_within) instead of a wave reduction.  Not in the instantiations specialised on fewer than
+  // 32 samples, as with shade(): their frames are jobs of one to four tasks that seldom reuse anything, and they ran 1 %
+  // slower with it; nor in the run-time LDS layout's (33..64 triangles, more than 64 samples), 2 % slower with it
+  // (profiles/wave_masks_ab.txt).  Those keep the three bools and the reduction, instruction for instruction.  The counting
+  // build, which is never timed, takes the new form: its counters are what tests/test_gpu_wave_masks.py holds against the
+  // parent's.
+  constexpr bool MASKS = !(SS > 0 && SS < 32) && (STRIDE != 0 || BIGAA || COUNT);
+  constexpr int kJkValid = 1, kJkSph = 2, kJkBlocked = 4;
+  int jk_flags = 0;
   bool jk_valid = false, jk_sph = false, jk_blocked = false;
   f3 jk_D0 = mk(0.f, 0.f, 0.f);
   float jk_ed = 0.0f;
@@ -625,14 +636,16 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
         // (Per-component widths — the points of a row on a plane differ along one line — keep fewer casters still, but three
         // reductions and the weighted sums cost more than that: 2.58; profiles/r03_l1_width.txt.)
         bool reuse = false;
-        if (jk_valid && all_sane) {
+        if ((MASKS ? (jk_flags & kJkValid) != 0 : jk_valid) && all_sane) {
           const f3 dj = dir - jk_D0;
-          reuse = wave_max_pos(slit ? norm_inf(dj) : 0.0f) <= jk_ed;
+          // (work is still ballot(slit) here; jk_ed = 0.9999 ed of a finite ed >= +0)
+          reuse = MASKS ? all_within(work, norm_inf(dj), jk_ed) : wave_max_pos(slit ? norm_inf(dj) : 0.0f) <= jk_ed;
         }
         int h = -1;                                 // the triangle Kh was certified for
         unsigned long long Kh = 0ull;
         if (reuse) {
-          K = jk_K; task_sph = jk_sph; task_blocked = jk_blocked; Kh = (unsigned long long)jk_Kh; h = jk_h;
+          K = jk_K; Kh = (unsigned long long)jk_Kh; h = jk_h;
+          task_sph = MASKS ? (jk_flags & kJkSph) != 0 : jk_sph; task_blocked = MASKS ? (jk_flags & kJkBlocked) != 0 : jk_blocked;
         } else {
         const int jr = 63 - __builtin_clzll(work);
         const f3 s0 = mk(rl(start.x, jr), rl(start.y, jr), rl(start.z, jr));
@@ -650,7 +663,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
         const float dlen_max = (dlen0 + 1.7321f * ed) * 1.000001f;
         const float dlen_min = fmaxf(dlen0 - 1.7321f * ed, 0.0f) * 0.999999f;
         const float es = 1.0002f * ed + 2e-6f * (P.light_inf + dlen_max);
-        jk_valid = false;
+        jk_flags = 0; jk_valid = false;
         if (all_sane && es < 1e30f && ed < 1e30f) {                    // finite, non-degenerate
           const float hh_task = 1.002f * hbox + 2e-6f * (dlen_max + hbox);
           if (P.nsph > 0)       // every sample direction lies within sqrt(3) (ed + hh) of D0, every start within es of s0
@@ -687,7 +700,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
           }
           jk_Kh = (kh_t)Kh; jk_h = h;
           // what the next tasks compare with: directions within 0.9999 ed of D0 (the bound itself allows 1.001 ed and more)
-          jk_valid = true; jk_D0 = D0; jk_ed = uniform(ed * 0.9999f); jk_K = K; jk_sph = task_sph; jk_blocked = task_blocked;
+          jk_D0 = D0; jk_ed = uniform(ed * 0.9999f); jk_K = K;
+          if (MASKS) jk_flags = kJkValid | (task_sph ? kJkSph : 0) | (task_blocked ? kJkBlocked : 0);
+          else { jk_valid = true; jk_sph = task_sph; jk_blocked = task_blocked; }
         }
         }
         // the smaller set for a task whose lit points all lie on h (level 3 is handed the set level 2 walks: `need` indexes it)

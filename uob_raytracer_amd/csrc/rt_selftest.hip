@@ -1,5 +1,5 @@
 // rt_selftest.hip — on-device self tests of the numerics building blocks (C ABI: rt_selftest_rcp, rt_selftest_normalize,
-// rt_selftest_shade).
+// rt_selftest_shade, rt_selftest_all_within).
 #include <hip/hip_runtime.h>
 
 #include "rt_host.h"
@@ -97,7 +97,41 @@ __global__ __launch_bounds__(64) void k_selftest_shade(const int* __restrict__ n
   else r = selftest_shade_one<0>(l, sec, u, NS, t, c);
   out[3 * i] = r.x; out[3 * i + 1] = r.y; out[3 * i + 2] = r.z;
 }
+// all_within() (rt_wave_common.h) beside the reduction it stands for, one wave per block with the wave's bound from bound[]:
+// out[2 w] = all_within, out[2 w + 1] = wave_max_pos(in ? v : 0.0f) <= bound.
+__global__ __launch_bounds__(64) void k_selftest_all_within(const int* __restrict__ in, const float* __restrict__ v,
+                                                            const float* __restrict__ bound, int* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const float b = uniform(bound[blockIdx.x]);
+  const bool lane_in = in[i] != 0;
+  const float x = v[i];
+  const bool got = all_within(ballot(lane_in), x, b);
+  const bool want = wave_max_pos(lane_in ? x : 0.0f) <= b;
+  if (threadIdx.x == 0) { out[2 * blockIdx.x] = got ? 1 : 0; out[2 * blockIdx.x + 1] = want ? 1 : 0; }
+}
 }  // namespace uobrt
+
+extern "C" int rt_selftest_all_within(int32_t nwaves, const int32_t* in, const float* v, const float* bound, int32_t* out) {
+  using namespace uobrt;
+  if (nwaves < 1 || nwaves > (1 << 20) || !in || !v || !bound || !out) {
+    set_error("rt_selftest_all_within: NULL argument or wave count outside 1 .. 2^20"); return RT_E_INVALID;
+  }
+  const size_t n = (size_t)nwaves * 64;
+  DevMem<int> d_int;                  // in, out
+  DevMem<float> d_f;                  // v, bound
+  if (d_int.alloc(n + 2 * (size_t)nwaves) != hipSuccess || d_f.alloc(n + (size_t)nwaves) != hipSuccess) {
+    set_error("hipMalloc failed (no device?)"); return RT_E_DEVICE;
+  }
+  hipError_t e = hipMemcpy(d_int.p, in, n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_f.p, v, n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_f.p + n, bound, (size_t)nwaves * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { set_error("rt_selftest_all_within: %s", hipGetErrorString(e)); return RT_E_DEVICE; }
+  hipLaunchKernelGGL(k_selftest_all_within, dim3(nwaves), dim3(64), 0, 0, d_int.p, d_f.p, d_f.p + n, d_int.p + n);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(out, d_int.p + n, (size_t)nwaves * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) { set_error("rt_selftest_all_within: %s", hipGetErrorString(e)); return RT_E_DEVICE; }
+  return RT_OK;
+}
 
 extern "C" int rt_selftest_shade(int32_t nwaves, const int32_t* ns, const int32_t* lit, const int32_t* secondary,
                                  const int32_t* unshadowed, const float* term, const float* col, int32_t straight_line, float* out) {

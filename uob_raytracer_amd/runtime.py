@@ -26,7 +26,7 @@ EXPORTS = (
     "rt_abi_version", "rt_last_error", "rt_config_default", "rt_config_owned_rows", "rt_init", "rt_render",
     "rt_render_device", "rt_count_work", "rt_count_executed", "rt_last_kernel_ms", "rt_destroy", "rt_scene_cornell_box",
     "rt_scene_load_obj", "rt_scene_load_obj_ex", "rt_triangle_compute_normal", "rt_scene_pack", "rt_rotation_matrix",
-    "rt_selftest_rcp", "rt_selftest_normalize", "rt_selftest_shade", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_register_output", "rt_unregister_output",
+    "rt_selftest_rcp", "rt_selftest_normalize", "rt_selftest_shade", "rt_selftest_all_within", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_register_output", "rt_unregister_output",
     "rt_debug_band_copy_plan", "rt_update_scene", "rt_update_scene_device", "rt_debug_tile_data",
     "rt_trace_rays", "rt_trace_rays_device", "rt_debug_trace_stats",
     "rt_render_aov", "rt_render_aov_device", "rt_debug_aov_stats",
@@ -227,6 +227,19 @@ def selftest_shade(ns, lit, secondary, unshadowed, term, col, straight_line=Fals
     _check(lib().rt_selftest_shade(w, ip(ns), ip(ints[0]), ip(ints[1]), ip(ints[2]), _fp(term), _fp(col), int(bool(straight_line)),
                                    _fp(out)))
     return out
+
+
+def selftest_all_within(lane_in, v, bound):
+    """The wave kernel's all_within() beside the wave reduction it stands for, one wave of 64 per entry of bound (include/uob_rt.h
+    rt_selftest_all_within): lane_in, v [nwaves, 64] -> (all_within's answers, the reduction's answers), bool [nwaves] each."""
+    bound = np.ascontiguousarray(bound, np.float32).reshape(-1)
+    w = bound.shape[0]
+    lane_in = np.ascontiguousarray(lane_in, np.int32).reshape(w, 64)
+    v = np.ascontiguousarray(v, np.float32).reshape(w, 64)
+    out = np.zeros((w, 2), np.int32)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    _check(lib().rt_selftest_all_within(w, ip(lane_in), _fp(v), _fp(bound), ip(out)))
+    return out[:, 0] != 0, out[:, 1] != 0
 
 
 def filter_params(width, height, passes=None, normal_min_dot=None, plane_eps=None, value_max_diff=None):
