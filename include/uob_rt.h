@@ -511,6 +511,97 @@ int rt_debug_filter_stats(rt_ctx* ctx, uint64_t out[8]);
 int rt_filter_plane_host(const rt_filter_params* params, const float* value, const float* position4, const float* normal4,
                          float* out);
 
+/* ---- temporal reprojection of per-pixel planes (rt_accumulate.hip) ------------------------------------
+ * Carries a per-pixel estimate from one view to the next: last view's history is gathered at the place where this view's
+ * surface point was seen then, under the AOV planes as guides, and the new sample is blended in.  Per pixel the history
+ * keeps the first two moments and a history length.  It reads no scene data.  With binary acceptance tests and a fixed
+ * operation order it is a pure FP32 function of its inputs; every implementation (the device kernel,
+ * rt_accumulate_plane_host) gives the same bits.
+ * Scope: the scene is assumed static between the two views.  Camera and light may move; geometry that moved fails the
+ * plane or prim test and restarts its history.  Motion vectors for posed or skinned objects are not built.
+ * Planes of `height` rows x `width` pixels, row-major, of the CURRENT view:
+ *   value      float32 [h][w]      this view's sample of the estimate;
+ *   position4  float32 [h][w][4]   the guides, in the layouts of rt_render_aov's position4 / normal4 planes.  A pixel is
+ *   normal4    float32 [h][w][4]   VALID iff position4.w > 0 (a NaN is invalid);
+ *   prim       int32   [h][w]      rt_render_aov's prim plane, or NULL: then no tap is tested for its primitive;
+ *   prev       rt_history_texel [h][w]   the history the previous call wrote as `next`, or NULL (first frame);
+ * and the outputs
+ *   next       rt_history_texel [h][w]   required, not the same pointer as prev; any other overlap is the caller's error;
+ *   out_mean, out_variance   float32 [h][w], each may be NULL.
+ * All arithmetic is FP32 without contraction, in exactly this order, for every pixel p = (x, y), with P / N the xyz of its
+ * guides and rot = prev_rot, W = width, H = height:
+ *   1. p not valid: mean = value (its bits), m2 = value * value, count = 0.
+ *   2. Projection into the previous view (only when prev != NULL): d = P - prev_cam component-wise;
+ *      q_j = (d.x*rot[j] + d.y*rot[4+j]) + d.z*rot[8+j] for j = 0, 1, 2 (the columns of rot: R^T d, which inverts the
+ *      frame's R * (bx, by*sy, focal) for a rotation matrix); fx = (q0 * prev_focal_px) / q2 + 0.5f * (float)W and
+ *      fy = (q1 * prev_focal_px) / q2 + 0.5f * (float)H, the divisions correctly rounded.  The pixel has a CANDIDATE iff
+ *      q2 > 0 && fx >= -1 && fx < (float)W && fy >= -1 && fy < (float)H; a NaN fails every comparison.  This inverts sample
+ *      0's primary ray (local x = x*aa_x - W*aa_x/2, local y*sy = (y - H/2)*aa_x at focal = prev_focal_px * aa_x), so the
+ *      guides of sample 0 of a still view reproject onto integer pixel coordinates up to rounding.
+ *   3. Taps: x0 = floorf(fx), y0 = floorf(fy), ax = fx - x0, ay = fy - y0 (both exact).  The four taps (x0+i, y0+j) are
+ *      visited with j outer and i inner, both ascending; wt = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay).  A tap with
+ *      record r is ACCEPTED iff it lies inside the plane, wt > 0, r.count > 0, prim == NULL || r.prim == prim[p],
+ *      (N.x*r.normal.x + N.y*r.normal.y) + N.z*r.normal.z >= normal_min_dot, and with e = r.position - P component-wise
+ *      fabsf((N.x*e.x + N.y*e.y) + N.z*e.z) <= plane_eps.  Over the accepted taps in visiting order:
+ *      num = num + wt * r.mean, num2 = num2 + wt * r.m2, den = den + wt, all from +0; cmin = the least r.count (exact).
+ *   4. prev == NULL, no candidate or no accepted tap: mean = value (its bits), m2 = value * value, count = 1.
+ *   5. Otherwise mp = num / den and sp = num2 / den, correctly rounded; n = min(cmin, (float)(max_history - 1)) + 1;
+ *      a = 1.0f / n; mean = mp + a * (value - mp); m2 = sp + a * (value * value - sp); count = n.
+ *   6. A NaN among the computed results — every m2, and the mean of step 5 — is stored as the quiet NaN 0x7FC00000 (the
+ *      sign of a generated NaN differs between x86 and the GPU; the filter has the same rule).  The mean of steps 1 and 4
+ *      is a copy and keeps the value's bits, a NaN's payload included.
+ *   7. next[p] = (P, mean, N, m2, count, prim[p] or -1, 0, 0): the guides are copied also for an invalid pixel;
+ *      out_mean[p] = mean; out_variance[p] = t > 0 ? t : 0 with t = m2 - mean * mean, so a NaN t gives 0.
+ * What follows exactly: a region whose values are all 1.0f (or all 0.0f) keeps them for as long as it finds history, since
+ * num == den (num == 0); normal_min_dot = 2 with unit normals rejects all history, so every valid pixel is a first frame;
+ * count is always an integer value when the history's counts are (0 .. max_history); the variance is never negative or NaN. */
+typedef struct rt_history_texel {      /* 48 bytes, 16-byte aligned in device memory */
+  float position[3]; float mean;       /* the pixel's guide position | accumulated first moment   */
+  float normal[3];   float m2;         /* the pixel's guide normal   | accumulated second moment  */
+  float count;                         /* history length, an integer value 0 .. max_history; 0 = no history (invalid pixel) */
+  int32_t prim;                        /* the pixel's primitive id (-1 when the call got no prim plane) */
+  float pad[2];                        /* written as 0 */
+} rt_history_texel;
+
+typedef struct rt_accumulate_params {
+  int32_t width, height;       /* >= 1; width * height <= 2^31                                            */
+  float   prev_rot[12];        /* the PREVIOUS view: rt_render's rot / cam, and its focal divided by aa_x  */
+  float   prev_cam[3];         /*   (focal in pixels); all finite, prev_focal_px > 0                       */
+  float   prev_focal_px;
+  float   normal_min_dot;      /* not NaN                                                                  */
+  float   plane_eps;           /* >= 0, not NaN                                                            */
+  int32_t max_history;         /* 1 .. 65536: the blend factor never falls below 1 / max_history           */
+} rt_accumulate_params;        /* 84 bytes */
+/* Identity prev_rot, zero prev_cam, prev_focal_px = width, normal_min_dot 0.9, plane_eps 0.01, max_history 32: defaults for
+ * a scene of the Cornell box's size.  They are stated, not tuned on images.                                              */
+void rt_accumulate_params_default(rt_accumulate_params* params, int32_t width, int32_t height);
+/* A NULL ctx, params or required plane (value, position4, normal4, next), any parameter outside the ranges above, a view
+ * that is not finite, and next == prev are RT_E_INVALID with a message that names the field or argument, before the
+ * context is looked at and before any device work.  Ordering: an accumulate call is no reader of the scene — it does not
+ * wait for updates, frames, passes, readers or filter calls, and they do not wait for it; it waits only for the context's
+ * previous accumulate call (they share the counters and the staging), and rt_destroy waits for it.  Ordering with whatever
+ * produces its input planes, the history included, is the caller's stream.  A multi-device context runs it on devices[0].
+ * rt_accumulate_plane: host arrays, blocking (staged through device memory the context keeps and only grows).
+ * rt_accumulate_plane_device: planes in device memory on the context's device, d_position4 / d_normal4 / d_prev / d_next
+ * 16-byte aligned, enqueued on hip_stream (NULL = default stream) after the caller's earlier work; returns without
+ * synchronising, and no stage waits for the host.  It needs no scratch: the history buffers are the caller's.  A context
+ * that never accumulates allocates nothing for the family.                                                               */
+int rt_accumulate_plane(rt_ctx* ctx, const rt_accumulate_params* params, const float* value, const float* position4,
+                        const float* normal4, const int32_t* prim, const rt_history_texel* prev, rt_history_texel* next,
+                        float* out_mean, float* out_variance);
+int rt_accumulate_plane_device(rt_ctx* ctx, const rt_accumulate_params* params, const void* d_value, const void* d_position4,
+                               const void* d_normal4, const void* d_prim, const void* d_prev, void* d_next, void* d_out_mean,
+                               void* d_out_variance, void* hip_stream);
+/* Diagnostic: work counters of the context's most recent accumulate call (synchronises it; zeros before the first).  out[0]
+ * pixels, out[1] valid pixels, out[2] valid pixels that found history (at least one accepted tap), out[3] accepted taps,
+ * out[4] valid pixels without a candidate (behind the previous camera or outside its frame), out[5..7] 0.  A call without
+ * prev makes no projection: out[2..4] are 0.                                                                             */
+int rt_debug_accumulate_stats(rt_ctx* ctx, uint64_t out[8]);
+/* The same function on the host (CPU only, no context): the statement the device kernel is pinned against.  Same checks. */
+int rt_accumulate_plane_host(const rt_accumulate_params* params, const float* value, const float* position4,
+                             const float* normal4, const int32_t* prim, const rt_history_texel* prev, rt_history_texel* next,
+                             float* out_mean, float* out_variance);
+
 /* Diagnostic, mesh kernel (n > 64): the cost of every 16x16-pixel block of the most recent frame in s_memtime ticks
  * (shader cycles) — the scheduling state "last frame's expensive blocks first" is built from it.  Row-major over
  * ceil(owned_rows/16) x ceil(width/16) blocks; writes min(count, cap) values, returns the block count, or
@@ -613,7 +704,7 @@ int rt_selftest_shade(int32_t nwaves, const int32_t* ns, const int32_t* lit, con
  * out[2 w + 1] that of  max over the lanes of (in ? v : +0), as bit patterns  <=  bound[w].  All pointers are host memory.  */
 int rt_selftest_all_within(int32_t nwaves, const int32_t* in, const float* v, const float* bound, int32_t* out);
 
-/* Releases everything the context holds: it waits for the context's streams, side calls and filter calls, then frees its device memory,
+/* Releases everything the context holds: it waits for the context's streams, side calls, filter calls and accumulate calls, then frees its device memory,
  * events and streams (and those of every device of a multi-device context), and unregisters a registered output.   */
 void rt_destroy(rt_ctx* ctx);
 

@@ -72,6 +72,25 @@ class RtFilterParams(C.Structure):
 RT_FILTER_MAX_PASSES = 8
 
 
+class RtAccumulateParams(C.Structure):
+    """rt_accumulate_params: the plane size, the previous view and the acceptance tests of rt_accumulate_plane (84 bytes)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("prev_rot", C.c_float * 12), ("prev_cam", C.c_float * 3),
+                ("prev_focal_px", C.c_float), ("normal_min_dot", C.c_float), ("plane_eps", C.c_float), ("max_history", C.c_int32)]
+
+
+class RtHistoryTexel(C.Structure):
+    """rt_history_texel: one pixel of a history plane (48 bytes)."""
+    _fields_ = [("position", C.c_float * 3), ("mean", C.c_float), ("normal", C.c_float * 3), ("m2", C.c_float),
+                ("count", C.c_float), ("prim", C.c_int32), ("pad", C.c_float * 2)]
+
+
+# A history plane in Python is the float32 [h, w, HISTORY_WORDS] view of rt_history_texel[h][w]: words 0..2 position, 3 mean,
+# 4..6 normal, 7 m2, 8 count, 9 the int32 BITS of prim, 10..11 zero
+HISTORY_WORDS = 12
+HISTORY_MEAN, HISTORY_M2, HISTORY_COUNT, HISTORY_PRIM = 3, 7, 8, 9
+RT_ACCUMULATE_MAX_HISTORY = 65536
+
+
 class RtTriangle(C.Structure):
     _fields_ = [(k, C.c_float * 4) for k in ("v0", "v1", "v2", "normal", "color")]
 

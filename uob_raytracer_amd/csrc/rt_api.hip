@@ -874,7 +874,7 @@ rt_ctx::~rt_ctx() {
   hipSetDevice(device);
   if (stream) hipStreamSynchronize(stream);
   if (aux_stream) hipStreamSynchronize(aux_stream);
-  for (SideCall* k : {&query, &shade, &rad, &aov, &filter})     // no call of any family may still be running
+  for (SideCall* k : {&query, &shade, &rad, &aov, &filter, &accum})     // no call of any family may still be running
     if (k->ev) hipEventSynchronize(k->ev);
   if (reg_host && reg_owner) hipHostUnregister(reg_host);
 }

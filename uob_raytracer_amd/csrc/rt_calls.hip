@@ -1,6 +1,7 @@
 // rt_calls.hip — the calls beside the frame, over the C ABI (include/uob_rt.h): ray queries (rt_trace_rays, rt_ray_query.hip),
 // shade calls (rt_shade_points, rt_shade.hip), radiance calls (rt_radiance_rays, rt_radiance.hip), AOV passes
-// (rt_render_aov, rt_aov.hip) and filter calls (rt_filter_plane, rt_filter.hip).  Each family has an enqueue on the caller's stream (the *_device entry), a blocking entry for
+// (rt_render_aov, rt_aov.hip), filter calls (rt_filter_plane, rt_filter.hip) and accumulate calls (rt_accumulate_plane,
+// rt_accumulate.hip).  Each family has an enqueue on the caller's stream (the *_device entry), a blocking entry for
 // host arrays that stages them through the family's device buffer, and a stats export.  What the families share is written
 // once: the steps around a call (call_prepare / reader_begin / call_end), the blocking entry (run_blocking) and the stats
 // reader (read_stats).  Which operation waits for which is DESIGN.md 4.9 (rt_host.h wait_scene_readers, wait_aov, wait_scene).
@@ -256,7 +257,61 @@ static int enqueue_filter(rt_ctx* c, const rt_filter_params& p, const float* d_v
   return call_end(c, &c->filter, s);
 }
 
+// ---- accumulate calls (rt_accumulate_plane / rt_accumulate_plane_device, rt_accumulate.hip) ---------------------------
+// One accumulate call of a single-device context on stream s (device planes of c->device); arguments checked.  Not a reader
+// of the scene: it waits for the accumulate call before it, whose counters it takes over, and for nothing else.
+static int enqueue_accumulate(rt_ctx* c, const rt_accumulate_params& p, const float* d_value, const float4* d_pos, const float4* d_nrm,
+                              const int* d_prim, const float4* d_prev, float4* d_next, float* d_mean, float* d_var, hipStream_t s) {
+  const int words = accumulate_stats_words();
+  const int rc = call_prepare(c, &c->accum, words);
+  if (rc != RT_OK) return rc;
+  if (c->accum.pending) HIP_TRY(hipStreamWaitEvent(s, c->accum.ev, 0));
+  HIP_TRY(hipMemsetAsync(c->accum.d_stats, 0, (size_t)words * sizeof(unsigned long long), s));
+  launch_accumulate(p, d_value, d_pos, d_nrm, d_prim, d_prev, d_next, d_mean, d_var, c->accum.d_stats, s);
+  return call_end(c, &c->accum, s);
+}
+
 extern "C" {
+
+int rt_accumulate_plane_device(rt_ctx* c, const rt_accumulate_params* p, const void* d_value, const void* d_position4,
+                               const void* d_normal4, const void* d_prim, const void* d_prev, void* d_next, void* d_out_mean,
+                               void* d_out_variance, void* hip_stream) {
+  if (!c) { set_error("rt_accumulate_plane_device: ctx is NULL"); return RT_E_INVALID; }
+  const int rc = accumulate_check(p, d_value, d_position4, d_normal4, d_prev, d_next, "rt_accumulate_plane_device");
+  if (rc != RT_OK) return rc;
+  if ((((uintptr_t)d_position4 | (uintptr_t)d_normal4 | (uintptr_t)d_prev | (uintptr_t)d_next) & 15) != 0) {
+    set_error("rt_accumulate_plane_device: d_position4 / d_normal4 / d_prev / d_next is not 16-byte aligned"); return RT_E_INVALID;
+  }
+  DeviceGuard guard;
+  return enqueue_accumulate(lead_ctx(c), *p, (const float*)d_value, (const float4*)d_position4, (const float4*)d_normal4,
+                            (const int*)d_prim, (const float4*)d_prev, (float4*)d_next, (float*)d_out_mean, (float*)d_out_variance,
+                            (hipStream_t)hip_stream);
+}
+
+int rt_accumulate_plane(rt_ctx* c, const rt_accumulate_params* p, const float* value, const float* position4, const float* normal4,
+                        const int32_t* prim, const rt_history_texel* prev, rt_history_texel* next, float* out_mean,
+                        float* out_variance) {
+  if (!c) { set_error("rt_accumulate_plane: ctx is NULL"); return RT_E_INVALID; }
+  const int rc = accumulate_check(p, value, position4, normal4, prev, next, "rt_accumulate_plane");
+  if (rc != RT_OK) return rc;
+  c = lead_ctx(c);
+  DeviceGuard guard;
+  const size_t n = (size_t)p->width * p->height;
+  // (what the kernel loads and stores as float4 first: the start of the staging buffer is aligned for that, and every one
+  // of these is a multiple of 16 bytes long)
+  IoSlot io[8] = {{(void*)position4, n * 16, true}, {(void*)normal4, n * 16, true}, {(void*)prev, n * 48, true}, {next, n * 48, false},
+                  {(void*)value, n * 4, true},      {(void*)prim, n * 4, true},     {out_mean, n * 4, false},    {out_variance, n * 4, false}};
+  return run_blocking(c, &c->accum, io, 8, [&] {
+    return enqueue_accumulate(c, *p, (const float*)io[4].dev, (const float4*)io[0].dev, (const float4*)io[1].dev, (const int*)io[5].dev,
+                              (const float4*)io[2].dev, (float4*)io[3].dev, (float*)io[6].dev, (float*)io[7].dev, c->stream);
+  });
+}
+
+int rt_debug_accumulate_stats(rt_ctx* c, uint64_t out[8]) {
+  const int rc = read_stats(c, &rt_ctx::accum, -1, out);
+  if (rc == RT_OK) out[5] = out[6] = out[7] = 0;
+  return rc;
+}
 
 int rt_filter_plane_device(rt_ctx* c, const rt_filter_params* p, const void* d_value, const void* d_position4, const void* d_normal4,
                            void* d_out, void* hip_stream) {

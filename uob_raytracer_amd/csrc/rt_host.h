@@ -97,6 +97,15 @@ void launch_filter_counters(unsigned long long* stats, hipStream_t stream);
 // filter_host.cpp: the ranges of rt_filter_params and the plane pointers, before anything else is looked at
 int filter_check(const rt_filter_params* p, const void* value, const void* position4, const void* normal4, const void* out,
                  const char* fn);
+// rt_accumulate.hip: the temporal reprojection of per-pixel planes (include/uob_rt.h rt_accumulate_plane): one
+// launch over the plane in the filter's tiles (kFilterTX x kFilterTY adjacent pixels) and one that sums the counters
+int accumulate_stats_words();
+void launch_accumulate(const rt_accumulate_params& p, const float* d_value, const float4* d_pos, const float4* d_nrm, const int* d_prim,
+                       const float4* d_prev, float4* d_next, float* d_out_mean, float* d_out_variance, unsigned long long* stats,
+                       hipStream_t stream);
+// accumulate_host.cpp: the ranges of rt_accumulate_params and the plane pointers, before anything else is looked at
+int accumulate_check(const rt_accumulate_params* p, const void* value, const void* position4, const void* normal4, const void* prev,
+                     const void* next, const char* fn);
 // rt_tile_sort.hip: the vertices' box, and the mesh kernel's tiled order and per-tile data (host arithmetic)
 void vertex_box(const float* vertices4, int n, float lo[3], float hi[3]);
 std::vector<int> tiled_order(const float* v4, int n, bool morton);
@@ -299,6 +308,10 @@ struct rt_ctx {
   // filter_guides: the packed guide records, 32 bytes per pixel; filter_planes: the two planes the passes alternate between
   uobrt::SideCall filter;
   uobrt::DevBuffer filter_guides, filter_planes;
+  // Accumulate calls (rt_accumulate.hip): like the filter calls they read no scene data, wait only for the accumulate call
+  // before them (they share the counters and the staging) and are waited for by the next one and the destructor.  They
+  // need no scratch: the history buffers are the caller's
+  uobrt::SideCall accum;
 };
 
 namespace uobrt {

@@ -38,6 +38,8 @@ EXPORTS = (
     "rt_scene_skin", "rt_set_skin", "rt_pose_skin", "rt_pose_skin_device", "rt_debug_skin_info",
     "rt_debug_live_device_objects",
     "rt_filter_params_default", "rt_filter_plane", "rt_filter_plane_device", "rt_debug_filter_stats", "rt_filter_plane_host",
+    "rt_accumulate_params_default", "rt_accumulate_plane", "rt_accumulate_plane_device", "rt_debug_accumulate_stats",
+    "rt_accumulate_plane_host",
 )
 
 # rt_debug_live_device_objects slots
@@ -57,6 +59,10 @@ RADIANCE_STATS_KEYS = ("rays", "bounce_rays", "shaded_points", "sample_rays", "c
 
 # rt_debug_filter_stats slots
 FILTER_STATS_KEYS = ("pixels", "passes", "accepted_taps", "valid_pixels", "kept", "reserved5", "reserved6", "reserved7")
+
+# rt_debug_accumulate_stats slots
+ACCUMULATE_STATS_KEYS = ("pixels", "valid_pixels", "found_history", "accepted_taps", "no_candidate", "reserved5", "reserved6",
+                         "reserved7")
 
 _lib = None
 
@@ -132,6 +138,13 @@ def lib():
         L.rt_filter_plane_device.argtypes = [vp, C.POINTER(abi.RtFilterParams), vp, vp, vp, vp, vp]
         L.rt_debug_filter_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_filter_plane_host.argtypes = [C.POINTER(abi.RtFilterParams), fp, fp, fp, fp]
+        ap, ip = C.POINTER(abi.RtAccumulateParams), C.POINTER(C.c_int32)
+        L.rt_accumulate_params_default.argtypes = [ap, C.c_int32, C.c_int32]
+        L.rt_accumulate_params_default.restype = None
+        L.rt_accumulate_plane.argtypes = [vp, ap, fp, fp, fp, ip, fp, fp, fp, fp]
+        L.rt_accumulate_plane_device.argtypes = [vp, ap] + [vp] * 9
+        L.rt_debug_accumulate_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_accumulate_plane_host.argtypes = [ap, fp, fp, fp, ip, fp, fp, fp, fp]
         L.rt_debug_block_costs.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int32]
         L.rt_debug_world_masks.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.rt_debug_wave_timeline.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -284,6 +297,66 @@ def filter_plane_host(value, position4, normal4, out=None, **params):
     return out
 
 
+def accumulate_params(width, height, prev_rot=None, prev_cam=None, prev_focal=None, aa_x=1, **overrides):
+    """rt_accumulate_params of a width x height plane: rt_accumulate_params_default's values (identity view, focal = width,
+    0.9, 0.01, 32 frames) unless given.  prev_rot / prev_cam / prev_focal are the previous view as rt_render takes it, so
+    prev_focal is in AA sub-pixels along x and is divided by aa_x here.  overrides: normal_min_dot, plane_eps, max_history,
+    prev_focal_px."""
+    p = abi.RtAccumulateParams()
+    lib().rt_accumulate_params_default(C.byref(p), int(width), int(height))
+    if prev_rot is not None:
+        p.prev_rot[:] = [float(v) for v in np.asarray(prev_rot, np.float32).reshape(-1)[:12]]
+    if prev_cam is not None:
+        p.prev_cam[:] = [float(v) for v in np.asarray(prev_cam, np.float32).reshape(-1)[:3]]
+    if prev_focal is not None:
+        p.prev_focal_px = np.float32(prev_focal) / np.float32(aa_x)
+    for key, v in overrides.items():
+        if key not in ("normal_min_dot", "plane_eps", "max_history", "prev_focal_px"):
+            raise TypeError("accumulate_params: unknown parameter %r" % key)
+        if v is not None:
+            setattr(p, key, v)
+    return p
+
+
+def _accumulate_host_planes(value, position4, normal4, prim, prev):
+    """The numpy planes of a blocking accumulate call: value float32 [h, w], the guides [h, w, 4], prim int32 [h, w] or None,
+    prev float32 [h, w, 12] (abi.HISTORY_WORDS) or None; and fresh next / out_mean / out_variance."""
+    if not isinstance(value, np.ndarray) or value.ndim != 2:
+        raise ValueError("value must be a numpy array of shape [height, width]")
+    h, w = value.shape
+    v = np.ascontiguousarray(value, np.float32)
+    pos = np.ascontiguousarray(position4, np.float32)
+    nrm = np.ascontiguousarray(normal4, np.float32)
+    if pos.shape != (h, w, 4) or nrm.shape != (h, w, 4):
+        raise ValueError("position4 and normal4 must have the shape [%d, %d, 4]" % (h, w))
+    if prim is not None:
+        prim = np.ascontiguousarray(prim, np.int32)
+        if prim.shape != (h, w):
+            raise ValueError("prim must have the shape [%d, %d]" % (h, w))
+    if prev is not None:
+        if not isinstance(prev, np.ndarray) or prev.dtype != np.float32 or prev.shape != (h, w, abi.HISTORY_WORDS):
+            raise ValueError("prev must be a float32 array of shape [%d, %d, %d]" % (h, w, abi.HISTORY_WORDS))
+        prev = np.ascontiguousarray(prev)
+    nxt = np.empty((h, w, abi.HISTORY_WORDS), np.float32)
+    return h, w, v, pos, nrm, prim, prev, nxt, np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+
+
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+
+
+def accumulate_plane_host(value, position4, normal4, prim=None, prev=None, params=None, **kw):
+    """The temporal reprojection on the host (rt_accumulate_plane_host; needs no device): value float32 [h, w], position4 /
+    normal4 float32 [h, w, 4], prim int32 [h, w] or None, prev = the `next` of the previous call or None -> (next float32
+    [h, w, 12], mean [h, w], variance [h, w]).  params: an abi.RtAccumulateParams, or kw for accumulate_params (prev_rot,
+    prev_cam, prev_focal, aa_x, normal_min_dot, plane_eps, max_history)."""
+    h, w, v, pos, nrm, prim, prev, nxt, mean, var = _accumulate_host_planes(value, position4, normal4, prim, prev)
+    p = params if params is not None else accumulate_params(w, h, **kw)
+    _check(lib().rt_accumulate_plane_host(C.byref(p), _fp(v), _fp(pos), _fp(nrm), _ip(prim), _fp(prev) if prev is not None else None,
+                                          _fp(nxt), _fp(mean), _fp(var)))
+    return nxt, mean, var
+
+
 def default_config():
     cfg = abi.RtConfig()
     lib().rt_config_default(C.byref(cfg))
@@ -428,6 +501,7 @@ class RayTracer:
         self.skin = None            # (first, count, nbones) of set_skin; forgotten likewise, and by set_objects
         # the device the context's queries run on (devices[0]; None: the device that was current at rt_init)
         self.device = cfg.devices[0] if cfg.num_devices >= 1 else (cfg.device if cfg.device >= 0 else None)
+        self._history = None        # render_accumulated_light: [the two history tensors, which is current, the view, frames]
 
     @staticmethod
     def _update_flags(reorder, device_tiles):
@@ -967,6 +1041,111 @@ class RayTracer:
         vis_f = self.filter_plane_device(vis, pos, nrm, **params)
         out = term * torch.where(hit, vis_f, zero)
         return (out, term, vis, vis_f) if want_parts else out
+
+    def accumulate_plane(self, value, position4, normal4, prim=None, prev=None, params=None, **kw):
+        """The temporal reprojection of a per-pixel plane on the device (rt_accumulate_plane), blocking: numpy planes as
+        runtime.accumulate_plane_host takes them, and the same bits -> (next, mean, variance)."""
+        h, w, v, pos, nrm, prim, prev, nxt, mean, var = _accumulate_host_planes(value, position4, normal4, prim, prev)
+        p = params if params is not None else accumulate_params(w, h, **kw)
+        _check(lib().rt_accumulate_plane(self._h, C.byref(p), _fp(v), _fp(pos), _fp(nrm), _ip(prim),
+                                         _fp(prev) if prev is not None else None, _fp(nxt), _fp(mean), _fp(var)))
+        return nxt, mean, var
+
+    def accumulate_plane_device(self, value, position4, normal4, prim=None, prev=None, next=None, out_mean=None, out_variance=None,
+                                want_mean=True, want_variance=True, stream=None, params=None, **kw):
+        """Enqueue rt_accumulate_plane_device on torch tensors of the context's device, without synchronising.  value: float32
+        [h, w]; position4, normal4: float32 [h, w, 4] (the AOV planes); prim: int32 [h, w] or None; prev: float32 [h, w, 12]
+        (the `next` of the previous call) or None; next, out_mean, out_variance: allocated when None (the two planes only
+        when wanted).  stream: a torch stream or a raw hipStream_t (default: torch's current stream).  Returns (next, mean,
+        variance), None for a plane that was not asked for."""
+        import torch
+        dev = self._torch_device()
+        if not isinstance(value, torch.Tensor) or value.dim() != 2:
+            raise ValueError("value must be a torch tensor of shape [height, width]")
+        h, w = value.shape
+        _need("value", value, torch.float32, (h, w), dev)
+        _need("position4", position4, torch.float32, (h, w, 4), dev)
+        _need("normal4", normal4, torch.float32, (h, w, 4), dev)
+        if prim is not None:
+            _need("prim", prim, torch.int32, (h, w), dev)
+        if prev is not None:
+            _need("prev", prev, torch.float32, (h, w, abi.HISTORY_WORDS), dev)
+        if next is None:
+            next = torch.empty((h, w, abi.HISTORY_WORDS), dtype=torch.float32, device=dev)
+        _need("next", next, torch.float32, (h, w, abi.HISTORY_WORDS), dev)
+        if out_mean is None and want_mean:
+            out_mean = torch.empty((h, w), dtype=torch.float32, device=dev)
+        if out_variance is None and want_variance:
+            out_variance = torch.empty((h, w), dtype=torch.float32, device=dev)
+        for name, t in (("out_mean", out_mean), ("out_variance", out_variance)):
+            if t is not None:
+                _need(name, t, torch.float32, (h, w), dev)
+        p = params if params is not None else accumulate_params(w, h, **kw)
+        raw = self._raw_stream(stream, dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        _check(lib().rt_accumulate_plane_device(self._h, C.byref(p), ptr(value), ptr(position4), ptr(normal4), ptr(prim), ptr(prev),
+                                                ptr(next), ptr(out_mean), ptr(out_variance), C.c_void_p(raw)))
+        return next, out_mean, out_variance
+
+    def accumulate_stats(self):
+        """Work counters of the context's most recent accumulate call (rt_debug_accumulate_stats): dict of
+        ACCUMULATE_STATS_KEYS."""
+        return self._stats("rt_debug_accumulate_stats", ACCUMULATE_STATS_KEYS)
+
+    def reset_history(self):
+        """Forget what render_accumulated_light keeps between its calls: the next one is a first frame again."""
+        self._history = None
+
+    def render_accumulated_light(self, rot, cam, light, focal, sample=0, filter=False, want_parts=False, **params):
+        """render_filtered_light's direct light with its shadow term accumulated over the calls of a sequence, on the device:
+        an AOV pass (position, normal, prim of AA sample `sample`), a shade call with counts whose seeds are (pixel id +
+        frame index * rows * width) mod 2^24, so that every frame of a sequence draws another jitter stream, the visibility
+        V = counts / shadow_samples, an accumulate call against the history and the view the object kept from its previous
+        call (two history tensors alternate; params: normal_min_dot, plane_eps, max_history), and term * V_mean -> torch
+        float32 [rows, W], 0 where the pixel sees nothing.  filter=True runs the a-trous filter (its defaults) over V_mean
+        first.  want_parts: also (term, V, V_mean, variance, count), V_mean as accumulated (unfiltered).  reset_history() starts a new sequence.  Runs on torch's
+        current stream; does not synchronise.  The same refusals as render_filtered_light."""
+        import math
+        import torch
+        aa = self.cfg.aa_x * self.cfg.aa_y
+        if sample is None or isinstance(sample, bool) or int(sample) != sample or not 0 <= int(sample) < aa:
+            raise ValueError("sample must be one AA sample index in [0, %d)" % aa)
+        if max(self.cfg.band_count, 1) != 1:
+            raise ValueError("render_accumulated_light: a context of row bands does not hold neighbouring rows")
+        if self.cfg.width * self.cfg.height > abi.RT_SHADE_SEED_MAX:
+            raise ValueError("render_accumulated_light: %d x %d pixels exceed the seed domain of 2^24 ids" % (self.cfg.width, self.cfg.height))
+        dev = self._torch_device()
+        shape = (self.rows, self.width)
+        count = shape[0] * shape[1]
+        if self._history is None:
+            hist = [torch.empty(shape + (abi.HISTORY_WORDS,), dtype=torch.float32, device=dev) for _ in range(2)]
+            self._history = [hist, 0, None, 0]
+        hist, cur, view, frame = self._history
+        planes = {"prim": torch.empty(shape, dtype=torch.int32, device=dev),
+                  "position": torch.empty(shape + (4,), dtype=torch.float32, device=dev),
+                  "normal": torch.empty(shape + (4,), dtype=torch.float32, device=dev)}
+        self.render_aov_device(rot, cam, focal, sample=sample, out=planes)
+        pos, nrm = planes["position"], planes["normal"]
+        seeds = ((torch.arange(count, dtype=torch.int64, device=dev) + frame * count) % abi.RT_SHADE_SEED_MAX).to(torch.int32)
+        p6 = torch.cat([pos[..., :3], nrm[..., :3]], -1).reshape(-1, 6).contiguous()
+        _, counts = self.shade_points_device(p6, light, seeds=seeds, want_counts=True)
+        hit = planes["prim"] != -1
+        zero = torch.zeros(shape, dtype=torch.float32, device=dev)
+        vis = torch.where(hit, counts.reshape(shape).to(torch.float32) / float(self.cfg.shadow_samples), zero)
+        d = torch.tensor(np.ascontiguousarray(light, np.float32)[:3], device=dev) - pos[..., :3]
+        r2 = (d * d).sum(-1)
+        term = 16.0 * (d * nrm[..., :3]).sum(-1).clamp_min(0.0) / (4.0 * math.pi * r2)
+        term = torch.where(hit, term, zero)
+        if view is None:
+            p, prev = accumulate_params(shape[1], shape[0], **params), None
+        else:
+            p, prev = accumulate_params(shape[1], shape[0], view[0], view[1], view[2], aa_x=self.cfg.aa_x, **params), hist[cur]
+        nxt, vis_m, var = self.accumulate_plane_device(vis, pos, nrm, prim=planes["prim"], prev=prev, next=hist[1 - cur], params=p)
+        r, c, _ = self._args(rot, cam, cam)
+        self._history = [hist, 1 - cur, (r, c, float(focal)), frame + 1]
+        vis_o = self.filter_plane_device(vis_m, pos, nrm) if filter else vis_m
+        out = term * torch.where(hit, vis_o, zero)
+        return (out, term, vis, vis_m, var, nxt[..., abi.HISTORY_COUNT].clone()) if want_parts else out
 
     def shade_stats(self):
         """Work counters of the context's most recent shade call (rt_debug_shade_stats): dict of SHADE_STATS_KEYS."""
