@@ -655,6 +655,17 @@ int rt_unregister_output(rt_ctx* ctx);
  * RT_E_UNSUPPORTED when the context was not created with the knob set or its last frame ran on another kernel. */
 int rt_debug_wave_timeline(rt_ctx* ctx, uint64_t out[8]);
 
+/* Diagnostic, wave kernel: the tile seeds of the most recent frame (DESIGN.md 4.1 "tile seeds"; devices[0]'s of a
+ * multi-device context).  The frame is cut into tiles of dims[2] rows x one job's pixels; before a frame whose kernel
+ * takes the seed a pre-pass leaves one 64-byte record per tile, indexed [global row / dims[2]][job column]:
+ *   float D0[3], ed;  uint64 K, Kh, Kp;  int32 h;  uint32 flags (1: primary part valid, 2: shadow part valid);  16 bytes unused
+ *   dims[0] tile rows   dims[1] tiles per row (jobs per row)   dims[2] rows per tile — all 0 when the last frame took no
+ *   seed (UOB_RT_NO_SEED=1, another kernel or instantiation, no frame yet): then nothing is copied and the counters are 0
+ *   counters[0] tiles with a valid primary part   counters[1] tiles with a valid shadow part
+ *   counters[2], counters[3] jobs of this context's rows that started from one (every job reads its tile's record)
+ * Copies min(tiles, cap) records to `records` (may be NULL with cap 0).  Waits for the context's last frame.            */
+int rt_debug_wave_seeds(rt_ctx* ctx, void* records, int64_t cap, int32_t dims[3], uint64_t counters[4]);
+
 /* Diagnostic, several devices in one context (rt_config.devices): the copies that carry device k's packed bands
  * (bands k, k+N, ... of device_band_rows rows, owned rows packed top to bottom in its stripe) to image order in a
  * destination frame of `width` x `height` elements of elem_bytes — exactly what rt_render / rt_render_device enqueue

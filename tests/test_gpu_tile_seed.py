@@ -1,0 +1,480 @@
+"""-m gpu: the wave kernel's tile seeds (rt_kernel_wave.hip rt_wave_seed, DESIGN.md 4.1 "tile seeds").
+
+Before a frame of the (4x2 AA, 64 samples) instantiation a pre-pass bounds every screen tile (UOB_RT_SEED_ROWS rows of one
+job column) once: which triangles a primary ray of the tile can hit, and — where that is one diffuse triangle — a level 1 of
+the shadow cull over the whole tile.  A job starts from its tile's record instead of from nothing.  The seed may change
+how much work a job does, never a bit of the frame.
+
+Frames: contexts made under UOB_RT_JOB_TASKS=8 (64-pixel jobs, as on the 4096^2 frame) and UOB_RT_SEED_ROWS of 1, 4 and 16.
+  * the strips of tests/wave_masks_util.py (128x8) against UOB_RT_NO_SEED=1, RT_FLAG_NO_CULL, the thread-per-pixel kernel
+    and the CPU oracle, ARGB and float tap, bit for bit; the other samplings there take no seed and stay what they were;
+  * windows of 65 536 pixels of the same views through a longer lens (WINDOWS below; 8x gives the pixel pitch of the 4096^2
+    frame, at which a 64-pixel tile is small against the room and level 1 over a tile can come out empty) for what the seed
+    does: the table
+    (RayTracer.wave_seeds) is held against the AOV pass's primitive ids tile by tile, and its counters against
+    tests/golden/tile_seed_counters.json, recorded by tools/record_tile_seed_golden.py from the build whose frames these
+    tests showed identical;
+  * frame shapes at which the table's indexing can go wrong; sequences of frames of one context with the view, the light,
+    the scene and the spheres changing in between; two streams; degenerate views.
+"""
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+
+import frame_coverage_util as fc
+import wave_masks_util as wm
+from conftest import ROOT
+from uob_raytracer_amd import abi, runtime as rt
+
+pytestmark = pytest.mark.gpu
+
+ROWS = ("1", "4", "16")
+NO_SEED = {"UOB_RT_NO_SEED": "1"}
+LENS = 8.0                                   # 512 pixels across, of a 4096-pixel view
+# view -> (width, height, lens) of its window: 65 536 pixels each.  The middle of the default view is the tall block and the
+# glass sphere, where a ray's line meets several triangles and no tile holds anything: its window is one job column of 1024
+# rows, which reaches the back wall above the block.  pulled_back has its seeded tiles at half the lens, and the diagonals of
+# rows_across_diagonal cross every row of the whole view.
+WINDOWS = {"default_view": (64, 1024, 8.0), "pulled_back": (512, 128, 4.0), "rows_across_diagonal": (512, 128, 1.0)}
+# Looking up at the back wall above the blocks, left and right of its diagonal: one triangle per tile, nothing between its
+# points and the light.  (yaw, pitch, cam, light)
+UP = ((0.1, 0.2, wm.DEFAULT_CAM, wm.DEFAULT_LIGHT), (-0.1, 0.2, wm.DEFAULT_CAM, wm.DEFAULT_LIGHT))
+# a diffuse sphere on the axis of the default view, 40 pixels across through that lens: its outline crosses the middle tiles
+BALL = (((0.0, 0.0, -1.0), 0.0004, (0.8, 0.3, 0.2, 1.0)),)
+_REF = {}                                    # references: computed once, shared, never changed
+
+
+def _render(kw, knobs, scene, rot, cam, light, focal, flags=0, seeds=False):
+    tr = wm.context(kw, knobs, scene, flags)
+    argb, tap = tr.render(rot, cam, light, focal, want_rgb=True)
+    d = tr.wave_seeds() if seeds else None
+    tr.close()
+    return argb, tap, d
+
+
+def _same(got, want, what):
+    a, f = got[0], got[1]
+    wa = np.asarray(want[0]).reshape(a.shape)
+    bad = np.argwhere(a != wa)
+    assert bad.size == 0, "%s: %d pixels differ, first at %s" % (what, len(bad), bad[0])
+    g = np.asarray(f, np.float32).reshape(a.size, -1)[:, :3]
+    w = np.asarray(want[1], np.float32).reshape(a.size, -1)[:, :3]
+    assert np.array_equal(g.view(np.uint32), w.view(np.uint32)), what + ": float tap differs"
+
+
+def _dims(d, kw, rows, job_pixels=64):
+    r = int(rows)
+    assert (d["tile_rows"], d["tiles_per_row"], d["rows_per_tile"]) == (
+        math.ceil(kw["height"] / r), math.ceil(kw["width"] / job_pixels), r), "the table's shape"
+
+
+def seeded_setup(view, box):
+    """A wave_masks_util view as its window (WINDOWS; 512x128 through the long lens otherwise; + BALL for `default_view_ball`)"""
+    ball = view.endswith("_ball")
+    kw, knobs, s, rot, cam, light, focal = wm.setup((view[:-5] if ball else view, "4x2_64"), box)
+    w, h, lens = WINDOWS.get(view, (512, 128, LENS))
+    focal = focal / kw["width"] * 512 * lens
+    kw = dict(kw, width=w, height=h)
+    if ball:
+        kw["spheres"] = BALL
+    return kw, knobs, s, rot, cam, light, focal
+
+
+SEEDED_VIEWS = ["default_view", "pulled_back", "floor_penumbra", "rows_across_diagonal", "mirror_wall_glass_sphere",
+                "moved_by_3e4", "default_view_ball"]
+
+
+def seed_counters(d):
+    return {k: d[k] for k in ("tile_rows", "tiles_per_row", "rows_per_tile", "tiles_primary", "tiles_shadow", "jobs_primary",
+                              "jobs_shadow")}
+
+
+def check_table(d, prim, scene):
+    """Every record against what the tile shows.  prim: the AOV pass's primitive ids [rows, W, aa] (-1 miss, -2 sphere).
+    -> (tiles that show two primitives or a sphere, primary-only tiles on a surface that is not diffuse)"""
+    rec, r = d["records"], d["rows_per_tile"]
+    mixed = not_diffuse = 0
+    for tr_ in range(d["tile_rows"]):
+        for col in range(d["tiles_per_row"]):
+            q = rec[tr_, col]
+            ids = set(np.unique(prim[tr_ * r:(tr_ + 1) * r, col * 64:(col + 1) * 64]).tolist()) - {-1}
+            fl, where = int(q["flags"]), "tile (%d, %d)" % (tr_, col)
+            assert fl in (0, rt.SEED_PRIMARY, rt.SEED_PRIMARY | rt.SEED_SHADOW), where
+            if len(ids) > 1 or -2 in ids:
+                mixed += 1
+                assert fl == 0, "%s shows %s and has a valid part" % (where, sorted(ids))
+            if fl & rt.SEED_PRIMARY:
+                kp = int(q["Kp"])
+                assert kp != 0 and kp & (kp - 1) == 0, where + ": the primary part names one triangle"
+                assert ids <= {kp.bit_length() - 1}, "%s shows %s, its record names %d" % (where, sorted(ids), kp.bit_length() - 1)
+                if scene.aos[kp.bit_length() - 1, 4, 3] <= 0:
+                    not_diffuse += 1
+                    assert not fl & rt.SEED_SHADOW, where + ": a shadow part on a surface that is not diffuse"
+            if fl & rt.SEED_SHADOW:
+                assert int(q["h"]) == int(q["Kp"]).bit_length() - 1 and int(q["Kh"]) == 0, where
+                assert np.isfinite(q["D0"]).all() and np.isfinite(q["ed"]) and q["ed"] > 0, where
+            else:
+                assert int(q["K"]) == 0 and int(q["Kh"]) == 0 and q["ed"] == 0, where + ": an invalid shadow part holds nothing"
+    return mixed, not_diffuse
+
+
+# ---- 1. the strips ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("view", wm.VIEWS)
+def test_strip_is_bit_identical(view, scene, oracle):
+    kw, knobs, s, rot, cam, light, focal = wm.setup((view, "4x2_64"), scene)
+    refs = {"UOB_RT_NO_SEED=1": _render(kw, dict(knobs, **NO_SEED), s, rot, cam, light, focal, seeds=True),
+            "no cull": _render(kw, knobs, s, rot, cam, light, focal, abi.RT_FLAG_NO_CULL, seeds=True),
+            "generic kernel": _render(kw, knobs, s, rot, cam, light, focal, abi.RT_FLAG_GENERIC_KERNEL, seeds=True)}
+    for what, (_, _, d) in refs.items():
+        assert d["tile_rows"] == 0 and d["records"].size == 0, what + " ran the pre-pass"
+    v, n, c = s.packed()
+    refs["CPU oracle"] = oracle.render(abi.make_config(**kw), v, n, c, rot, cam, light, focal, nthreads=8)
+    for rows in ROWS:
+        got = _render(kw, dict(knobs, UOB_RT_SEED_ROWS=rows), s, rot, cam, light, focal, seeds=True)
+        _dims(got[2], kw, rows)
+        for what, want in refs.items():
+            _same(got, want, "%s, %s rows per tile, against %s" % (view, rows, what))
+
+
+@pytest.mark.parametrize("pair", [p for p in wm.PAIRS if p[1] != "4x2_64"], ids=wm.pair_id)
+def test_other_instantiations_take_no_seed(pair, scene):
+    kw, knobs, s, rot, cam, light, focal = wm.setup(pair, scene)
+    got = _render(kw, dict(knobs, UOB_RT_SEED_ROWS="4"), s, rot, cam, light, focal, seeds=True)
+    assert got[2]["tile_rows"] == 0, "an instantiation other than (4x2, 64) took the seed"
+    _same(got, _render(kw, dict(knobs, **NO_SEED), s, rot, cam, light, focal), wm.pair_id(pair))
+
+
+# ---- 2. the seed is exercised ----------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def golden():
+    with open(os.path.join(ROOT, "tests", "golden", "tile_seed_counters.json")) as f:
+        return json.load(f)
+
+
+def seeded_case(view, rows, box):
+    """-> (seeded frame, no-seed frame, table, AOV primitive ids, scene) of a SEEDED_VIEWS window"""
+    kw, knobs, s, rot, cam, light, focal = seeded_setup(view, box)
+    k = ("noseed", view)
+    if k not in _REF:
+        tr = wm.context(kw, dict(knobs, **NO_SEED), s)
+        a, f = tr.render(rot, cam, light, focal, want_rgb=True)
+        prim = tr.render_aov(rot, cam, focal, sample=None, planes=("prim",))["prim"]
+        tr.close()
+        _REF[k] = (a, f, prim)
+    got = _render(kw, dict(knobs, UOB_RT_SEED_ROWS=rows), s, rot, cam, light, focal, seeds=True)
+    _dims(got[2], kw, rows)
+    return got, _REF[k][:2], got[2], _REF[k][2], s
+
+
+@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("view", SEEDED_VIEWS)
+def test_seeded_window(view, rows, scene, golden, capsys):
+    got, want, d, prim, s = seeded_case(view, rows, scene)
+    _same(got, want, "%s, %s rows per tile, against UOB_RT_NO_SEED=1" % (view, rows))
+    mixed, not_diffuse = check_table(d, prim, s)
+    c = seed_counters(d)
+    with capsys.disabled():
+        print("\n[tile seed] %s R=%s: %s, tiles showing two primitives or a sphere %d, primary-only on a mirror %d" % (
+            view, rows, c, mixed, not_diffuse))
+    assert c["jobs_primary"] >= c["tiles_primary"] and c["jobs_shadow"] >= c["tiles_shadow"]
+    if view in ("default_view", "pulled_back"):
+        assert c["tiles_shadow"] > 0 and c["jobs_shadow"] > 0, "no job started from a shadow record"
+    if view in ("rows_across_diagonal", "default_view_ball"):
+        assert mixed > 0, "no tile of the window shows a diagonal / the sphere's outline"
+    if view == "mirror_wall_glass_sphere":
+        assert not_diffuse > 0, "no tile of the window lies on the mirror wall"
+    if view == "moved_by_3e4":
+        assert c["tiles_shadow"] == 0, "the plane clause fired 3e4 from the origin"
+    assert c == golden["%s-%s" % (view, rows)]
+
+
+def test_seeded_window_against_the_oracle(scene, oracle):
+    """The window with the most seeded jobs, whole frame against the CPU oracle"""
+    kw, knobs, s, rot, cam, light, focal = seeded_setup("default_view", scene)
+    got = _render(kw, dict(knobs, UOB_RT_SEED_ROWS="16"), s, rot, cam, light, focal)
+    v, n, c = s.packed()
+    _same(got, oracle.render(abi.make_config(**kw), v, n, c, rot, cam, light, focal, nthreads=8), "default_view window")
+
+
+# ---- 3. shapes at which indexing can go wrong ------------------------------------------------------------------------
+
+# name -> (config, knobs, rows per tile, job pixels; None: the sampling takes no seed)
+SHAPES = {
+    "width-200": (dict(width=200, height=32), {}, "16", 64),
+    "height-21": (dict(width=128, height=21), {}, "4", 64),
+    "rows-5-of-16": (dict(width=128, height=5), {}, "16", 64),
+    "1x1": (dict(width=1, height=1), {}, "4", 64),
+    "64x1": (dict(width=64, height=1), {}, "4", 64),
+    "65x2": (dict(width=65, height=2), {}, "4", 64),
+    "nseg-1": (dict(width=64, height=9), {}, "4", 64),
+    "nseg-2": (dict(width=128, height=9), {}, "4", 64),
+    "nseg-4": (dict(width=256, height=9), {}, "1", 64),
+    "jobs-of-40": (dict(width=100, height=10), {"UOB_RT_JOB_TASKS": "5"}, "4", None),          # only 64-pixel jobs take the seed
+    "jobs-of-35": (dict(width=100, height=10, aa_x=3, aa_y=3, shadow_samples=5), {"UOB_RT_JOB_TASKS": "5"}, "4", None),
+}
+
+
+def _shape_view(kw):
+    """UP[0] through the long lens of a 512-pixel window, whatever the frame's size: the small frames lie on one triangle of
+    the back wall and their tiles hold something"""
+    yaw, pitch, cam, light = UP[0]
+    return rt.rotation_matrix(yaw, pitch), cam, light, 1100.0 * 512 / 1024.0 * kw["aa_x"] * LENS
+
+
+@pytest.mark.parametrize("name", sorted(SHAPES))
+def test_shapes(name, scene, oracle):
+    extra, knobs, rows, job_pixels = SHAPES[name]
+    kw = dict(dict(aa_x=4, aa_y=2, shadow_samples=64), **extra)
+    knobs = dict(wm.KNOBS, **knobs)
+    rot, cam, light, focal = _shape_view(kw)
+    got = _render(kw, dict(knobs, UOB_RT_SEED_ROWS=rows), scene, rot, cam, light, focal, seeds=True)
+    if job_pixels is None:
+        assert got[2]["tile_rows"] == 0
+    else:
+        _dims(got[2], kw, rows, job_pixels)
+        assert got[2]["jobs_primary"] > 0, "no job of the frame started from a record"
+    _same(got, _render(kw, dict(knobs, **NO_SEED), scene, rot, cam, light, focal), name + " against UOB_RT_NO_SEED=1")
+    v, n, c = scene.packed()
+    _same(got, oracle.render(abi.make_config(**kw), v, n, c, rot, cam, light, focal, nthreads=8), name + " against the CPU oracle")
+
+
+def test_bands_of_one_row(scene, oracle):
+    """Seven ranks of one-row bands on a 33x5 frame (two of them own no row), tiles of 4 rows: every tile holds rows of
+    several ranks, the last tile row is ragged"""
+    kw = dict(width=33, height=5, aa_x=4, aa_y=2, shadow_samples=64)
+    rot, cam, light, focal = _shape_view(kw)
+    v, n, c = scene.packed()
+    o_argb, o_rgb = oracle.render(abi.make_config(**kw), v, n, c, rot, cam, light, focal, nthreads=8)
+    frame = np.full((5, 33), fc.SENTINEL, np.uint32)
+    taps = np.full((5, 33, 4), np.nan, np.float32)
+    jobs = 0
+    for index in range(7):
+        cfg = abi.make_config(band_rows=1, band_index=index, band_count=7, **kw)
+        rows = fc.owned_rows(cfg)
+        tr = wm.context(dict(kw, band_rows=1, band_index=index, band_count=7), dict(wm.KNOBS, UOB_RT_SEED_ROWS="4"), scene)
+        assert tr.rows == len(rows) and bool(rows) != (index >= 5)
+        argb, tap = fc.render_checked(tr, rot, cam, light, focal)
+        d = tr.wave_seeds()
+        tr.close()
+        if rows:
+            assert (d["tile_rows"], d["tiles_per_row"]) == (2, 1) and d["jobs_primary"] <= len(rows)
+            jobs += d["jobs_primary"]
+            frame[rows], taps[rows] = argb, tap
+    assert jobs > 0, "no rank's job started from a record"
+    fc.check_written(frame, taps, o_rgb)
+    fc.same_frame(frame, taps, o_argb, o_rgb, "33x5 in 7 bands")
+
+
+def test_two_children_of_a_parent(scene):
+    """A parent of two children on device 0, bands of 16 rows, tiles of 16 and of 4 rows, against an unseeded single context"""
+    kw = dict(width=256, height=96, aa_x=4, aa_y=2, shadow_samples=64)
+    rot, cam, light, focal = _shape_view(kw)
+    want = _render(kw, dict(wm.KNOBS, **NO_SEED), scene, rot, cam, light, focal)
+    for rows in ("16", "4"):
+        tr = wm.context(dict(kw, devices=(0, 0), device_band_rows=16), dict(wm.KNOBS, UOB_RT_SEED_ROWS=rows), scene)
+        for _ in range(2):
+            argb, tap = fc.render_checked(tr, rot, cam, light, focal)
+            fc.same_frame(argb, tap, want[0], want[1], "two children, %s rows per tile" % rows)
+        d = tr.wave_seeds()                  # devices[0]'s table: its bands are half of the rows
+        tr.close()
+        _dims(d, kw, rows)
+        assert 0 < d["jobs_primary"] <= 48 * 4
+
+
+# ---- 4. state across the frames of one context -----------------------------------------------------------------------
+
+SEQ = dict(width=256, height=96, aa_x=4, aa_y=2, shadow_samples=64)
+
+
+def _seq_focal():
+    return 1100.0 * 512 / 1024.0 * 4 * LENS
+
+
+def _fresh(scene, key, view, spheres=None):
+    """The frame of a fresh unseeded context: (argb, tap)"""
+    k = ("fresh", key, tuple(map(repr, view)), repr(spheres))
+    if k not in _REF:
+        yaw, pitch, cam, light = view
+        kw = dict(SEQ) if spheres is None else dict(SEQ, spheres=spheres)
+        _REF[k] = _render(kw, dict(wm.KNOBS, **NO_SEED), scene, rt.rotation_matrix(yaw, pitch), cam, light, _seq_focal())[:2]
+    return _REF[k]
+
+
+# views through the long lens: the back wall above the blocks on either side of its diagonal, the floor
+VIEWS3 = (UP[0], UP[1], (0.0, wm.FLOOR_PITCH, wm.DEFAULT_CAM, wm.DEFAULT_LIGHT))
+
+
+def _frame_of(tr, view):
+    yaw, pitch, cam, light = view
+    return fc.render_checked(tr, rt.rotation_matrix(yaw, pitch), cam, light, _seq_focal())
+
+
+@pytest.mark.parametrize("rows", ("4", "16"))
+def test_views_and_light_change_between_frames(rows, scene):
+    tr = wm.context(SEQ, dict(wm.KNOBS, UOB_RT_SEED_ROWS=rows), scene)
+    seeded = []
+    for k, vi in enumerate(fc.SEQ_ORDER):
+        argb, tap = _frame_of(tr, VIEWS3[vi])
+        fc.same_frame(argb, tap, *_fresh(scene, "box", VIEWS3[vi]), "frame %d (view %d)" % (k, vi))
+        seeded.append(tr.wave_seeds()["jobs_shadow"])
+    for k, lx in enumerate((0.0, 0.3, -0.4, 0.0)):                    # the light moves, the view stands
+        view = (UP[0][0], UP[0][1], wm.DEFAULT_CAM, [lx, -0.5, -0.7])
+        argb, tap = _frame_of(tr, view)
+        fc.same_frame(argb, tap, *_fresh(scene, "box", view), "light at x = %g" % lx)
+    tr.close()
+    assert any(seeded), "no frame of the sequence started a job from a shadow record: %s" % seeded
+
+
+def test_scene_edits_between_frames(scene, tmp_path):
+    mirror = scene.with_color(wm.BACK_WALL, wm.MIRROR)
+    mesh = fc.mesh_scene(tmp_path)
+    blocks = [(10, 8)]                                                # the short block
+    xf = np.asarray([[[1, 0, 0, 0.05], [0, 1, 0, -0.2], [0, 0, 1, 0.1]]], np.float32)     # the first block, lifted and shifted
+    posed = scene.posed(blocks, xf)
+    view = VIEWS3[0]
+    r = rt.rotation_matrix(view[0], view[1])
+    # a diffuse sphere two units down the view's middle ray (the third column of the rotation), 40 pixels across
+    ball = ((tuple(float(np.float32(view[2][k]) + np.float32(2.0) * r[4 * k + 2]) for k in range(3)), 0.0004, (0.8, 0.3, 0.2, 1.0)),)
+    tr = wm.context(SEQ, dict(wm.KNOBS, UOB_RT_SEED_ROWS="4"), scene)
+
+    def check(s, key, what, spheres=None, shadow=None):
+        argb, tap = _frame_of(tr, view)
+        fc.same_frame(argb, tap, *_fresh(s, key, view, spheres), what)
+        d = tr.wave_seeds()
+        if shadow is not None:
+            assert (d["jobs_shadow"] > 0) == shadow, "%s: %d jobs started from a shadow record" % (what, d["jobs_shadow"])
+        return d
+
+    before = check(scene, "box", "first frame", shadow=True)
+    tr.update_scene(mirror)
+    check(mirror, "mirror", "after rt_update_scene: the wall is a mirror", shadow=False)
+    tr.replace_scene(scene)
+    assert seed_counters(check(scene, "box", "after rt_replace_scene, same count", shadow=True)) == seed_counters(before)
+    tr.replace_scene(mesh)
+    assert check(mesh, "mesh70", "after rt_replace_scene to 70 triangles")["tile_rows"] == 0
+    tr.replace_scene(scene)
+    assert seed_counters(check(scene, "box", "back to 30 triangles", shadow=True)) == seed_counters(before)
+    tr.update_spheres(ball)                                           # a sphere moves into tiles that were seeded
+    d = check(scene, "box", "after rt_update_spheres", spheres=ball)
+    assert d["tiles_primary"] < before["tiles_primary"]
+    tr.update_spheres(abi.REFERENCE_SPHERES)
+    assert seed_counters(check(scene, "box", "the spheres back", shadow=True)) == seed_counters(before)
+    tr.set_objects(blocks)
+    tr.pose_objects(xf)
+    check(posed, "posed", "after rt_pose_objects")
+    tr.close()
+
+
+def test_two_contexts_on_two_streams_and_one_on_alternating_streams(scene):
+    import torch
+    dev = torch.device("cuda")
+    s = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    trs = [wm.context(SEQ, dict(wm.KNOBS, UOB_RT_SEED_ROWS=r), scene) for r in ("4", "16")]
+    order = [0, 1, 2, 0, 2, 1]
+    rows, w = trs[0].rows, trs[0].width
+
+    def poisoned():
+        return (torch.full((rows * w,), fc.SENTINEL, dtype=torch.int32, device=dev),
+                torch.full((rows * w, 4), float("nan"), dtype=torch.float32, device=dev))
+
+    # two contexts, each on its own stream, frames interleaved, nothing waited for in between
+    out = []
+    torch.cuda.synchronize(dev)
+    for k, vi in enumerate(order):
+        for c in (0, 1):
+            yaw, pitch, cam, light = VIEWS3[(vi + c) % 3]
+            a, t = poisoned()
+            trs[c].render_device(rt.rotation_matrix(yaw, pitch), cam, light, _seq_focal(), a.data_ptr(), t.data_ptr(), stream=s[c].cuda_stream)
+            out.append(((vi + c) % 3, a, t, "context %d, frame %d" % (c, k)))
+    # one context, its frames on alternating streams
+    for k, vi in enumerate(order):
+        yaw, pitch, cam, light = VIEWS3[vi]
+        a, t = poisoned()
+        trs[0].render_device(rt.rotation_matrix(yaw, pitch), cam, light, _seq_focal(), a.data_ptr(), t.data_ptr(), stream=s[k & 1].cuda_stream)
+        out.append((vi, a, t, "alternating streams, frame %d" % k))
+    torch.cuda.synchronize(dev)
+    for vi, a, t, what in out:
+        argb, tap = a.reshape(rows, w).cpu().numpy().view(np.uint32), t.reshape(rows, w, 4).cpu().numpy()
+        fc.check_written(argb, tap)
+        fc.same_frame(argb, tap, *_fresh(scene, "box", VIEWS3[vi]), what)
+    for tr in trs:
+        tr.close()
+
+
+# ---- 5. degenerate inputs ---------------------------------------------------------------------------------------------
+
+def _floor_y(scene):
+    return float(scene.aos[wm.FLOOR, :3, 1].flat[0])
+
+
+DEGENERATE = ["camera_in_a_block", "floor_edge_on", "light_in_the_wall's_plane", "light_in_the_floor's_plane"]
+
+
+@pytest.mark.parametrize("case", DEGENERATE)
+def test_degenerate_views(case, scene):
+    kw = dict(SEQ)
+    cam, light, yaw, pitch = list(wm.DEFAULT_CAM), list(wm.DEFAULT_LIGHT), UP[0][0], UP[0][1]
+    if case == "camera_in_a_block":
+        v = scene.aos[10:18, :3, :3].reshape(-1, 3)                                 # the short block: the middle of its box
+        cam = (0.5 * (v.min(axis=0) + v.max(axis=0))).tolist()
+    elif case == "floor_edge_on":                                                   # the camera in the floor's plane: every tile
+        cam, yaw, pitch = [0.0, _floor_y(scene), -3.2], 0.0, 0.0                    # of the middle rows sees the floor edge-on
+    elif case == "light_in_the_wall's_plane":
+        light = [0.1, -0.2, float(scene.aos[wm.BACK_WALL[0], 0, 2])]
+        assert (scene.aos[wm.BACK_WALL, :3, 2] == light[2]).all()
+    else:
+        light, pitch = [0.1, _floor_y(scene), -0.2], wm.FLOOR_PITCH
+    rot = rt.rotation_matrix(yaw, pitch)
+    want = _render(kw, dict(wm.KNOBS, **NO_SEED), scene, rot, cam, light, _seq_focal())
+    for rows in ("4", "16"):
+        got = _render(kw, dict(wm.KNOBS, UOB_RT_SEED_ROWS=rows), scene, rot, cam, light, _seq_focal(), seeds=True)
+        _same(got, want, "%s, %s rows per tile" % (case, rows))
+        rec = got[2]["records"]
+        valid = (rec["flags"] & rt.SEED_SHADOW) != 0
+        assert np.isfinite(rec["D0"]).all() and np.isfinite(rec["ed"]).all(), "a non-finite value reached the table"
+        assert (rec["ed"][valid] > 0).all() and (rec["ed"][~valid] == 0).all()
+        if case.startswith("light_in_the"):
+            h = rec["h"][valid]
+            on = wm.BACK_WALL if "wall" in case else wm.FLOOR
+            assert not np.isin(h, on).any(), "a shadow part on the surface the light lies in (term == 0 there)"
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")])
+def test_a_light_that_is_not_finite_never_reaches_the_pre_pass(bad, scene):
+    """rt_render refuses it before anything is enqueued, seeded or not"""
+    tr = wm.context(SEQ, dict(wm.KNOBS, UOB_RT_SEED_ROWS="4"), scene)
+    with pytest.raises(rt.RtError) as e:
+        tr.render(rt.rotation_matrix(0.0, 0.0), wm.DEFAULT_CAM, [0.0, bad, -0.7], _seq_focal())
+    assert e.value.code == abi.RT_E_INVALID
+    yaw, pitch, cam, light = VIEWS3[0]
+    got = tr.render(rt.rotation_matrix(yaw, pitch), cam, light, _seq_focal(), want_rgb=True)
+    tr.close()
+    _same(got, _fresh(scene, "box", VIEWS3[0]), "the frame after the refused one")
+
+
+# ---- 6. nothing is left behind ----------------------------------------------------------------------------------------
+
+def test_the_table_goes_with_the_context(scene):
+    """A context's first seeded frame allocates the table — 24 x 4 records of 64 bytes here — on top of what an unseeded
+    context's first frame allocates; later frames allocate nothing; rt_destroy leaves nothing"""
+    import gc
+    gc.collect()
+    base = rt.live_device_objects()
+    keys = list(base)                        # allocations, bytes, events, streams
+    grew = {}
+    for name, knobs in (("unseeded", NO_SEED), ("seeded", {"UOB_RT_SEED_ROWS": "4"})):
+        tr = wm.context(SEQ, dict(wm.KNOBS, **knobs), scene)
+        held = rt.live_device_objects()
+        _frame_of(tr, VIEWS3[0])
+        first = rt.live_device_objects()
+        _frame_of(tr, VIEWS3[1])
+        assert rt.live_device_objects() == first, name + ": a later frame allocated again"
+        grew[name] = [first[k] - held[k] for k in keys]
+        tr.close()
+        assert rt.live_device_objects() == base, name + ": rt_destroy left something"
+    assert [a - b for a, b in zip(grew["seeded"], grew["unseeded"])] == [1, 24 * 4 * 64, 0, 0]

@@ -92,6 +92,8 @@ static Tuning read_tuning(const rt_config& cfg) {
   t.timeline = getenv("UOB_RT_TIMELINE") != nullptr;
   if (const char* e = getenv("UOB_RT_MASK_DEBUG")) t.mask_debug = atoi(e);
   if (const char* e = getenv("UOB_RT_TILE_ORDER")) t.tile_morton = !strcmp(e, "morton");
+  if (const char* e = getenv("UOB_RT_NO_SEED")) t.no_seed = atoi(e) != 0;
+  if (const char* e = getenv("UOB_RT_SEED_ROWS")) { const int v = atoi(e); if (v >= 1 && v <= 64) t.seed_rows = v; }
   if (const char* e = getenv("UOB_RT_FILTER_FORM")) t.filter_form = !strcmp(e, "direct") ? kFilterFormDirect : kFilterFormBuiltIn;
   return t;
 }
@@ -380,6 +382,7 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
   HIP_TRY(wait_scene(c, stream));          // before ev0: rt_last_kernel_ms times the frame's kernels only
   HIP_TRY(hipEventRecord(c->ev0, stream));
   const bool wave_paths = !(c->cfg.flags & RT_FLAG_GENERIC_KERNEL);
+  c->seed_tile_rows = 0;                      // (set again below by a frame that takes the seed)
   if (wave_paths && wave_kernel_supports(P) && (P.aa_x * P.aa_y <= 64 || !(c->cfg.flags & RT_FLAG_NO_CULL))) {
     // last frame's expensive jobs first — where jobs are long enough (4+ tasks) for the extra look-up per
     // hand-out not to matter (measured: 1024^2 frames with 16-pixel jobs lose 12-18 % to it, larger ones gain 2-8 %)
@@ -407,6 +410,23 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
         P.counters = reinterpret_cast<unsigned long long*>(c->d_timeline.p);
         c->timeline_valid = true;
       }
+    }
+    // The tile seeds (rt_kernel_wave.hip rt_wave_seed): written from THIS frame's parameters in front of the draw kernel on
+    // the caller's stream, every frame — view, light, scene and spheres may all have changed since the last one.  The table
+    // is one more of the buffers a context's frames share: "one frame of a context at a time" above orders its writers and
+    // readers as it orders those of the queue heads and the expensive-job lists.
+    if (!c->tune.no_seed && wave_takes_seed(P, !(c->cfg.flags & RT_FLAG_NO_CULL))) {
+      const int R = c->tune.seed_rows;
+      const int tile_rows = (P.H + R - 1) / R;
+      const size_t tiles = (size_t)tile_rows * (size_t)P.nseg;
+      if (c->seed_cap < tiles) {
+        if (c->d_seed.alloc(tiles) != hipSuccess) return alloc_failed();
+        c->seed_cap = tiles;
+      }
+      P.seed = c->d_seed; P.seed_rows = R; P.seed_tile_rows = tile_rows; P.seed_rows_magic = div_magic_for(R);
+      P.seed_hy = 0.5f * (float)(R * P.aa_y - 1) * P.sy;
+      for (int k = 0; k < 3; ++k) P.seed_eu[k] = 1.0001f * (fabsf(rot[4 * k]) * P.job_hx + fabsf(rot[4 * k + 1]) * P.seed_hy);
+      c->seed_tile_rows = tile_rows; c->seed_nseg = P.nseg; c->seed_rows = R;
     }
     launch_wave(P, !(c->cfg.flags & RT_FLAG_NO_CULL), false, stream);
   } else if (wave_paths && !(c->cfg.flags & RT_FLAG_NO_CULL) && mesh_kernel_supports(P)) {
@@ -746,6 +766,34 @@ int rt_debug_wave_timeline(rt_ctx* c, uint64_t out[8]) {
     if (t1 > out[2]) out[2] = t1;
     if (jobs > out[6]) out[6] = jobs;
   }
+  return RT_OK;
+}
+
+int rt_debug_wave_seeds(rt_ctx* c, void* records, int64_t cap, int32_t dims[3], uint64_t counters[4]) {
+  if (!c || !dims || !counters || cap < 0 || (cap > 0 && !records)) { set_error("NULL argument"); return RT_E_INVALID; }
+  c = lead_ctx(c);
+  dims[0] = c->seed_tile_rows; dims[1] = c->seed_nseg; dims[2] = c->seed_rows;
+  for (int q = 0; q < 4; ++q) counters[q] = 0;
+  if (c->seed_tile_rows == 0) { dims[1] = 0; return RT_OK; }      // the last frame took no seed: an empty table
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->timed) HIP_TRY(hipEventSynchronize(c->ev1));
+  const size_t tiles = (size_t)c->seed_tile_rows * (size_t)c->seed_nseg;
+  std::vector<SeedRec> rec(tiles);
+  HIP_TRY(hipMemcpy(rec.data(), c->d_seed, tiles * sizeof(SeedRec), hipMemcpyDeviceToHost));
+  const rt_config& g = c->cfg;
+  for (int tr = 0; tr < c->seed_tile_rows; ++tr) {
+    // the rows of this tile the context renders: each of them is one job per column, and every job reads its tile's record
+    uint64_t rows = 0;
+    for (int y = tr * c->seed_rows; y < (tr + 1) * c->seed_rows && y < g.height; ++y)
+      rows += ((y / g.band_rows) % g.band_count) == g.band_index;
+    for (int col = 0; col < c->seed_nseg; ++col) {
+      const uint32_t f = rec[(size_t)tr * c->seed_nseg + col].flags;
+      if (f & kSeedPrimary) { counters[0] += 1; counters[2] += rows; }
+      if (f & kSeedShadow) { counters[1] += 1; counters[3] += rows; }
+    }
+  }
+  if (records) memcpy(records, rec.data(), (size_t)((int64_t)tiles < cap ? (int64_t)tiles : cap) * sizeof(SeedRec));
   return RT_OK;
 }
 

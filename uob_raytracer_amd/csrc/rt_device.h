@@ -27,6 +27,22 @@ struct DevSphere {
   float col[4];
 };
 
+// One record per screen tile (seed_rows rows of one job column), DESIGN.md 4.1 "tile seeds".  Both parts are statements
+// about SETS of rays, used by a job only through tests the draw kernel already makes:
+//   primary (kSeedPrimary): no primary ray through the tile's sub-pixel rectangle can hit a triangle outside Kp, nor a sphere
+//   shadow  (kSeedShadow) : the outcome of level 1 over every shadow ray whose direction lies within ed of D0 — the casters K,
+//                           K without those whose plane holds triangle h (Kh), no sphere candidate, not blocked
+// A record without a flag says nothing: the job does what it did before there were seeds.
+struct alignas(16) SeedRec {
+  float D0[3], ed;
+  unsigned long long K, Kh, Kp;
+  int32_t h;
+  uint32_t flags;
+  uint32_t pad[4];
+};
+constexpr uint32_t kSeedPrimary = 1u, kSeedShadow = 2u;
+static_assert(sizeof(SeedRec) == 64, "one record per 64-byte line");
+
 // Everything one frame needs, passed by value as the kernel argument (lives in SGPRs / the scalar cache).
 struct FrameParams {
   float rot[12];          // 3 rows x (x,y,z,pad), skeleton.cpp:149-151
@@ -108,7 +124,17 @@ struct FrameParams {
                                       // 64 = bounce rays visit every tile (no tile pre-test), 256 = shadow-ray masks without the tile-level certificate
   int32_t nwords, scx, scy, grid_g;   // 64-bit words per mask; screen cells per row / column; world cells per axis
   float grid_lo[3], grid_cell, grid_inv;   // world grid: origin, cell edge, 1 / cell edge
+  // wave kernel: the tile seeds of this frame (rt_wave_seed writes them, the instantiations that take the seed read them at
+  // job start); nullptr = no pre-pass ran, every job starts as it always did.  (Behind every older field: their kernarg
+  // offsets are what the listings of the kernels that know nothing of this hold.)
+  SeedRec* seed;
+  int32_t seed_rows;                  // rows of a tile (its width is a job's)
+  int32_t seed_tile_rows;             // tile rows of the frame: ceil(H / seed_rows)
+  uint32_t seed_rows_magic;           // div_magic of seed_rows
+  float seed_hy;                      // half height of a tile's sub-pixel rectangle (job_hy of seed_rows rows)
+  float seed_eu[3];                   // job_eu with seed_hy in place of job_hy
 };
+
 
 // The planes of an AOV pass (rt_aov.hip; include/uob_rt.h rt_aov_buffers) in device memory, nullptr = not asked for
 struct AovPlanes {

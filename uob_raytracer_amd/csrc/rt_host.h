@@ -44,6 +44,7 @@ void launch_trace_rays(const FrameParams& P, int what, const float* d_rays, cons
 void launch_wave(const FrameParams& P, bool cull, bool count, hipStream_t stream);
 void launch_wave_prof(const FrameParams& P, hipStream_t stream);
 bool wave_kernel_supports(const FrameParams& P);
+bool wave_takes_seed(const FrameParams& P, bool cull);
 int wave_blocks_per_cu(bool leave_room);
 // rt_kernel_mesh.hip
 void launch_mesh(const FrameParams& P, bool count, bool prof, hipStream_t stream, hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join);
@@ -139,6 +140,8 @@ struct Tuning {
   int mask_debug = 0;         // UOB_RT_MASK_DEBUG: mesh kernel, switch single tile-mask stages off (fault isolation)
   bool tile_morton = false;   // UOB_RT_TILE_ORDER=morton: the mesh kernel's tiles in plain Morton order (tiled_order)
   int filter_form = 0;        // UOB_RT_FILTER_FORM=direct: every filter pass takes its taps from the caches (tools/filter_time.py)
+  bool no_seed = false;       // UOB_RT_NO_SEED=1: no tile-seed pre-pass, every job of the wave kernel starts unseeded
+  int seed_rows = 16;         // UOB_RT_SEED_ROWS: rows of a seed tile (1 .. 64); the default is the default band height
 };
 
 // ---- owners of device objects: move-only, and no device is stored — whoever frees on a given device sets
@@ -239,6 +242,11 @@ struct rt_ctx {
   uobrt::DevMem<float4> d_rgb;     // lazily allocated float tap
   uobrt::DevMem<unsigned long long> d_counters;
   uobrt::DevMem<unsigned int> d_jobctr; // wave kernel's job queue heads
+  // wave kernel: the tile seeds (rt_kernel_wave.hip rt_wave_seed), rewritten in front of every frame whose instantiation
+  // takes them; sized by the frame's tiles on first use.  seed_* describe the table the last frame left (0 tiles: none)
+  uobrt::DevMem<uobrt::SeedRec> d_seed;
+  size_t seed_cap = 0;
+  int seed_tile_rows = 0, seed_nseg = 0, seed_rows = 0;
   int cus = 256;                    // compute units of the device
   // wave kernel: last frame's expensive jobs go first (rt_device.h FrameParams::heavy_*); two lists, used in turn
   unsigned int *d_heavy[2] = {nullptr, nullptr}, *d_heavy_flags = nullptr;

@@ -153,8 +153,7 @@ __device__ __forceinline__ int wave_unshadowed_all(const FrameParams& P, const T
 // dependent chain  LDS record -> determinants -> reciprocal -> compares  two independent instances to
 // interleave: with one point per pass this level ran at ~20 % VALU utilisation, bound by latency (7.8 ms
 // of the headline frame; 5.5 ms with two; four or eight points cost more in registers than they gain).
-// SC = the shadow-casting triangles' records (v0,e1,e2,c) in K's bit order.  Returns both counts.
-struct ShadowCasters { const float4 *v0, *e1, *e2, *c; };
+// SC = the shadow-casting triangles' records (v0,e1,e2,c) in K's bit order (rt_wave_common.h).  Returns both counts.
 struct Count2 { int a, b; };
 template <bool COUNT>
 __device__ __forceinline__ Count2 wave_unshadowed_pair(const FrameParams& P, const ShadowCasters& SC, const WaveLds& L,
@@ -522,7 +521,28 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
   // narrower and a triangle or so fewer survives, but the bound itself costs more than that triangle's tests.)
   unsigned long long Kp_job = n == 64 ? ~0ull : ((1ull << n) - 1ull);
   bool sph_job = P.nsph > 0;
-  if (CULL) {
+  // SEED: the job starts from its screen tile's record (rt_wave_seed below, DESIGN.md 4.1 "tile seeds") where that holds
+  // something: a primary part stands for the job's own bound — the tile's rectangle contains the job's — and a shadow part is
+  // a level 1 in the state the previous task of a job leaves behind, which every task puts to the reuse test as it does any
+  // other: nothing downstream knows where jk_* came from.  One wave-uniform load per job through the scalar cache (the table
+  // is written by the launch in front of this one and read-only here).  The (4x2, 64) instantiation alone, like MASKS a
+  // compile-time condition: the others hold the code they held.
+  constexpr bool SEED = CULL && !COUNT && !PROF && MASKS && STRIDE == 32 && AA_X == 4 && AA_Y == 2 && SS == 64 && !MULTI && !BIGAA;
+  bool seeded = false;
+  if (SEED && PC(seed) != nullptr) {
+    const int trow = (int)div_magic((uint32_t)y, PC(seed_rows_magic));
+    const int ti = __builtin_amdgcn_readfirstlane(trow * PC(nseg) + (job - jrow * PC(nseg)));
+    typedef const __attribute__((address_space(4))) SeedRec* SeedPtr;
+    const SeedPtr rec = (SeedPtr)(unsigned long long)(PC(seed) + ti);
+    const uint32_t sf = rec->flags;
+    if ((sf & kSeedPrimary) != 0u) { Kp_job = rec->Kp; sph_job = false; seeded = true; }
+    if ((sf & kSeedShadow) != 0u) {
+      jk_D0 = mk(rec->D0[0], rec->D0[1], rec->D0[2]); jk_ed = rec->ed;
+      jk_K = rec->K; jk_Kh = (kh_t)rec->Kh; jk_h = rec->h;
+      jk_flags = kJkValid;
+    }
+  }
+  if (CULL && !(SEED && seeded)) {
     const int lnJ = opaque(lane);
     const float Xlo = (float)(x0 * aa_x) - P.half_wx;
     const float Ylo = ((float)(y * aa_y) - P.half_hy) * sy;
@@ -924,6 +944,130 @@ template __global__ void rt_draw_wave<true, false, false, 32, false, 2, 2, 10>(c
 template __global__ void rt_draw_wave<false, false, false, 0, true>(const FrameParams);
 template __global__ void rt_draw_wave<true, false, false, 0, false, 0, 0, 0, true>(const FrameParams);   // 65..256 AA samples per pixel
 
+// ---- the tile seeds ------------------------------------------------------------------------------------------------
+// One wave per screen tile (P.seed_rows rows of one job column), lane = triangle / caster throughout, in a loop over the
+// tiles by a grid the device holds at once; the scene is staged as the draw kernel stages it.  Per tile one SeedRec:
+//   primary part  the job's own bound (primary_clear, sphere_bundle_maybe) over the tile's sub-pixel rectangle, which
+//                 contains the rectangle of every job of the tile: kept when it leaves ONE triangle h and no sphere;
+//   shadow part   only then, and only for a diffuse h: level 1 (level1_bundle: the draw kernel's fresh level 1) around the
+//                 surface point X0 the tile's centre ray hits, over every direction within ed of D0 = light - X0, ed from the
+//                 four corner rays' hits on h's plane.  ed decides how many tasks pass the draw kernel's reuse test, never
+//                 whether the bound is right: it only has to be finite.  Kept when the outcome is "nothing to do": no caster
+//                 left off h's plane, no sphere candidate, not blocked.
+// Everything else — a non-finite value anywhere, a tile with no row of this rank, a centre ray that misses h or faces away
+// from the light — leaves the part invalid, which is always a correct answer.
+__global__ __launch_bounds__(64 * kWavesPerBlock) void rt_wave_seed(const FrameParams P) {
+  extern __shared__ float4 lds_dyn[];
+  float4* const lds = lds_dyn;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int n = P.n, ns = P.n_shadow;
+  stage_triangles(P, lds, tid, 64 * kWavesPerBlock, n);
+  stage_spheres(P, tid);
+  int* sidx = reinterpret_cast<int*>(lds + kLdsRecords * n);
+  if (wave == 0) {
+    const bool casts = (lane < n) && (P.colors[lane < n ? lane : 0].w != -1.0f);   // glass casts no shadow, :247
+    const unsigned long long m = ballot(casts);
+    if (casts) sidx[__popcll(m & ((1ull << lane) - 1ull))] = lane;
+  }
+  __syncthreads();
+  float4* scbase = reinterpret_cast<float4*>(sidx + ((n + 3) & ~3));
+  for (int kq = tid; kq < ns; kq += 64 * kWavesPerBlock) {
+    const int ti = sidx[kq];
+    scbase[kq] = lds[ti]; scbase[ns + kq] = lds[n + ti]; scbase[2 * ns + kq] = lds[2 * n + ti];
+    const float4 c4 = lds[3 * n + ti];
+    scbase[3 * ns + kq] = make_float4(c4.x, c4.y, c4.z, norm1(xyz(c4)));
+  }
+  __syncthreads();
+  const ShadowCasters SC{scbase, scbase + ns, scbase + 2 * ns, scbase + 3 * ns};
+  const LdsScene S = lds_scene(lds, n, n);
+  const f3 light = mk(P.light[0], P.light[1], P.light[2]);
+  const unsigned long long tri_lanes = ns == 64 ? ~0ull : ((1ull << ns) - 1ull);
+  const int aa = P.aa_x * P.aa_y;
+  const int JP = P.job_tasks * (64 / aa);                      // pixels of a job (aa <= 64: the callers check)
+  const int R = P.seed_rows, nseg = P.nseg;
+  const int tiles = P.seed_tile_rows * nseg;
+  for (int t = (int)blockIdx.x * kWavesPerBlock + wave; t < tiles; t += (int)gridDim.x * kWavesPerBlock) {
+    const int trow = t / nseg, col = t - trow * nseg;
+    const int x0 = col * JP, y0 = trow * R;
+    SeedRec rec;
+    rec.D0[0] = rec.D0[1] = rec.D0[2] = 0.0f; rec.ed = 0.0f;
+    rec.K = 0ull; rec.Kh = 0ull; rec.Kp = 0ull; rec.h = -1; rec.flags = 0u;
+    rec.pad[0] = rec.pad[1] = rec.pad[2] = rec.pad[3] = 0u;
+    // a row of this rank in the tile?  lane r answers for row y0 + r (R <= 64)
+    bool mine = false;
+    {
+      const int yr = y0 + lane;
+      const int q = yr / P.band_rows;
+      const int lr = (q / P.band_count) * P.band_rows + (yr - q * P.band_rows);
+      mine = lane < R && yr < P.H && q % P.band_count == P.band_index && lr < P.owned_rows;
+    }
+    if (ballot(mine) != 0ull) {
+      // ---- primary part: the job's bound (rt_draw_wave, job set-up) with the tile's half height in place of job_hy
+      const float Xlo = (float)(x0 * P.aa_x) - P.half_wx;
+      const float Ylo = ((float)(y0 * P.aa_y) - P.half_hy) * P.sy;
+      const f3 wc = mk(Xlo + P.job_hx, Ylo + P.seed_hy, P.focal);
+      const f3 duc = mk(P.rot[0] * wc.x + P.rot[1] * wc.y + P.rzf[0], P.rot[4] * wc.x + P.rot[5] * wc.y + P.rzf[1],
+                        P.rot[8] * wc.x + P.rot[9] * wc.y + P.rzf[2]);
+      const f3 eu = mk(P.seed_eu[0], P.seed_eu[1], P.seed_eu[2]);
+      const float dumax = fmaxf(fmaxf(fabsf(duc.x) + eu.x, fabsf(duc.y) + eu.y), fabsf(duc.z) + eu.z);
+      const int ti = lane < n ? lane : 0;
+      const float4 c4 = S.c[ti];
+      const bool clear = primary_clear(duc, eu, dumax, xyz(c4), c4.w, xyz(S.pc[ti]), xyz(S.qc[ti]));
+      const unsigned long long Kp = (n == 64 ? ~0ull : ((1ull << n) - 1ull)) & ~ballot(clear);
+      bool sph = P.nsph > 0;
+      if (P.nsph > 0 && dumax < 1e30f)
+        sph = ballot(sphere_bundle_maybe(P, lane, mk(P.cam[0], P.cam[1], P.cam[2]), 0.0f, duc, bsqrt(dot3(duc, duc)),
+                                         1.0001f * bsqrt(dot3(eu, eu)), false)) != 0ull;
+      if (dumax < 1e30f && __popcll(Kp) == 1 && !sph) {
+        rec.Kp = Kp; rec.flags = kSeedPrimary;
+        const int h = __builtin_ctzll(Kp);
+        // ---- shadow part.  Lanes 0..3 send the tile's corner rays, the others its centre ray: all of them rays of the
+        // bundle bounded above, so h is the one triangle any of them can hit.
+        const int cx = lane < 4 ? ((lane & 1) ? x0 + JP - 1 : x0) : x0 + (JP >> 1);
+        const int cy = lane < 4 ? ((lane & 2) ? y0 + R - 1 : y0) : y0 + (R >> 1);
+        const int cdx = (lane < 4 && (lane & 1)) ? P.aa_x - 1 : 0, cdy = (lane < 4 && (lane & 2)) ? P.aa_y - 1 : 0;
+        Ray ray = primary_ray(P, cx, cy, cdx, cdy, P.aa_x, P.aa_y, P.sy);
+        const f3 rd = ray.dir;
+        closest_hit_primary_masked(S, P, ray, Kp, false);            // the centre ray's hit, by the arithmetic of the primary hit
+        const LightSetup ls = light_setup(light, ray);
+        const bool slit = ray.tri == h && ray.col.w > 0.0f && !(ls.term == 0.0f);
+        const CullConsts cc = cull_consts(ls.radius_sq, P.hbox, slit);
+        const int jr = 4;                                            // a centre lane
+        const f3 s0 = mk(rl(ls.start.x, jr), rl(ls.start.y, jr), rl(ls.start.z, jr));
+        const f3 D0 = mk(rl(ls.dir.x, jr), rl(ls.dir.y, jr), rl(ls.dir.z, jr));
+        const float dlen0 = rl(cc.dlen, jr);
+        const bool sane0 = ((ballot(cc.sane) >> jr) & 1ull) != 0ull;
+        // the corner rays on h's plane: det(X - v0, e1, e2) = 0 at t = det(A0) / det(A), the primary test's own t
+        const float4 hc = S.c[h];
+        const float tc = hc.w / detc(-rd, xyz(hc));
+        const f3 Xc = mk(P.cam[0], P.cam[1], P.cam[2]) + tc * rd;
+        const float dev = norm_inf((light - Xc) - D0);
+        const bool corner_ok = tc > 0.0f && dev < 1e30f;             // false for a NaN; a plane behind a corner has no bounded image
+        const bool corners = (ballot(!corner_ok) & 0xfull) == 0ull;
+        const float ed = 1.05f * wave_max_pos(lane < 4 && corner_ok ? dev : 0.0f) + 1e-5f * (P.light_inf + dlen0);
+        if (sane0 && corners && ed < 1e30f) {
+          const Level1 l1 = level1_bundle(P, S, SC, lane, ns, tri_lanes, light, P.hbox, s0, D0, ed, dlen0, h);
+          if (l1.ok && l1.Kh == 0ull && !l1.sph && !l1.blocked) {
+            rec.D0[0] = D0.x; rec.D0[1] = D0.y; rec.D0[2] = D0.z;
+            rec.ed = uniform(ed * 0.9999f);       // what the tasks compare with (the bound itself allows 1.001 ed and more)
+            rec.K = l1.K; rec.Kh = l1.Kh; rec.h = h; rec.flags = kSeedPrimary | kSeedShadow;
+          }
+        }
+      }
+    }
+    if (lane == 0) P.seed[t] = rec;
+  }
+}
+
+// Does the frame take the seed?  launch_wave's own choice of instantiation (rt_draw_wave, SEED), asked by the host before it
+// sizes the table — and jobs of eight tasks, 64 pixels: the shorter jobs of frames with few rows (32 pixels from 1024 rows per
+// rank down) have half as many level 1s to save per tile and twice the tiles, and one rank's 512 rows of an 8-rank split ran
+// 3 % SLOWER with the pre-pass in front (0.447 -> 0.463 ms, profiles/tile_seed_ab.txt).  They start every job unseeded.
+bool wave_takes_seed(const FrameParams& P, bool cull) {
+  return cull && P.n <= 32 && !P.no_specialise && P.aa_x == 4 && P.aa_y == 2 && P.S == 64 && P.job_tasks == 8;
+}
+
 bool wave_kernel_supports(const FrameParams& P) {
   const int aa = P.aa_x * P.aa_y;
   // (more than 64 AA samples per pixel: the chunked instantiation exists for <= 64 shadow samples, with the cull)
@@ -953,6 +1097,14 @@ void launch_wave(const FrameParams& P, bool cull, bool count, hipStream_t stream
   const dim3 block(64 * kWavesPerBlock);
   const dim3 grid = wave_grid(P);
   const size_t lds_bytes = wave_kernel_lds(P, cull);
+  // the tile seeds of this frame, directly in front of the draw kernel that reads them (the host sets P.seed only where
+  // wave_takes_seed holds and the table has room)
+  if (P.seed != nullptr && !count) {
+    const int tiles = P.seed_tile_rows * P.nseg;
+    const int want = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int room = P.wave_blocks > 0 ? P.wave_blocks : 256 * kMinWaves;
+    hipLaunchKernelGGL(rt_wave_seed, dim3(want < room ? (want > 0 ? want : 1) : room), block, wave_kernel_lds(P, true) , stream, P);
+  }
   // one memset: the queue heads, and this frame's HeavyState, which lies directly before or behind them
   const size_t heads_bytes = 2 * kJobHeads * kJobHeadStride * sizeof(unsigned int), state_bytes = kJobHeadStride * sizeof(unsigned int);
   if (P.heavy_new != nullptr && !count) {

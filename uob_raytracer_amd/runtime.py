@@ -26,7 +26,7 @@ EXPORTS = (
     "rt_abi_version", "rt_last_error", "rt_config_default", "rt_config_owned_rows", "rt_init", "rt_render",
     "rt_render_device", "rt_count_work", "rt_count_executed", "rt_last_kernel_ms", "rt_destroy", "rt_scene_cornell_box",
     "rt_scene_load_obj", "rt_scene_load_obj_ex", "rt_triangle_compute_normal", "rt_scene_pack", "rt_rotation_matrix",
-    "rt_selftest_rcp", "rt_selftest_normalize", "rt_selftest_shade", "rt_selftest_all_within", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_register_output", "rt_unregister_output",
+    "rt_selftest_rcp", "rt_selftest_normalize", "rt_selftest_shade", "rt_selftest_all_within", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_debug_wave_seeds", "rt_register_output", "rt_unregister_output",
     "rt_debug_band_copy_plan", "rt_update_scene", "rt_update_scene_device", "rt_debug_tile_data",
     "rt_trace_rays", "rt_trace_rays_device", "rt_debug_trace_stats",
     "rt_render_aov", "rt_render_aov_device", "rt_debug_aov_stats",
@@ -71,6 +71,12 @@ class RtError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libuob_rt: error %d: %s" % (code, msg))
         self.code = code
+
+
+# one tile-seed record (include/uob_rt.h rt_debug_wave_seeds): 64 bytes
+SEED_DTYPE = np.dtype([("D0", "<f4", 3), ("ed", "<f4"), ("K", "<u8"), ("Kh", "<u8"), ("Kp", "<u8"), ("h", "<i4"), ("flags", "<u4"),
+                       ("pad", "<u4", 4)])
+SEED_PRIMARY, SEED_SHADOW = 1, 2
 
 
 def lib():
@@ -1239,6 +1245,21 @@ class RayTracer:
         first, last = int(out[1]), int(out[2])
         return {"waves": int(out[0]), "span_us": (last - first) / 100.0, "mean_start_us": (int(out[3]) / n - first) / 100.0,
                 "mean_idle_tail_us": (last - int(out[4]) / n) / 100.0, "jobs": int(out[5]), "max_jobs_per_wave": int(out[6]), "listed_jobs": int(out[7])}
+
+    def wave_seeds(self):
+        """Wave kernel: the tile seeds of the last frame (rt_debug_wave_seeds).  -> dict: tile_rows, tiles_per_row, rows_per_tile
+        (all 0 when the frame took no seed), tiles_primary, tiles_shadow, jobs_primary, jobs_shadow, and `records`, a
+        structured array [tile_rows, tiles_per_row] of SEED_DTYPE."""
+        fn = lib().rt_debug_wave_seeds
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+        dims, cnt = (C.c_int32 * 3)(), (C.c_uint64 * 4)()
+        _check(fn(self._h, None, 0, dims, cnt))
+        rec = np.zeros((int(dims[0]), int(dims[1])), SEED_DTYPE)
+        if rec.size:
+            _check(fn(self._h, rec.ctypes.data_as(C.c_void_p), rec.size, dims, cnt))
+        return {"tile_rows": int(dims[0]), "tiles_per_row": int(dims[1]), "rows_per_tile": int(dims[2]),
+                "tiles_primary": int(cnt[0]), "tiles_shadow": int(cnt[1]), "jobs_primary": int(cnt[2]), "jobs_shadow": int(cnt[3]),
+                "records": rec}
 
     def world_masks(self):
         """Mesh kernel: the last frame's shadow-ray tile masks, uint64 [G, G, G, words] indexed [z, y, x] (rt_debug_world_masks)."""
