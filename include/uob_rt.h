@@ -663,8 +663,20 @@ int rt_debug_wave_timeline(rt_ctx* ctx, uint64_t out[8]);
  *   seed (UOB_RT_NO_SEED=1, another kernel or instantiation, no frame yet): then nothing is copied and the counters are 0
  *   counters[0] tiles with a valid primary part   counters[1] tiles with a valid shadow part
  *   counters[2], counters[3] jobs of this context's rows that started from one (every job reads its tile's record)
- * Copies min(tiles, cap) records to `records` (may be NULL with cap 0).  Waits for the context's last frame.            */
+ * Copies min(tiles, cap) records to `records` (may be NULL with cap 0).  Waits for the context's last frame.
+ * This is the STRICT view of the table: a primary part counts where the tile's bound leaves one triangle and no sphere, a
+ * shadow part where level 1 over such a tile has nothing to do; the fields of a part that is not strict read as unset.  */
 int rt_debug_wave_seeds(rt_ctx* ctx, void* records, int64_t cap, int32_t dims[3], uint64_t counters[4]);
+
+/* The same table as the draw kernel reads it (records, cap, dims as above).  flags: 1, 2 the strict bits above;
+ *   4  primary part: Kp holds every triangle a primary ray of the tile can hit   8  ... and a sphere may be touched
+ *   16 shadow part: D0, ed, K, Kh, h are level 1's outcome around the point the tile's centre ray hits on triangle h
+ *   32 ... with a sphere candidate   64 ... blocked (one caster shadows every ray of the set)
+ * What is kept: UOB_RT_SEED_KP (most triangles of a primary part), UOB_RT_SEED_CASTERS (most casters off h's plane, Kh, of
+ * a shadow part), UOB_RT_SEED_SPH (0: no shadow part with a sphere candidate); a blocked shadow part is always kept.
+ *   counters[2 q], counters[2 q + 1]: tiles, and jobs of this context's rows, whose record has   q = 0 a primary part
+ *   1 a shadow part   2 a shadow part with Kh != 0   3 a shadow part with a sphere candidate   4 a blocked shadow part  */
+int rt_debug_wave_seeds_wide(rt_ctx* ctx, void* records, int64_t cap, int32_t dims[3], uint64_t counters[10]);
 
 /* Diagnostic, several devices in one context (rt_config.devices): the copies that carry device k's packed bands
  * (bands k, k+N, ... of device_band_rows rows, owned rows packed top to bottom in its stripe) to image order in a

@@ -94,6 +94,9 @@ static Tuning read_tuning(const rt_config& cfg) {
   if (const char* e = getenv("UOB_RT_TILE_ORDER")) t.tile_morton = !strcmp(e, "morton");
   if (const char* e = getenv("UOB_RT_NO_SEED")) t.no_seed = atoi(e) != 0;
   if (const char* e = getenv("UOB_RT_SEED_ROWS")) { const int v = atoi(e); if (v >= 1 && v <= 64) t.seed_rows = v; }
+  if (const char* e = getenv("UOB_RT_SEED_KP")) { const int v = atoi(e); if (v >= 1 && v <= 64) t.seed_kp = v; }
+  if (const char* e = getenv("UOB_RT_SEED_CASTERS")) { const int v = atoi(e); if (v >= 0 && v <= 64) t.seed_casters = v; }
+  if (const char* e = getenv("UOB_RT_SEED_SPH")) t.seed_sph = atoi(e) != 0;
   if (const char* e = getenv("UOB_RT_FILTER_FORM")) t.filter_form = !strcmp(e, "direct") ? kFilterFormDirect : kFilterFormBuiltIn;
   return t;
 }
@@ -426,6 +429,7 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
       P.seed = c->d_seed; P.seed_rows = R; P.seed_tile_rows = tile_rows; P.seed_rows_magic = div_magic_for(R);
       P.seed_hy = 0.5f * (float)(R * P.aa_y - 1) * P.sy;
       for (int k = 0; k < 3; ++k) P.seed_eu[k] = 1.0001f * (fabsf(rot[4 * k]) * P.job_hx + fabsf(rot[4 * k + 1]) * P.seed_hy);
+      P.seed_kp_cap = c->tune.seed_kp; P.seed_caster_cap = c->tune.seed_casters; P.seed_keep_sph = c->tune.seed_sph ? 1 : 0;
       c->seed_tile_rows = tile_rows; c->seed_nseg = P.nseg; c->seed_rows = R;
     }
     launch_wave(P, !(c->cfg.flags & RT_FLAG_NO_CULL), false, stream);
@@ -769,31 +773,69 @@ int rt_debug_wave_timeline(rt_ctx* c, uint64_t out[8]) {
   return RT_OK;
 }
 
+// The last frame's seed table and, per tile, the rows of it the context renders (each of them is one job per column, and
+// every job reads its tile's record); an empty table when the last frame took no seed
+static int read_seed_table(rt_ctx* c, std::vector<SeedRec>* rec, std::vector<uint64_t>* rows) {
+  rec->clear(); rows->clear();
+  if (c->seed_tile_rows == 0) return RT_OK;
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->timed) HIP_TRY(hipEventSynchronize(c->ev1));
+  rec->resize((size_t)c->seed_tile_rows * (size_t)c->seed_nseg);
+  HIP_TRY(hipMemcpy(rec->data(), c->d_seed, rec->size() * sizeof(SeedRec), hipMemcpyDeviceToHost));
+  const rt_config& g = c->cfg;
+  rows->assign((size_t)c->seed_tile_rows, 0);
+  for (int tr = 0; tr < c->seed_tile_rows; ++tr)
+    for (int y = tr * c->seed_rows; y < (tr + 1) * c->seed_rows && y < g.height; ++y)
+      (*rows)[tr] += ((y / g.band_rows) % g.band_count) == g.band_index;
+  return RT_OK;
+}
+
+// The strict view: the strict bits alone, and nothing of a part whose strict bit is not set
 int rt_debug_wave_seeds(rt_ctx* c, void* records, int64_t cap, int32_t dims[3], uint64_t counters[4]) {
   if (!c || !dims || !counters || cap < 0 || (cap > 0 && !records)) { set_error("NULL argument"); return RT_E_INVALID; }
   c = lead_ctx(c);
   dims[0] = c->seed_tile_rows; dims[1] = c->seed_nseg; dims[2] = c->seed_rows;
   for (int q = 0; q < 4; ++q) counters[q] = 0;
   if (c->seed_tile_rows == 0) { dims[1] = 0; return RT_OK; }      // the last frame took no seed: an empty table
-  DeviceGuard guard;
-  HIP_TRY(hipSetDevice(c->device));
-  if (c->timed) HIP_TRY(hipEventSynchronize(c->ev1));
-  const size_t tiles = (size_t)c->seed_tile_rows * (size_t)c->seed_nseg;
-  std::vector<SeedRec> rec(tiles);
-  HIP_TRY(hipMemcpy(rec.data(), c->d_seed, tiles * sizeof(SeedRec), hipMemcpyDeviceToHost));
-  const rt_config& g = c->cfg;
-  for (int tr = 0; tr < c->seed_tile_rows; ++tr) {
-    // the rows of this tile the context renders: each of them is one job per column, and every job reads its tile's record
-    uint64_t rows = 0;
-    for (int y = tr * c->seed_rows; y < (tr + 1) * c->seed_rows && y < g.height; ++y)
-      rows += ((y / g.band_rows) % g.band_count) == g.band_index;
-    for (int col = 0; col < c->seed_nseg; ++col) {
-      const uint32_t f = rec[(size_t)tr * c->seed_nseg + col].flags;
-      if (f & kSeedPrimary) { counters[0] += 1; counters[2] += rows; }
-      if (f & kSeedShadow) { counters[1] += 1; counters[3] += rows; }
-    }
+  std::vector<SeedRec> rec;
+  std::vector<uint64_t> rows;
+  const int rc = read_seed_table(c, &rec, &rows);
+  if (rc != RT_OK) return rc;
+  for (size_t t = 0; t < rec.size(); ++t) {
+    SeedRec& r = rec[t];
+    r.flags &= kSeedPrimary | kSeedShadow;
+    if (!(r.flags & kSeedPrimary)) r.Kp = 0ull;
+    if (!(r.flags & kSeedShadow)) { r.D0[0] = r.D0[1] = r.D0[2] = 0.0f; r.ed = 0.0f; r.K = 0ull; r.Kh = 0ull; r.h = -1; }
+    const uint64_t n = rows[t / (size_t)c->seed_nseg];
+    if (r.flags & kSeedPrimary) { counters[0] += 1; counters[2] += n; }
+    if (r.flags & kSeedShadow) { counters[1] += 1; counters[3] += n; }
   }
-  if (records) memcpy(records, rec.data(), (size_t)((int64_t)tiles < cap ? (int64_t)tiles : cap) * sizeof(SeedRec));
+  if (records) memcpy(records, rec.data(), (size_t)((int64_t)rec.size() < cap ? (int64_t)rec.size() : cap) * sizeof(SeedRec));
+  return RT_OK;
+}
+
+// The records as the draw kernel reads them
+int rt_debug_wave_seeds_wide(rt_ctx* c, void* records, int64_t cap, int32_t dims[3], uint64_t counters[10]) {
+  if (!c || !dims || !counters || cap < 0 || (cap > 0 && !records)) { set_error("NULL argument"); return RT_E_INVALID; }
+  c = lead_ctx(c);
+  dims[0] = c->seed_tile_rows; dims[1] = c->seed_nseg; dims[2] = c->seed_rows;
+  for (int q = 0; q < 10; ++q) counters[q] = 0;
+  if (c->seed_tile_rows == 0) { dims[1] = 0; return RT_OK; }
+  std::vector<SeedRec> rec;
+  std::vector<uint64_t> rows;
+  const int rc = read_seed_table(c, &rec, &rows);
+  if (rc != RT_OK) return rc;
+  for (size_t t = 0; t < rec.size(); ++t) {
+    const SeedRec& r = rec[t];
+    const uint64_t n = rows[t / (size_t)c->seed_nseg];
+    const bool shadow = (r.flags & kSeedShadowWide) != 0u;
+    const bool is[5] = {(r.flags & kSeedPrimaryWide) != 0u, shadow, shadow && r.Kh != 0ull, shadow && (r.flags & kSeedShadowSph) != 0u,
+                        shadow && (r.flags & kSeedShadowBlocked) != 0u};
+    for (int q = 0; q < 5; ++q)
+      if (is[q]) { counters[2 * q] += 1; counters[2 * q + 1] += n; }
+  }
+  if (records) memcpy(records, rec.data(), (size_t)((int64_t)rec.size() < cap ? (int64_t)rec.size() : cap) * sizeof(SeedRec));
   return RT_OK;
 }
 

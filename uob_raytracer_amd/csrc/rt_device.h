@@ -33,6 +33,14 @@ struct DevSphere {
 //   shadow  (kSeedShadow) : the outcome of level 1 over every shadow ray whose direction lies within ed of D0 — the casters K,
 //                           K without those whose plane holds triangle h (Kh), no sphere candidate, not blocked
 // A record without a flag says nothing: the job does what it did before there were seeds.
+// The two bits above are the STRICT parts — one triangle and no sphere; then level 1 with nothing to do — and what
+// rt_debug_wave_seeds reports.  What the draw kernel reads are the wide bits (a strict part is always a wide one too):
+//   kSeedPrimaryWide  Kp holds every triangle a primary ray of the tile can hit (at most FrameParams.seed_kp_cap of them),
+//   kSeedPrimarySph   ... and a sphere may be touched;
+//   kSeedShadowWide   D0, ed, K, Kh, h are the whole outcome of level 1 around the point the tile's centre ray hits on the
+//                     diffuse triangle h, whatever else the tile shows; kSeedShadowSph: a sphere candidate, kSeedShadowBlocked:
+//                     one caster blocks every ray of the set.  The three bits lie as the draw kernel's kJkValid, kJkSph,
+//                     kJkBlocked do: jk_flags = (flags >> kSeedShadowShift) & 7.
 struct alignas(16) SeedRec {
   float D0[3], ed;
   unsigned long long K, Kh, Kp;
@@ -41,6 +49,9 @@ struct alignas(16) SeedRec {
   uint32_t pad[4];
 };
 constexpr uint32_t kSeedPrimary = 1u, kSeedShadow = 2u;
+constexpr uint32_t kSeedPrimaryWide = 4u, kSeedPrimarySph = 8u;
+constexpr int kSeedShadowShift = 4;
+constexpr uint32_t kSeedShadowWide = 1u << kSeedShadowShift, kSeedShadowSph = 2u << kSeedShadowShift, kSeedShadowBlocked = 4u << kSeedShadowShift;
 static_assert(sizeof(SeedRec) == 64, "one record per 64-byte line");
 
 // Everything one frame needs, passed by value as the kernel argument (lives in SGPRs / the scalar cache).
@@ -133,6 +144,9 @@ struct FrameParams {
   uint32_t seed_rows_magic;           // div_magic of seed_rows
   float seed_hy;                      // half height of a tile's sub-pixel rectangle (job_hy of seed_rows rows)
   float seed_eu[3];                   // job_eu with seed_hy in place of job_hy
+  // what rt_wave_seed keeps (UOB_RT_SEED_KP, UOB_RT_SEED_CASTERS, UOB_RT_SEED_SPH): a primary part of at most seed_kp_cap
+  // triangles; a shadow part with at most seed_caster_cap casters off h's plane; one that names a sphere candidate
+  int32_t seed_kp_cap, seed_caster_cap, seed_keep_sph;
 };
 
 

@@ -142,6 +142,11 @@ struct Tuning {
   int filter_form = 0;        // UOB_RT_FILTER_FORM=direct: every filter pass takes its taps from the caches (tools/filter_time.py)
   bool no_seed = false;       // UOB_RT_NO_SEED=1: no tile-seed pre-pass, every job of the wave kernel starts unseeded
   int seed_rows = 16;         // UOB_RT_SEED_ROWS: rows of a seed tile (1 .. 64); the default is the default band height
+  // what the pre-pass keeps (rt_device.h FrameParams seed_*_cap; the defaults by profiles/tile_seed_wide_ab.txt).  (1, 0, 0)
+  // keeps what the strict rule kept, and a blocked level 1
+  int seed_kp = 64;           // UOB_RT_SEED_KP: most triangles of a primary part (1 .. 64)
+  int seed_casters = 32;      // UOB_RT_SEED_CASTERS: most casters off h's plane of a shadow part (0 .. 64)
+  bool seed_sph = true;       // UOB_RT_SEED_SPH: keep shadow parts that name a sphere candidate
 };
 
 // ---- owners of device objects: move-only, and no device is stored — whoever frees on a given device sets

@@ -522,9 +522,11 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
   unsigned long long Kp_job = n == 64 ? ~0ull : ((1ull << n) - 1ull);
   bool sph_job = P.nsph > 0;
   // SEED: the job starts from its screen tile's record (rt_wave_seed below, DESIGN.md 4.1 "tile seeds") where that holds
-  // something: a primary part stands for the job's own bound — the tile's rectangle contains the job's — and a shadow part is
-  // a level 1 in the state the previous task of a job leaves behind, which every task puts to the reuse test as it does any
-  // other: nothing downstream knows where jk_* came from.  One wave-uniform load per job through the scalar cache (the table
+  // something: a primary part stands for the job's own bound — the tile's rectangle contains the job's, and a set of several
+  // triangles or one with the sphere bit is the same superset statement as a single triangle — and a shadow part is a level 1
+  // in the state the previous task of a job leaves behind (casters in K and Kh, a sphere candidate, blocked: the states level 2
+  // and the sphere test cope with after any fresh level 1), which every task puts to the reuse test as it does any other:
+  // nothing downstream knows where jk_* came from.  One wave-uniform load per job through the scalar cache (the table
   // is written by the launch in front of this one and read-only here).  The (4x2, 64) instantiation alone, like MASKS a
   // compile-time condition: the others hold the code they held.
   constexpr bool SEED = CULL && !COUNT && !PROF && MASKS && STRIDE == 32 && AA_X == 4 && AA_Y == 2 && SS == 64 && !MULTI && !BIGAA;
@@ -535,12 +537,15 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
     typedef const __attribute__((address_space(4))) SeedRec* SeedPtr;
     const SeedPtr rec = (SeedPtr)(unsigned long long)(PC(seed) + ti);
     const uint32_t sf = rec->flags;
-    if ((sf & kSeedPrimary) != 0u) { Kp_job = rec->Kp; sph_job = false; seeded = true; }
-    if ((sf & kSeedShadow) != 0u) {
+    if ((sf & kSeedPrimaryWide) != 0u) { Kp_job = rec->Kp; sph_job = (sf & kSeedPrimarySph) != 0u; seeded = true; }
+    if ((sf & kSeedShadowWide) != 0u) {
       jk_D0 = mk(rec->D0[0], rec->D0[1], rec->D0[2]); jk_ed = rec->ed;
       jk_K = rec->K; jk_Kh = (kh_t)rec->Kh; jk_h = rec->h;
-      jk_flags = kJkValid;
     }
+    // valid, sphere candidate, blocked: the record's three bits lie as kJkValid, kJkSph, kJkBlocked do (0 without a shadow part)
+    static_assert((kSeedShadowWide >> kSeedShadowShift) == kJkValid && (kSeedShadowSph >> kSeedShadowShift) == kJkSph &&
+                  (kSeedShadowBlocked >> kSeedShadowShift) == kJkBlocked, "jk_flags is a shift and a mask of the record's flags");
+    jk_flags = (int)((sf >> kSeedShadowShift) & 7u);
   }
   if (CULL && !(SEED && seeded)) {
     const int lnJ = opaque(lane);
@@ -948,14 +953,18 @@ template __global__ void rt_draw_wave<true, false, false, 0, false, 0, 0, 0, tru
 // One wave per screen tile (P.seed_rows rows of one job column), lane = triangle / caster throughout, in a loop over the
 // tiles by a grid the device holds at once; the scene is staged as the draw kernel stages it.  Per tile one SeedRec:
 //   primary part  the job's own bound (primary_clear, sphere_bundle_maybe) over the tile's sub-pixel rectangle, which
-//                 contains the rectangle of every job of the tile: kept when it leaves ONE triangle h and no sphere;
-//   shadow part   only then, and only for a diffuse h: level 1 (level1_bundle: the draw kernel's fresh level 1) around the
-//                 surface point X0 the tile's centre ray hits, over every direction within ed of D0 = light - X0, ed from the
+//                 contains the rectangle of every job of the tile: kept when it is finite and leaves at most seed_kp_cap
+//                 triangles, with a bit for "a sphere may be touched" (strict: ONE triangle and no sphere);
+//   shadow part   for a diffuse triangle h, the one the tile's centre ray hits: level 1 (level1_bundle: the draw kernel's
+//                 fresh level 1) around that surface point X0, over every direction within ed of D0 = light - X0, ed from the
 //                 four corner rays' hits on h's plane.  ed decides how many tasks pass the draw kernel's reuse test, never
-//                 whether the bound is right: it only has to be finite.  Kept when the outcome is "nothing to do": no caster
-//                 left off h's plane, no sphere candidate, not blocked.
-// Everything else — a non-finite value anywhere, a tile with no row of this rank, a centre ray that misses h or faces away
-// from the light — leaves the part invalid, which is always a correct answer.
+//                 whether the bound is right: it only has to be finite — K is a statement about every shadow ray of that
+//                 direction set, whatever triangle its point lies on, and Kh one about those that leave h.  Kept whole (K, Kh,
+//                 sphere candidate, blocked) when blocked, or when Kh has at most seed_caster_cap casters and no sphere
+//                 candidate is named or seed_keep_sph is set (strict: on a strict tile, Kh empty, no sphere, not blocked).
+// Everything else — a non-finite value anywhere, a tile with no row of this rank, a corner behind h's plane, a centre ray that
+// misses, hits a sphere, glass or a mirror or faces away from the light — leaves the part invalid, which is always a correct
+// answer.  (Measured on the headline frame, profiles/tile_seed_wide_ab.txt: every cap wide open is the fastest setting.)
 __global__ __launch_bounds__(64 * kWavesPerBlock) void rt_wave_seed(const FrameParams P) {
   extern __shared__ float4 lds_dyn[];
   float4* const lds = lds_dyn;
@@ -1019,21 +1028,30 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void rt_wave_seed(const FrameP
       if (P.nsph > 0 && dumax < 1e30f)
         sph = ballot(sphere_bundle_maybe(P, lane, mk(P.cam[0], P.cam[1], P.cam[2]), 0.0f, duc, bsqrt(dot3(duc, duc)),
                                          1.0001f * bsqrt(dot3(eu, eu)), false)) != 0ull;
-      if (dumax < 1e30f && __popcll(Kp) == 1 && !sph) {
-        rec.Kp = Kp; rec.flags = kSeedPrimary;
-        const int h = __builtin_ctzll(Kp);
+      const int nkp = __popcll(Kp);
+      if (dumax < 1e30f) {
+        const bool strict = nkp == 1 && !sph;                        // one triangle, no sphere: the strict primary part
+        if (nkp <= P.seed_kp_cap) {
+          rec.Kp = Kp;
+          rec.flags = kSeedPrimaryWide | (sph ? kSeedPrimarySph : 0u) | (strict ? kSeedPrimary : 0u);
+        }
         // ---- shadow part.  Lanes 0..3 send the tile's corner rays, the others its centre ray: all of them rays of the
-        // bundle bounded above, so h is the one triangle any of them can hit.
+        // bundle bounded above, so Kp (and the spheres, where one may be touched) is all any of them can hit.
         const int cx = lane < 4 ? ((lane & 1) ? x0 + JP - 1 : x0) : x0 + (JP >> 1);
         const int cy = lane < 4 ? ((lane & 2) ? y0 + R - 1 : y0) : y0 + (R >> 1);
         const int cdx = (lane < 4 && (lane & 1)) ? P.aa_x - 1 : 0, cdy = (lane < 4 && (lane & 2)) ? P.aa_y - 1 : 0;
         Ray ray = primary_ray(P, cx, cy, cdx, cdy, P.aa_x, P.aa_y, P.sy);
         const f3 rd = ray.dir;
-        closest_hit_primary_masked(S, P, ray, Kp, false);            // the centre ray's hit, by the arithmetic of the primary hit
+        closest_hit_primary_masked(S, P, ray, Kp, sph);              // the centre ray's hit, by the arithmetic of the primary hit
+        const int jr = 4;                                            // a centre lane
+        // h: the triangle the centre ray hits (the one triangle of a strict tile, hit or not, as ever); a miss (-1) or a
+        // sphere (-2) leaves no shadow part
+        const int hc_tri = __builtin_amdgcn_readlane(ray.tri, jr);
+        const int h = nkp == 1 ? __builtin_ctzll(Kp) : hc_tri;
+        if (h >= 0 && h < n) {
         const LightSetup ls = light_setup(light, ray);
         const bool slit = ray.tri == h && ray.col.w > 0.0f && !(ls.term == 0.0f);
         const CullConsts cc = cull_consts(ls.radius_sq, P.hbox, slit);
-        const int jr = 4;                                            // a centre lane
         const f3 s0 = mk(rl(ls.start.x, jr), rl(ls.start.y, jr), rl(ls.start.z, jr));
         const f3 D0 = mk(rl(ls.dir.x, jr), rl(ls.dir.y, jr), rl(ls.dir.z, jr));
         const float dlen0 = rl(cc.dlen, jr);
@@ -1048,11 +1066,18 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void rt_wave_seed(const FrameP
         const float ed = 1.05f * wave_max_pos(lane < 4 && corner_ok ? dev : 0.0f) + 1e-5f * (P.light_inf + dlen0);
         if (sane0 && corners && ed < 1e30f) {
           const Level1 l1 = level1_bundle(P, S, SC, lane, ns, tri_lanes, light, P.hbox, s0, D0, ed, dlen0, h);
-          if (l1.ok && l1.Kh == 0ull && !l1.sph && !l1.blocked) {
+          // kept: "blocked" always — the cheapest outcome a task can have, and nothing of K is walked then; else within the
+          // caps, which "nothing to do" (the strict outcome, on a strict tile) always is
+          const bool nothing = l1.Kh == 0ull && !l1.sph && !l1.blocked;
+          const bool keep = l1.blocked || (__popcll(l1.Kh) <= P.seed_caster_cap && (!l1.sph || P.seed_keep_sph != 0));
+          if (l1.ok && keep) {
             rec.D0[0] = D0.x; rec.D0[1] = D0.y; rec.D0[2] = D0.z;
             rec.ed = uniform(ed * 0.9999f);       // what the tasks compare with (the bound itself allows 1.001 ed and more)
-            rec.K = l1.K; rec.Kh = l1.Kh; rec.h = h; rec.flags = kSeedPrimary | kSeedShadow;
+            rec.K = l1.K; rec.Kh = l1.Kh; rec.h = h;
+            rec.flags |= kSeedShadowWide | (l1.sph ? kSeedShadowSph : 0u) | (l1.blocked ? kSeedShadowBlocked : 0u) |
+                         (strict && nothing ? kSeedShadow : 0u);
           }
+        }
         }
       }
     }

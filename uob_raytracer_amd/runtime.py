@@ -26,7 +26,7 @@ EXPORTS = (
     "rt_abi_version", "rt_last_error", "rt_config_default", "rt_config_owned_rows", "rt_init", "rt_render",
     "rt_render_device", "rt_count_work", "rt_count_executed", "rt_last_kernel_ms", "rt_destroy", "rt_scene_cornell_box",
     "rt_scene_load_obj", "rt_scene_load_obj_ex", "rt_triangle_compute_normal", "rt_scene_pack", "rt_rotation_matrix",
-    "rt_selftest_rcp", "rt_selftest_normalize", "rt_selftest_shade", "rt_selftest_all_within", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_debug_wave_seeds", "rt_register_output", "rt_unregister_output",
+    "rt_selftest_rcp", "rt_selftest_normalize", "rt_selftest_shade", "rt_selftest_all_within", "rt_debug_trace_rays", "rt_debug_block_costs", "rt_debug_world_masks", "rt_debug_wave_timeline", "rt_debug_wave_seeds", "rt_debug_wave_seeds_wide", "rt_register_output", "rt_unregister_output",
     "rt_debug_band_copy_plan", "rt_update_scene", "rt_update_scene_device", "rt_debug_tile_data",
     "rt_trace_rays", "rt_trace_rays_device", "rt_debug_trace_stats",
     "rt_render_aov", "rt_render_aov_device", "rt_debug_aov_stats",
@@ -77,6 +77,9 @@ class RtError(RuntimeError):
 SEED_DTYPE = np.dtype([("D0", "<f4", 3), ("ed", "<f4"), ("K", "<u8"), ("Kh", "<u8"), ("Kp", "<u8"), ("h", "<i4"), ("flags", "<u4"),
                        ("pad", "<u4", 4)])
 SEED_PRIMARY, SEED_SHADOW = 1, 2
+# rt_debug_wave_seeds_wide: the bits the draw kernel reads, and its counters (tiles_<key>, jobs_<key> in this order)
+SEED_PRIMARY_WIDE, SEED_PRIMARY_SPH, SEED_SHADOW_WIDE, SEED_SHADOW_SPH, SEED_SHADOW_BLOCKED = 4, 8, 16, 32, 64
+SEED_WIDE_KEYS = ("primary", "shadow", "casters", "sphere", "blocked")
 
 
 def lib():
@@ -1260,6 +1263,22 @@ class RayTracer:
         return {"tile_rows": int(dims[0]), "tiles_per_row": int(dims[1]), "rows_per_tile": int(dims[2]),
                 "tiles_primary": int(cnt[0]), "tiles_shadow": int(cnt[1]), "jobs_primary": int(cnt[2]), "jobs_shadow": int(cnt[3]),
                 "records": rec}
+
+    def wave_seeds_wide(self):
+        """Wave kernel: the tile seeds of the last frame as the draw kernel reads them (rt_debug_wave_seeds_wide).  -> dict:
+        tile_rows, tiles_per_row, rows_per_tile, tiles_<k> and jobs_<k> for k in SEED_WIDE_KEYS (records with a primary part,
+        a shadow part, and of those the ones with casters off h's plane, a sphere candidate, blocked), and the raw `records`."""
+        fn = lib().rt_debug_wave_seeds_wide
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+        dims, cnt = (C.c_int32 * 3)(), (C.c_uint64 * 10)()
+        _check(fn(self._h, None, 0, dims, cnt))
+        rec = np.zeros((int(dims[0]), int(dims[1])), SEED_DTYPE)
+        if rec.size:
+            _check(fn(self._h, rec.ctypes.data_as(C.c_void_p), rec.size, dims, cnt))
+        d = {"tile_rows": int(dims[0]), "tiles_per_row": int(dims[1]), "rows_per_tile": int(dims[2]), "records": rec}
+        for q, k in enumerate(SEED_WIDE_KEYS):
+            d["tiles_" + k], d["jobs_" + k] = int(cnt[2 * q]), int(cnt[2 * q + 1])
+        return d
 
     def world_masks(self):
         """Mesh kernel: the last frame's shadow-ray tile masks, uint64 [G, G, G, words] indexed [z, y, x] (rt_debug_world_masks)."""
