@@ -132,6 +132,40 @@ def main():
     print("golden vectors written to", HERE)
 
 
+class _RefCalls:
+    """The reference kernel's closest hit behind the oracle's signature (tests/ties_util.py census takes either)"""
+
+    def __init__(self, kernel):
+        self.k = kernel
+
+    def closest_hit(self, cfg, v, n, c, rays):
+        return self.k.closest_hit(v, n, c, rays)
+
+
+def vs_ref_ties(T, box):
+    """The tie scenes of tests/test_oracle_vs_ref.py on the reference's default kernel: per scene the hashes of its frames,
+    of the winning triangle and the ten outputs of single_ray_intersections on the scene's rays, and how many of those rays
+    meet two triangles at bit-equal t (the lower index wins in either order of the pair) by the reference's own answer."""
+    import ties_util as tu
+    from uob_raytracer_amd import runtime as rt
+    k = R.RefKernel(T.TIE_CASE)
+    out = {"case": T.TIE_CASE, "views": T.TIE_VIEWS, "rays": T.TIE_RAYS, "scenes": {}}
+    for name in T.TIE_SCENES:
+        aos, pairs, rays = T.tie_scene(name, box)
+        v, n, c = R.pack_scene(aos)
+        frames = []
+        for vname in T.TIE_VIEWS:
+            rot, cam, light, focal = T.tie_view(vname)
+            argb, tap = k.render(v, n, c, rot, cam, light, focal)
+            frames.append({"argb": T.digest(argb), "tap": T.digest(tap)})
+        tri, hit = k.closest_hit(v, n, c, rays)
+        assert (tri != -1).all()         # (-2: one of the reference's spheres in front)
+        tied = tu.census(_RefCalls(k), None, rt.Scene(aos), pairs, rays)["tied"]
+        out["scenes"][name] = {"n": int(aos.shape[0]), "frames": frames, "tied_rays": int(tied),
+                               "closest_hit": {"tri": T.digest(tri), "out": T.digest(hit)}}
+    return out
+
+
 def vs_ref():
     """oracle_vs_ref.json: hashes of the reference kernel's frames for the cases of tests/test_oracle_vs_ref.py."""
     sys.path.insert(0, os.path.dirname(HERE))
@@ -149,6 +183,7 @@ def vs_ref():
                 row.append({"argb": T.digest(argb), "tap": T.digest(tap)})
             frames.append(row)
         out["cases"][name] = {"config": kw, "frames": frames}
+    out["ties"] = vs_ref_ties(T, aos)
     with open(os.path.join(HERE, "oracle_vs_ref.json"), "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
     print("reference-kernel hashes written to", os.path.join(HERE, "oracle_vs_ref.json"))

@@ -378,9 +378,13 @@ def test_two_contexts_on_two_streams_and_one_on_alternating_streams(scene):
     order = [0, 1, 2, 0, 2, 1]
     rows, w = trs[0].rows, trs[0].width
 
+    # every frame's buffers poisoned before the first frame is enqueued: the fills run on torch's current stream, which the two
+    # streams below do not wait for (a fill enqueued between two frames can land on a frame already written)
+    bufs = [(torch.full((rows * w,), fc.SENTINEL, dtype=torch.int32, device=dev),
+             torch.full((rows * w, 4), float("nan"), dtype=torch.float32, device=dev)) for _ in range(3 * len(order))]
+
     def poisoned():
-        return (torch.full((rows * w,), fc.SENTINEL, dtype=torch.int32, device=dev),
-                torch.full((rows * w, 4), float("nan"), dtype=torch.float32, device=dev))
+        return bufs.pop()
 
     # two contexts, each on its own stream, frames interleaved, nothing waited for in between
     out = []

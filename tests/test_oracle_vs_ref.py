@@ -62,6 +62,63 @@ def test_oracle_equals_reference_kernel(name, scene, oracle, golden):
             assert digest(tap) == ref["tap"], "%s scene %d view %d: taps differ from the reference kernel" % (name, si, vi)
 
 
+# ---- closest-hit ties --------------------------------------------------------------------------------------------------
+# The reference keeps a hit unless a later triangle is STRICTLY nearer (kernels.cl:120, :194): at bit-equal t the lowest
+# original index wins.  Scenes of tests/ties_util.py in which thousands of rays meet two triangles at equal t, on the
+# reference's default kernel at 256x256: frames, and single_ray_intersections (:168) on 4 000 rays aimed at the tied
+# triangles — the winning index and the ten outputs.  tests/golden/ties_mesh_10x8_aos.npy is meshgen's (10, 8) sphere
+# through the product's loader, stored so that the hashed input does not depend on a machine's sin and cos.
+TIE_CASE = "default256"
+TIE_VIEWS = ["default", "side", "mesh_front"]
+TIE_SCENES = ["double_reversed_after", "double_reversed_first", "decal_wall_after", "decal_wall_first", "mesh_10x8_double_sided"]
+TIE_RAYS = 4000
+
+
+def tie_scene(name, box):
+    """-> (aos, pairs, rays) of a TIE_SCENES name"""
+    import ties_util as tu
+    from uob_raytracer_amd import runtime as rt
+    if name.startswith("mesh_"):
+        s, pairs = tu.mesh_scene(rt.Scene(box), np.load(os.path.join(G, "ties_mesh_10x8_aos.npy")), "mesh_copies")
+    else:
+        kind, order = name.rsplit("_", 1)
+        s, pairs = tu.box_scene(rt.Scene(box), {"double_reversed": "reversed", "decal_wall": "decal_wall"}[kind], order)
+    return s.aos, pairs, tu.seeded_rays(TIE_RAYS, 4242, s, pairs)
+
+
+def tie_view(name):
+    """-> (rot, cam, light, focal) of a TIE_VIEWS name on the TIE_CASE frame"""
+    import ties_util as tu
+    yaw, pitch, cam, light, lens = tu.view(name)
+    kw = CASES[TIE_CASE]
+    return pyref.rot_matrix(yaw, pitch), cam, light, 1100.0 * min(kw["width"], kw["height"]) / 1024.0 * 2 * lens
+
+
+@pytest.mark.parametrize("name", TIE_SCENES)
+def test_oracle_ties_equal_reference_kernel(name, scene, oracle, golden):
+    import ties_util as tu
+    want = golden["ties"]
+    assert want["case"] == TIE_CASE and want["views"] == TIE_VIEWS and want["rays"] == TIE_RAYS
+    cfg = abi.make_config(**CASES[TIE_CASE])
+    aos, pairs, rays = tie_scene(name, scene.aos)
+    v, n, c = pyref.pack_scene(aos)
+    ref = want["scenes"][name]
+    for vi, vname in enumerate(TIE_VIEWS):
+        rot, cam, light, focal = tie_view(vname)
+        a1, r1 = oracle.render(cfg, v, n, c, rot, cam, light, focal)
+        assert digest(a1) == ref["frames"][vi]["argb"], "%s view %s: ARGB differs from the reference kernel" % (name, vname)
+        assert digest(pyref.quantise(r1)[1]) == ref["frames"][vi]["tap"], "%s view %s: taps differ" % (name, vname)
+    tri, out = oracle.closest_hit(cfg, v, n, c, rays)
+    assert (tri != -1).all(), "a ray of the record misses the scene"        # (-2: a sphere in front)
+    assert digest(tri) == ref["closest_hit"]["tri"], name + ": the winning triangles differ from the reference's"
+    assert digest(out) == ref["closest_hit"]["out"], name + ": the ten outputs differ from the reference's"
+    # the record holds what it is for: rays that meet a pair at equal t, won by the lower index
+    from uob_raytracer_amd import runtime as rt
+    c_ = tu.census(oracle, cfg, rt.Scene(aos), pairs, rays)
+    print("%s: of %d rays %d on a pair, %d tied, %d untied" % (name, len(rays), c_["on_pair"], c_["tied"], c_["untied"]))
+    assert c_["tied"] >= 200 and c_["higher"] == 0 and ref["tied_rays"] == c_["tied"]
+
+
 def test_product_scene_equals_reference_scene(scene):
     """scene_cornell_aos.npy is the reference's own LoadTestModel (tests/golden/make_golden.py)."""
     want = np.load(os.path.join(G, "scene_cornell_aos.npy"))
