@@ -270,8 +270,12 @@ int rt_render_device(rt_ctx* ctx, const float rot[12], const float cam[3], const
 int rt_count_work(rt_ctx* ctx, const float rot[12], const float cam[3], const float light[3],
                   float focal, rt_work* out);
 
-/* Work the wave kernel actually EXECUTES for the frame (un-timed instrumented pass; fails with
- * RT_E_UNSUPPORTED for configurations that run on the generic kernel).  out[0] = surface points whose
+/* Work the wave kernel actually EXECUTES for the frame (un-timed instrumented pass).  Fails with
+ * RT_E_UNSUPPORTED for every frame the thread-per-pixel kernel renders — RT_FLAG_GENERIC_KERNEL; an empty scene
+ * or one whose triangles are all glass; a mesh (n > 64) with RT_FLAG_NO_CULL or with more than 64 AA samples per
+ * pixel; up to 64 triangles with more than 64 AA samples per pixel and either RT_FLAG_NO_CULL or more than 64
+ * shadow samples — and for the wave-kernel frames that have no counting build: more than 64 shadow samples, or
+ * more than 64 AA samples per pixel (the table at its head).  out[0] = surface points whose
  * samples were tested (level 3), out[1] = first-stage (t) sample-test passes = 64 sample tests each,
  * out[2] = second-stage (u,v) passes, out[3] = wave-wide sphere evaluations, out[4] = lit surface points
  * decided fully lit by the interval bounds, out[5] = 64-ray tasks that needed no sampling at all,

@@ -236,9 +236,9 @@ int rt_init(const rt_config* cfg, const float* vertices4, const float* normals4,
 
 }  // extern "C"
 
-void uobrt::fill_params(const rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal,
-                        FrameParams* P) {
-  memset(P, 0, sizeof *P);
+// fill_params, part 1: the view, the frame's constants and the scene
+static void fill_view_and_scene(const rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal,
+                                FrameParams* P) {
   memcpy(P->rot, rot, 12 * sizeof(float));
   memcpy(P->cam, cam, 3 * sizeof(float));
   memcpy(P->light, light, 3 * sizeof(float));
@@ -276,75 +276,89 @@ void uobrt::fill_params(const rt_ctx* c, const float rot[12], const float cam[3]
   P->records = c->d_records;
   P->mask_debug = c->tune.mask_debug;
   P->job_counter = c->d_jobctr + kJobHeadStride;      // [HeavyState 0 | queue heads | HeavyState 1], one line each
-  {   // wave kernel: a job is a run of job_tasks 64-ray tasks (job_tasks * 64/aa pixels) of one row
-    const int aa = g.aa_x * g.aa_y;
-    const bool wave_aa = aa >= 1 && aa <= 64;
-    const int big_chunks = aa > 64 ? (aa + 63) / 64 : 0;      // 65..256 AA samples: a pixel is big_chunks tasks (rt_kernel_wave.hip BIGAA)
-    // Job size: up to 64 pixels, halved while the queue would hold fewer than ~16 jobs per resident wave (jobs differ
-    // 10x in cost, but every hand-out stalls its wave for microseconds; measured with last frame's expensive jobs
-    // going first: 4096 and 2048 rows -> 64 px, 1024 and 512 rows -> 32 px), but not below 16 pixels.
-    const int pt = wave_aa ? 64 / aa : 64;              // pixels per 64-ray task
-    P->aa_magic = wave_aa ? (65536 + aa - 1) / aa : 65536;
-    P->aax_magic = (65536 + g.aa_x - 1) / g.aa_x;
-    // workgroups the chip holds at once; a rank of a multi-GPU job leaves one slot per CU free (registers and LDS
-    // for a workgroup of a collective's kernels), so that the gather of the previous frame can run beside it
-    const int per_cu = c->tune.grid_per_cu ? c->tune.grid_per_cu : wave_blocks_per_cu(g.band_count > 1 && !c->tune.full_grid);
-    P->wave_blocks = c->cus * per_cu;
-    const long waves = (long)P->wave_blocks * 4;
-    int jt = wave_aa ? 64 / pt : 1;                      // tasks of a 64-pixel job (aa for the power-of-two grids)
-    while (jt > 1 && ((jt + 1) / 2) * pt >= 16 && (long)((g.width + jt * pt - 1) / (jt * pt)) * c->owned_rows < 16 * waves) jt = (jt + 1) / 2;
-    // (the knob may not make a job smaller than 16 pixels: div_magic's exactness bound, rt_device.h, is stated for >= 16)
-    if (wave_aa && c->tune.job_tasks >= 1 && c->tune.job_tasks * pt <= 64 && (c->tune.job_tasks * pt >= 16 || c->tune.job_tasks >= jt))
-      jt = c->tune.job_tasks;
-    if (big_chunks) jt = 16 * big_chunks;                      // jobs of 16 pixels
-    // job / nseg by one multiply-high (rt_device.h div_magic) is exact while (njobs - 1) * (magic * nseg - 2^32) < 2^32.
-    // Every accepted frame with jobs of 16+ pixels satisfies it; a knob that asks for smaller jobs is honoured only as far
-    // as the bound still holds (checked here, not assumed): the job is doubled until it does.
-    int job_pixels = 0;
-    for (;;) {
-      job_pixels = big_chunks ? jt / big_chunks : jt * pt;
-      P->nseg = (g.width + job_pixels - 1) / job_pixels;
-      P->njobs = P->nseg * c->owned_rows;
-      P->nseg_magic = div_magic_for(P->nseg);
-      if (big_chunks) break;                                     // 16-pixel jobs: within div_magic's bound for every accepted frame
-      const uint64_t err = P->nseg_magic ? (uint64_t)P->nseg_magic * (uint64_t)P->nseg - 0x100000000ull : 0ull;
-      if ((uint64_t)(P->njobs > 0 ? P->njobs - 1 : 0) * err < 0x100000000ull || 2 * jt * pt > 64) break;
-      jt *= 2;
-    }
-    P->job_tasks = jt;
-    P->no_specialise = c->tune.no_specialise ? 1 : 0;
-    P->l1_inflate = c->tune.l1_inflate;
-    P->job_hx = 0.5f * (float)(job_pixels * g.aa_x - 1);
-    P->job_hy = 0.5f * (float)(g.aa_y - 1) * P->sy;
-    for (int k = 0; k < 3; ++k)
-      P->job_eu[k] = 1.0001f * (fabsf(rot[4 * k]) * P->job_hx + fabsf(rot[4 * k + 1]) * P->job_hy);
+}
+
+// fill_params, part 2: the wave kernel's job layout — a job is a run of job_tasks 64-ray tasks (job_tasks * 64/aa pixels) of one row
+static void fill_wave_jobs(const rt_ctx* c, const float rot[12], FrameParams* P) {
+  const rt_config& g = c->cfg;
+  const int aa = g.aa_x * g.aa_y;
+  const bool wave_aa = aa >= 1 && aa <= 64;
+  const int big_chunks = aa > 64 ? (aa + 63) / 64 : 0;      // 65..256 AA samples: a pixel is big_chunks tasks (rt_kernel_wave.hip BIGAA)
+  // Job size: up to 64 pixels, halved while the queue would hold fewer than ~16 jobs per resident wave (jobs differ
+  // 10x in cost, but every hand-out stalls its wave for microseconds; measured with last frame's expensive jobs
+  // going first: 4096 and 2048 rows -> 64 px, 1024 and 512 rows -> 32 px), but not below 16 pixels.
+  const int pt = wave_aa ? 64 / aa : 64;              // pixels per 64-ray task
+  P->aa_magic = wave_aa ? (65536 + aa - 1) / aa : 65536;
+  P->aax_magic = (65536 + g.aa_x - 1) / g.aa_x;
+  // workgroups the chip holds at once; a rank of a multi-GPU job leaves one slot per CU free (registers and LDS
+  // for a workgroup of a collective's kernels), so that the gather of the previous frame can run beside it
+  const int per_cu = c->tune.grid_per_cu ? c->tune.grid_per_cu : wave_blocks_per_cu(g.band_count > 1 && !c->tune.full_grid);
+  P->wave_blocks = c->cus * per_cu;
+  const long waves = (long)P->wave_blocks * 4;
+  int jt = wave_aa ? 64 / pt : 1;                      // tasks of a 64-pixel job (aa for the power-of-two grids)
+  while (jt > 1 && ((jt + 1) / 2) * pt >= 16 && (long)((g.width + jt * pt - 1) / (jt * pt)) * c->owned_rows < 16 * waves) jt = (jt + 1) / 2;
+  // (the knob may not make a job smaller than 16 pixels: div_magic's exactness bound, rt_device.h, is stated for >= 16)
+  if (wave_aa && c->tune.job_tasks >= 1 && c->tune.job_tasks * pt <= 64 && (c->tune.job_tasks * pt >= 16 || c->tune.job_tasks >= jt))
+    jt = c->tune.job_tasks;
+  if (big_chunks) jt = 16 * big_chunks;                      // jobs of 16 pixels
+  // job / nseg by one multiply-high (rt_device.h div_magic) is exact while (njobs - 1) * (magic * nseg - 2^32) < 2^32.
+  // Every accepted frame with jobs of 16+ pixels satisfies it; a knob that asks for smaller jobs is honoured only as far
+  // as the bound still holds (checked here, not assumed): the job is doubled until it does.
+  int job_pixels = 0;
+  for (;;) {
+    job_pixels = big_chunks ? jt / big_chunks : jt * pt;
+    P->nseg = (g.width + job_pixels - 1) / job_pixels;
+    P->njobs = P->nseg * c->owned_rows;
+    P->nseg_magic = div_magic_for(P->nseg);
+    if (big_chunks) break;                                     // 16-pixel jobs: within div_magic's bound for every accepted frame
+    const uint64_t err = P->nseg_magic ? (uint64_t)P->nseg_magic * (uint64_t)P->nseg - 0x100000000ull : 0ull;
+    if ((uint64_t)(P->njobs > 0 ? P->njobs - 1 : 0) * err < 0x100000000ull || 2 * jt * pt > 64) break;
+    jt *= 2;
   }
-  if (c->d_screen_masks) {
-    P->screen_masks = c->d_screen_masks; P->world_masks = c->d_world_masks; P->world_occ = c->d_world_occ;
-    P->nwords = c->nwords; P->scx = c->scx; P->scy = c->scy; P->grid_g = kWorldGrid;
-    // World grid: a cube over the scene box, grown so that every shadow-ray start point X + 1e-4 (light - X)
-    // of a surface point X in the box (kernels.cl:324) stays inside, rounding included; X itself is computed
-    // from the camera (X = cam + t dir, or v0 + u e1 + v e2), so its rounding scales with the camera's and the
-    // scene's coordinates.
-    float ext = 0.0f, dmax = 0.0f, amax = 0.0f, cmax = 0.0f;
-    for (int k = 0; k < 3; ++k) {
-      ext = fmaxf(ext, c->box_hi[k] - c->box_lo[k]);
-      dmax = fmaxf(dmax, fmaxf(fabsf(light[k] - c->box_lo[k]), fabsf(light[k] - c->box_hi[k])));
-      amax = fmaxf(amax, fmaxf(fabsf(c->box_lo[k]), fabsf(c->box_hi[k])));
-      cmax = fmaxf(cmax, fabsf(cam[k]));
-    }
-    float grow = 2e-4f * dmax + 1e-4f * (amax + cmax) + 1e-3f * ext + 1e-30f;
-    // hit points on spheres can lie 2e-3 (|ray origin - centre| + R) off the sphere (rt_bin_occupancy): the grid holds them
-    for (int i = 0; i < g.num_spheres; ++i) {
-      float l2 = 0.0f;
-      for (int k = 0; k < 3; ++k) l2 += (cam[k] - g.spheres[i].center[k]) * (cam[k] - g.spheres[i].center[k]);
-      const float far = fmaxf(sqrtf(l2), 1.7321f * (ext + 2.0f * grow));
-      grow = fmaxf(grow, 2.5e-3f * (far + sqrtf(fmaxf(g.spheres[i].radius_sq, 0.0f))));
-    }
-    for (int k = 0; k < 3; ++k) P->grid_lo[k] = c->box_lo[k] - grow;
-    P->grid_cell = (ext + 2.0f * grow) / (float)kWorldGrid;
-    P->grid_inv = 1.0f / P->grid_cell;
+  P->job_tasks = jt;
+  P->no_specialise = c->tune.no_specialise ? 1 : 0;
+  P->l1_inflate = c->tune.l1_inflate;
+  P->job_hx = 0.5f * (float)(job_pixels * g.aa_x - 1);
+  P->job_hy = 0.5f * (float)(g.aa_y - 1) * P->sy;
+  for (int k = 0; k < 3; ++k)
+    P->job_eu[k] = 1.0001f * (fabsf(rot[4 * k]) * P->job_hx + fabsf(rot[4 * k + 1]) * P->job_hy);
+}
+
+// fill_params, part 3: the mesh kernel's tile masks and their world grid (a context that builds them: c->d_screen_masks)
+static void fill_world_grid(const rt_ctx* c, const float cam[3], const float light[3], FrameParams* P) {
+  const rt_config& g = c->cfg;
+  P->screen_masks = c->d_screen_masks; P->world_masks = c->d_world_masks; P->world_occ = c->d_world_occ;
+  P->nwords = c->nwords; P->scx = c->scx; P->scy = c->scy; P->grid_g = kWorldGrid;
+  // World grid: a cube over the scene box, grown so that every shadow-ray start point X + 1e-4 (light - X)
+  // of a surface point X in the box (kernels.cl:324) stays inside, rounding included; X itself is computed
+  // from the camera (X = cam + t dir, or v0 + u e1 + v e2), so its rounding scales with the camera's and the
+  // scene's coordinates.
+  float ext = 0.0f, dmax = 0.0f, amax = 0.0f, cmax = 0.0f;
+  for (int k = 0; k < 3; ++k) {
+    ext = fmaxf(ext, c->box_hi[k] - c->box_lo[k]);
+    dmax = fmaxf(dmax, fmaxf(fabsf(light[k] - c->box_lo[k]), fabsf(light[k] - c->box_hi[k])));
+    amax = fmaxf(amax, fmaxf(fabsf(c->box_lo[k]), fabsf(c->box_hi[k])));
+    cmax = fmaxf(cmax, fabsf(cam[k]));
   }
+  float grow = 2e-4f * dmax + 1e-4f * (amax + cmax) + 1e-3f * ext + 1e-30f;
+  // hit points on spheres can lie 2e-3 (|ray origin - centre| + R) off the sphere (rt_bin_occupancy): the grid holds them
+  for (int i = 0; i < g.num_spheres; ++i) {
+    float l2 = 0.0f;
+    for (int k = 0; k < 3; ++k) l2 += (cam[k] - g.spheres[i].center[k]) * (cam[k] - g.spheres[i].center[k]);
+    const float far = fmaxf(sqrtf(l2), 1.7321f * (ext + 2.0f * grow));
+    grow = fmaxf(grow, 2.5e-3f * (far + sqrtf(fmaxf(g.spheres[i].radius_sq, 0.0f))));
+  }
+  for (int k = 0; k < 3; ++k) P->grid_lo[k] = c->box_lo[k] - grow;
+  P->grid_cell = (ext + 2.0f * grow) / (float)kWorldGrid;
+  P->grid_inv = 1.0f / P->grid_cell;
+}
+
+void uobrt::fill_params(const rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal,
+                        FrameParams* P) {
+  memset(P, 0, sizeof *P);
+  fill_view_and_scene(c, rot, cam, light, focal, P);
+  fill_wave_jobs(c, rot, P);
+  if (c->d_screen_masks) fill_world_grid(c, cam, light, P);
 }
 
 // The mesh kernel works on the reordered copy of the scene (rt_scene.hip upload_tiled_scene)
@@ -360,6 +374,75 @@ void uobrt::scene_params(const rt_ctx* c, const float light[3], bool tiled, Fram
   const float zero3[3] = {0.f, 0.f, 0.f}, ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
   fill_params(c, ident, zero3, light, 1.0f, P);
   if (tiled) use_tiled_scene(c, P);
+}
+
+// ---- which kernel renders a frame ----------------------------------------------------------------------------------------
+// The ONE statement of it (DESIGN.md 4, table at its head), for launch_frame and rt_count_executed alike; which wave
+// instantiation is rt_kernel_wave.hip's (kWaveVariants).  It reads the context's working pointers through P (P.records), as
+// scene_select (rt_scene.hip) leaves them: a context made with RT_FLAG_GENERIC_KERNEL has no tiled copy to render from.
+enum class Family { wave, mesh, generic };
+
+static bool frame_cull(const rt_ctx* c) { return !(c->cfg.flags & RT_FLAG_NO_CULL); }
+
+static Family frame_family(const rt_ctx* c, const FrameParams& P) {
+  if (c->cfg.flags & RT_FLAG_GENERIC_KERNEL) return Family::generic;
+  // (more than 64 AA samples per pixel: the wave kernel's chunked instantiation exists with the cull only)
+  if (wave_kernel_supports(P) && (frame_cull(c) || P.aa_x * P.aa_y <= 64)) return Family::wave;
+  return frame_cull(c) && mesh_kernel_supports(P) ? Family::mesh : Family::generic;
+}
+
+// Wave kernel: last frame's expensive jobs first — where jobs are long enough (4+ tasks) for the extra look-up per
+// hand-out not to matter (measured: 1024^2 frames with 16-pixel jobs lose 12-18 % to it, larger ones gain 2-8 %)
+static void attach_heavy_lists(rt_ctx* c, FrameParams* P) {
+  if (!c->d_heavy_flags || P->job_tasks < 4) return;
+  const int prev = c->heavy_phase, cur = prev ^ 1;
+  unsigned int* const st[2] = {c->d_jobctr, c->d_jobctr + (2 * kJobHeads + 1) * kJobHeadStride};
+  P->heavy_prev = c->d_heavy[prev]; P->heavy_prev_state = st[prev];
+  P->heavy_new = c->d_heavy[cur]; P->heavy_new_state = st[cur];
+  P->heavy_flags = c->d_heavy_flags + (size_t)prev * c->heavy_jobs_max; P->heavy_flags_new = c->d_heavy_flags + (size_t)cur * c->heavy_jobs_max;
+  P->heavy_gen = ++c->heavy_gen;
+  P->heavy_factor4 = c->tune.heavy_factor4;                      // expensive = more than twice the average job
+  P->heavy_cap = P->njobs / 3 < c->heavy_cap ? P->njobs / 3 : c->heavy_cap;
+  P->heavy_dilate = c->tune.heavy_dilate ? 1 : 0;
+  c->heavy_phase = cur;
+}
+
+// Wave kernel, diagnostic (UOB_RT_TIMELINE): the shipped kernel, with its per-wave start / end stamps
+static int attach_timeline(rt_ctx* c, hipStream_t stream, FrameParams* P) {
+  c->timeline_valid = false;
+  if (!c->tune.timeline) return RT_OK;
+  const size_t waves = (size_t)P->wave_blocks * 4;
+  if (!c->d_timeline) {
+    if (c->d_timeline.alloc(waves * 3) != hipSuccess) { set_error("hipMalloc failed (timeline)"); return RT_E_NOMEM; }
+    c->timeline_waves = waves;
+  }
+  if (c->timeline_waves >= waves) {
+    HIP_TRY(hipMemsetAsync(c->d_timeline, 0, c->timeline_waves * 3 * sizeof(uint64_t), stream));
+    P->counters = reinterpret_cast<unsigned long long*>(c->d_timeline.p);
+    c->timeline_valid = true;
+  }
+  return RT_OK;
+}
+
+// Wave kernel, the tile seeds (rt_kernel_wave.hip rt_wave_seed): written from THIS frame's parameters in front of the draw
+// kernel on the caller's stream, every frame — view, light, scene and spheres may all have changed since the last one.  The
+// table is one more of the buffers a context's frames share: "one frame of a context at a time" orders its writers and
+// readers as it orders those of the queue heads and the expensive-job lists.
+static int attach_seeds(rt_ctx* c, const float rot[12], FrameParams* P) {
+  if (c->tune.no_seed || !wave_takes_seed(*P, frame_cull(c))) return RT_OK;
+  const int R = c->tune.seed_rows;
+  const int tile_rows = (P->H + R - 1) / R;
+  const size_t tiles = (size_t)tile_rows * (size_t)P->nseg;
+  if (c->seed_cap < tiles) {
+    if (c->d_seed.alloc(tiles) != hipSuccess) return alloc_failed();
+    c->seed_cap = tiles;
+  }
+  P->seed = c->d_seed; P->seed_rows = R; P->seed_tile_rows = tile_rows; P->seed_rows_magic = div_magic_for(R);
+  P->seed_hy = 0.5f * (float)(R * P->aa_y - 1) * P->sy;
+  for (int k = 0; k < 3; ++k) P->seed_eu[k] = 1.0001f * (fabsf(rot[4 * k]) * P->job_hx + fabsf(rot[4 * k + 1]) * P->seed_hy);
+  P->seed_kp_cap = c->tune.seed_kp; P->seed_caster_cap = c->tune.seed_casters; P->seed_keep_sph = c->tune.seed_sph ? 1 : 0;
+  c->seed_tile_rows = tile_rows; c->seed_nseg = P->nseg; c->seed_rows = R;
+  return RT_OK;
 }
 
 // One frame of a single-device context into d_argb (packed rows, or global rows when out_global) on `stream`
@@ -384,56 +467,15 @@ static int launch_frame(rt_ctx* c, const float rot[12], const float cam[3], cons
   HIP_TRY(wait_aov(c, stream));
   HIP_TRY(wait_scene(c, stream));          // before ev0: rt_last_kernel_ms times the frame's kernels only
   HIP_TRY(hipEventRecord(c->ev0, stream));
-  const bool wave_paths = !(c->cfg.flags & RT_FLAG_GENERIC_KERNEL);
-  c->seed_tile_rows = 0;                      // (set again below by a frame that takes the seed)
-  if (wave_paths && wave_kernel_supports(P) && (P.aa_x * P.aa_y <= 64 || !(c->cfg.flags & RT_FLAG_NO_CULL))) {
-    // last frame's expensive jobs first — where jobs are long enough (4+ tasks) for the extra look-up per
-    // hand-out not to matter (measured: 1024^2 frames with 16-pixel jobs lose 12-18 % to it, larger ones gain 2-8 %)
-    if (c->d_heavy_flags && P.job_tasks >= 4) {
-      const int prev = c->heavy_phase, cur = prev ^ 1;
-      unsigned int* const st[2] = {c->d_jobctr, c->d_jobctr + (2 * kJobHeads + 1) * kJobHeadStride};
-      P.heavy_prev = c->d_heavy[prev]; P.heavy_prev_state = st[prev];
-      P.heavy_new = c->d_heavy[cur]; P.heavy_new_state = st[cur];
-      P.heavy_flags = c->d_heavy_flags + (size_t)prev * c->heavy_jobs_max; P.heavy_flags_new = c->d_heavy_flags + (size_t)cur * c->heavy_jobs_max;
-      P.heavy_gen = ++c->heavy_gen;
-      P.heavy_factor4 = c->tune.heavy_factor4;                      // expensive = more than twice the average job
-      P.heavy_cap = P.njobs / 3 < c->heavy_cap ? P.njobs / 3 : c->heavy_cap;
-      P.heavy_dilate = c->tune.heavy_dilate ? 1 : 0;
-      c->heavy_phase = cur;
-    }
-    c->timeline_valid = false;
-    if (c->tune.timeline) {                 // diagnostic: the shipped kernel, with its per-wave start / end stamps
-      const size_t waves = (size_t)P.wave_blocks * 4;
-      if (!c->d_timeline) {
-        if (c->d_timeline.alloc(waves * 3) != hipSuccess) { set_error("hipMalloc failed (timeline)"); return RT_E_NOMEM; }
-        c->timeline_waves = waves;
-      }
-      if (c->timeline_waves >= waves) {
-        HIP_TRY(hipMemsetAsync(c->d_timeline, 0, c->timeline_waves * 3 * sizeof(uint64_t), stream));
-        P.counters = reinterpret_cast<unsigned long long*>(c->d_timeline.p);
-        c->timeline_valid = true;
-      }
-    }
-    // The tile seeds (rt_kernel_wave.hip rt_wave_seed): written from THIS frame's parameters in front of the draw kernel on
-    // the caller's stream, every frame — view, light, scene and spheres may all have changed since the last one.  The table
-    // is one more of the buffers a context's frames share: "one frame of a context at a time" above orders its writers and
-    // readers as it orders those of the queue heads and the expensive-job lists.
-    if (!c->tune.no_seed && wave_takes_seed(P, !(c->cfg.flags & RT_FLAG_NO_CULL))) {
-      const int R = c->tune.seed_rows;
-      const int tile_rows = (P.H + R - 1) / R;
-      const size_t tiles = (size_t)tile_rows * (size_t)P.nseg;
-      if (c->seed_cap < tiles) {
-        if (c->d_seed.alloc(tiles) != hipSuccess) return alloc_failed();
-        c->seed_cap = tiles;
-      }
-      P.seed = c->d_seed; P.seed_rows = R; P.seed_tile_rows = tile_rows; P.seed_rows_magic = div_magic_for(R);
-      P.seed_hy = 0.5f * (float)(R * P.aa_y - 1) * P.sy;
-      for (int k = 0; k < 3; ++k) P.seed_eu[k] = 1.0001f * (fabsf(rot[4 * k]) * P.job_hx + fabsf(rot[4 * k + 1]) * P.seed_hy);
-      P.seed_kp_cap = c->tune.seed_kp; P.seed_caster_cap = c->tune.seed_casters; P.seed_keep_sph = c->tune.seed_sph ? 1 : 0;
-      c->seed_tile_rows = tile_rows; c->seed_nseg = P.nseg; c->seed_rows = R;
-    }
-    launch_wave(P, !(c->cfg.flags & RT_FLAG_NO_CULL), false, stream);
-  } else if (wave_paths && !(c->cfg.flags & RT_FLAG_NO_CULL) && mesh_kernel_supports(P)) {
+  c->seed_tile_rows = 0;                      // (set again by a frame that takes the seed)
+  const Family family = frame_family(c, P);
+  if (family == Family::wave) {
+    attach_heavy_lists(c, &P);
+    int rc = attach_timeline(c, stream, &P);
+    if (rc == RT_OK) rc = attach_seeds(c, rot, &P);
+    if (rc != RT_OK) return rc;
+    launch_wave(P, frame_cull(c), false, false, stream);
+  } else if (family == Family::mesh) {
     use_tiled_scene(c, &P);
     if (c->d_mesh_cost) {                   // last frame's expensive blocks first; this frame's costs make the next order
       P.mesh_order = c->mesh_order_valid ? c->d_mesh_order : nullptr;
@@ -678,73 +720,55 @@ int rt_register_output(rt_ctx* c, void* host, size_t bytes) {
   return RT_OK;
 }
 
-int rt_count_work(rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal, rt_work* out) {
+// Both counting calls, on the context's own stream: rt_count_work's pass (the thread-per-pixel kernel, the reference's
+// semantics) or, `executed`, rt_count_executed's (the counting build of what renders the frame).  Behind what rewrites the
+// scene or shares the frames' buffers — the executed pass behind the previous frame too, whose queues and records it uses
+//  —, the counters cleared, the instrumented launch, the blocking read-back.  Several devices: the children's sum
+static int count_frame(rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal, bool executed,
+                       uint64_t out[8]) {
+  static_assert(sizeof(rt_work) == 8 * sizeof(uint64_t), "rt_work is eight counters");
   if (!c || !out || !rot || !cam || !light) { set_error("NULL argument"); return RT_E_INVALID; }
-  memset(out, 0, sizeof *out);
+  memset(out, 0, sizeof(rt_work));
   DeviceGuard guard;
-  if (!c->kids.empty()) {
-    for (rt_ctx* k : c->kids) {
-      rt_work w;
-      const int rc = rt_count_work(k, rot, cam, light, focal, &w);
-      if (rc != RT_OK) return rc;
-      for (size_t q = 0; q < sizeof(rt_work) / 8; ++q) ((uint64_t*)out)[q] += ((const uint64_t*)&w)[q];
-    }
-    return RT_OK;
+  for (rt_ctx* k : c->kids) {
+    uint64_t w[8];
+    const int rc = count_frame(k, rot, cam, light, focal, executed, w);
+    if (rc != RT_OK) return rc;
+    for (int q = 0; q < 8; ++q) out[q] += w[q];
   }
-  if (c->owned_rows == 0) return RT_OK;
+  if (!c->kids.empty() || c->owned_rows == 0) return RT_OK;
   FrameParams P;
   fill_params(c, rot, cam, light, focal, &P);
+  const Family family = executed ? frame_family(c, P) : Family::generic;
+  if (executed && (family == Family::generic || (family == Family::wave && !wave_can_count(P, frame_cull(c))))) {
+    // (two texts, as ever: the chunked build's frames are told of it, every other frame — one of more than 64 shadow samples
+    // on the wave kernel too — of rt_count_work)
+    set_error("%s", family == Family::wave && P.aa_x * P.aa_y > 64
+                  ? "rt_count_executed: more than 64 AA samples per pixel run on the wave kernel's chunked build, which has no counting build"
+                  : "rt_count_executed: this configuration runs on the generic kernel, whose executed work is rt_count_work");
+    return RT_E_UNSUPPORTED;
+  }
   P.counters = c->d_counters;
   HIP_TRY(hipSetDevice(c->device));
+  if (executed && c->timed) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev1, 0));
   HIP_TRY(wait_aov(c, c->stream));
   HIP_TRY(wait_scene(c, c->stream));
   HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt_work), c->stream));
-  launch_generic(P, true, c->stream);
+  if (family == Family::generic) launch_generic(P, true, c->stream);
+  else if (family == Family::wave) launch_wave(P, frame_cull(c), true, c->tune.phase_profile, c->stream);   // (phase_profile: s_memtime per phase)
+  else { use_tiled_scene(c, &P); launch_stage_records(P, c->stream); launch_mesh(P, true, c->tune.phase_profile, c->stream, nullptr, nullptr, nullptr); }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out, c->d_counters, sizeof(rt_work), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return RT_OK;
 }
 
+int rt_count_work(rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal, rt_work* out) {
+  return count_frame(c, rot, cam, light, focal, false, reinterpret_cast<uint64_t*>(out));
+}
+
 int rt_count_executed(rt_ctx* c, const float rot[12], const float cam[3], const float light[3], float focal, uint64_t out[8]) {
-  if (!c || !out || !rot || !cam || !light) { set_error("NULL argument"); return RT_E_INVALID; }
-  memset(out, 0, 8 * sizeof(uint64_t));
-  DeviceGuard guard;
-  if (!c->kids.empty()) {
-    for (rt_ctx* k : c->kids) {
-      uint64_t w[8];
-      const int rc = rt_count_executed(k, rot, cam, light, focal, w);
-      if (rc != RT_OK) return rc;
-      for (int q = 0; q < 8; ++q) out[q] += w[q];
-    }
-    return RT_OK;
-  }
-  if (c->owned_rows == 0) return RT_OK;
-  FrameParams P;
-  fill_params(c, rot, cam, light, focal, &P);
-  const bool generic = (c->cfg.flags & RT_FLAG_GENERIC_KERNEL) != 0;
-  const bool mesh = !generic && !wave_kernel_supports(P) && !(c->cfg.flags & RT_FLAG_NO_CULL) && mesh_kernel_supports(P);
-  if (generic || (!wave_kernel_supports(P) && !mesh) || (!mesh && P.S > 64)) {
-    set_error("rt_count_executed: this configuration runs on the generic kernel, whose executed work is rt_count_work");
-    return RT_E_UNSUPPORTED;
-  }
-  if (!mesh && P.aa_x * P.aa_y > 64) {
-    set_error("rt_count_executed: more than 64 AA samples per pixel run on the wave kernel's chunked build, which has no counting build");
-    return RT_E_UNSUPPORTED;
-  }
-  P.counters = c->d_counters;
-  HIP_TRY(hipSetDevice(c->device));
-  if (c->timed) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev1, 0));
-  HIP_TRY(wait_aov(c, c->stream));
-  HIP_TRY(wait_scene(c, c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt_work), c->stream));
-  if (mesh) { use_tiled_scene(c, &P); launch_stage_records(P, c->stream); launch_mesh(P, true, c->tune.phase_profile, c->stream, nullptr, nullptr, nullptr); }
-  else if (c->tune.phase_profile) launch_wave_prof(P, c->stream);   // diagnostic: s_memtime per phase
-  else launch_wave(P, !(c->cfg.flags & RT_FLAG_NO_CULL), true, c->stream);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, c->d_counters, sizeof(rt_work), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return RT_OK;
+  return count_frame(c, rot, cam, light, focal, true, out);
 }
 
 int rt_debug_wave_timeline(rt_ctx* c, uint64_t out[8]) {
@@ -773,70 +797,52 @@ int rt_debug_wave_timeline(rt_ctx* c, uint64_t out[8]) {
   return RT_OK;
 }
 
-// The last frame's seed table and, per tile, the rows of it the context renders (each of them is one job per column, and
-// every job reads its tile's record); an empty table when the last frame took no seed
-static int read_seed_table(rt_ctx* c, std::vector<SeedRec>* rec, std::vector<uint64_t>* rows) {
-  rec->clear(); rows->clear();
-  if (c->seed_tile_rows == 0) return RT_OK;
+// What both views of the last frame's seed table share: the argument check, dims, the table and per tile the rows of it the
+// context renders (each of them is one job per column, and every job reads its tile's record), `view` over every record with
+// its rows, the copy into the caller's array.  An empty table when the last frame took no seed
+static int seed_table_view(rt_ctx* c, void* records, int64_t cap, int32_t dims[3], uint64_t* counters, int ncounters,
+                           void (*view)(SeedRec& r, uint64_t rows, uint64_t* counters)) {
+  if (!c || !dims || !counters || cap < 0 || (cap > 0 && !records)) { set_error("NULL argument"); return RT_E_INVALID; }
+  c = lead_ctx(c);
+  dims[0] = c->seed_tile_rows; dims[1] = c->seed_nseg; dims[2] = c->seed_rows;
+  for (int q = 0; q < ncounters; ++q) counters[q] = 0;
+  if (c->seed_tile_rows == 0) { dims[1] = 0; return RT_OK; }
   DeviceGuard guard;
   HIP_TRY(hipSetDevice(c->device));
   if (c->timed) HIP_TRY(hipEventSynchronize(c->ev1));
-  rec->resize((size_t)c->seed_tile_rows * (size_t)c->seed_nseg);
-  HIP_TRY(hipMemcpy(rec->data(), c->d_seed, rec->size() * sizeof(SeedRec), hipMemcpyDeviceToHost));
+  std::vector<SeedRec> rec((size_t)c->seed_tile_rows * (size_t)c->seed_nseg);
+  HIP_TRY(hipMemcpy(rec.data(), c->d_seed, rec.size() * sizeof(SeedRec), hipMemcpyDeviceToHost));
   const rt_config& g = c->cfg;
-  rows->assign((size_t)c->seed_tile_rows, 0);
-  for (int tr = 0; tr < c->seed_tile_rows; ++tr)
+  for (int tr = 0; tr < c->seed_tile_rows; ++tr) {
+    uint64_t rows = 0;
     for (int y = tr * c->seed_rows; y < (tr + 1) * c->seed_rows && y < g.height; ++y)
-      (*rows)[tr] += ((y / g.band_rows) % g.band_count) == g.band_index;
+      rows += ((y / g.band_rows) % g.band_count) == g.band_index;
+    for (int col = 0; col < c->seed_nseg; ++col) view(rec[(size_t)tr * (size_t)c->seed_nseg + (size_t)col], rows, counters);
+  }
+  if (records) memcpy(records, rec.data(), (size_t)((int64_t)rec.size() < cap ? (int64_t)rec.size() : cap) * sizeof(SeedRec));
   return RT_OK;
 }
 
 // The strict view: the strict bits alone, and nothing of a part whose strict bit is not set
 int rt_debug_wave_seeds(rt_ctx* c, void* records, int64_t cap, int32_t dims[3], uint64_t counters[4]) {
-  if (!c || !dims || !counters || cap < 0 || (cap > 0 && !records)) { set_error("NULL argument"); return RT_E_INVALID; }
-  c = lead_ctx(c);
-  dims[0] = c->seed_tile_rows; dims[1] = c->seed_nseg; dims[2] = c->seed_rows;
-  for (int q = 0; q < 4; ++q) counters[q] = 0;
-  if (c->seed_tile_rows == 0) { dims[1] = 0; return RT_OK; }      // the last frame took no seed: an empty table
-  std::vector<SeedRec> rec;
-  std::vector<uint64_t> rows;
-  const int rc = read_seed_table(c, &rec, &rows);
-  if (rc != RT_OK) return rc;
-  for (size_t t = 0; t < rec.size(); ++t) {
-    SeedRec& r = rec[t];
+  return seed_table_view(c, records, cap, dims, counters, 4, [](SeedRec& r, uint64_t n, uint64_t* counters) {
     r.flags &= kSeedPrimary | kSeedShadow;
     if (!(r.flags & kSeedPrimary)) r.Kp = 0ull;
     if (!(r.flags & kSeedShadow)) { r.D0[0] = r.D0[1] = r.D0[2] = 0.0f; r.ed = 0.0f; r.K = 0ull; r.Kh = 0ull; r.h = -1; }
-    const uint64_t n = rows[t / (size_t)c->seed_nseg];
     if (r.flags & kSeedPrimary) { counters[0] += 1; counters[2] += n; }
     if (r.flags & kSeedShadow) { counters[1] += 1; counters[3] += n; }
-  }
-  if (records) memcpy(records, rec.data(), (size_t)((int64_t)rec.size() < cap ? (int64_t)rec.size() : cap) * sizeof(SeedRec));
-  return RT_OK;
+  });
 }
 
 // The records as the draw kernel reads them
 int rt_debug_wave_seeds_wide(rt_ctx* c, void* records, int64_t cap, int32_t dims[3], uint64_t counters[10]) {
-  if (!c || !dims || !counters || cap < 0 || (cap > 0 && !records)) { set_error("NULL argument"); return RT_E_INVALID; }
-  c = lead_ctx(c);
-  dims[0] = c->seed_tile_rows; dims[1] = c->seed_nseg; dims[2] = c->seed_rows;
-  for (int q = 0; q < 10; ++q) counters[q] = 0;
-  if (c->seed_tile_rows == 0) { dims[1] = 0; return RT_OK; }
-  std::vector<SeedRec> rec;
-  std::vector<uint64_t> rows;
-  const int rc = read_seed_table(c, &rec, &rows);
-  if (rc != RT_OK) return rc;
-  for (size_t t = 0; t < rec.size(); ++t) {
-    const SeedRec& r = rec[t];
-    const uint64_t n = rows[t / (size_t)c->seed_nseg];
+  return seed_table_view(c, records, cap, dims, counters, 10, [](SeedRec& r, uint64_t n, uint64_t* counters) {
     const bool shadow = (r.flags & kSeedShadowWide) != 0u;
     const bool is[5] = {(r.flags & kSeedPrimaryWide) != 0u, shadow, shadow && r.Kh != 0ull, shadow && (r.flags & kSeedShadowSph) != 0u,
                         shadow && (r.flags & kSeedShadowBlocked) != 0u};
     for (int q = 0; q < 5; ++q)
       if (is[q]) { counters[2 * q] += 1; counters[2 * q + 1] += n; }
-  }
-  if (records) memcpy(records, rec.data(), (size_t)((int64_t)rec.size() < cap ? (int64_t)rec.size() : cap) * sizeof(SeedRec));
-  return RT_OK;
+  });
 }
 
 int rt_debug_trace_rays(rt_ctx* c, int32_t what, const float* rays6, const float* radius_sq, int64_t nray,

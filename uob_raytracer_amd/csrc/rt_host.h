@@ -41,10 +41,10 @@ void launch_stage_records(const FrameParams& P, hipStream_t stream);
 void launch_trace_rays(const FrameParams& P, int what, const float* d_rays, const float* d_r2, long nray, int* d_tri,
                        float* d_out10, hipStream_t stream);
 // rt_kernel_wave.hip
-void launch_wave(const FrameParams& P, bool cull, bool count, hipStream_t stream);
-void launch_wave_prof(const FrameParams& P, hipStream_t stream);
+void launch_wave(const FrameParams& P, bool cull, bool count, bool prof, hipStream_t stream);
 bool wave_kernel_supports(const FrameParams& P);
 bool wave_takes_seed(const FrameParams& P, bool cull);
+bool wave_can_count(const FrameParams& P, bool cull);
 int wave_blocks_per_cu(bool leave_room);
 // rt_kernel_mesh.hip
 void launch_mesh(const FrameParams& P, bool count, bool prof, hipStream_t stream, hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join);

@@ -39,6 +39,7 @@
 #include "rt_wave_common.h"
 
 #include <type_traits>
+#include <utility>
 
 namespace uobrt {
 
@@ -333,8 +334,32 @@ __host__ __device__ constexpr int wave_fixed_lds_float4() {
 // worked off in chunks of 64 — a task is one chunk of ONE pixel, a job's tasks run pixel by pixel, chunk by chunk, and the
 // pixel's running sum (final_color_total +=, :415-425, in sample order) is carried from chunk to chunk.
 // PROF: per-phase s_memtime shares (RT_STAMP), summed over waves, in counters[0..7]
+//
+// WaveVariant: one instantiation, by the kernel's template arguments in their order and with their defaults.  Whatever follows from them is a function
+// of it, stated here once: the kernel reads them of itself (`me`), the host of the variant it chose (kWaveVariants below).
+struct WaveVariant {
+  bool cull, count, prof = false; int stride = 0; bool multi = false; int aa_x = 0, aa_y = 0, ss = 0; bool bigaa = false;
+};
+// the task's wave-uniform tests as bits of one scalar register (rt_draw_wave, MASKS)
+__host__ __device__ constexpr bool masks(WaveVariant v) { return !(v.ss > 0 && v.ss < 32) && (v.stride != 0 || v.bigaa || v.count); }
+// a job starts from its screen tile's record (rt_draw_wave, SEED): the (4x2, 64) instantiation alone
+__host__ __device__ constexpr bool takes_seed(WaveVariant v) {
+  return v.cull && !v.count && !v.prof && masks(v) && v.stride == 32 && v.aa_x == 4 && v.aa_y == 2 && v.ss == 64 && !v.multi && !v.bigaa;
+}
+// level 3 with lane = (surface point, sample): the most samples of a frame that takes it, 0 where none does — the
+// instantiations specialised on up to 32 samples, and the static-layout generic one with up to 16
+__host__ __device__ constexpr int packed_level3_samples(WaveVariant v) {
+  return !v.cull || v.count || v.multi ? 0 : v.ss > 0 ? (v.ss <= 32 ? 32 : 0) : (v.stride == 32 && !v.bigaa ? 16 : 0);
+}
+// the whole LDS layout is static: the launch asks for no dynamic LDS
+__host__ __device__ constexpr bool static_lds(WaveVariant v) { return v.stride != 0; }
+// rt_count_executed can count the frames this variant renders: the counting builds take up to 64 sample lanes in one pass
+// and up to 64 AA samples per pixel
+__host__ __device__ constexpr bool has_counting_build(WaveVariant v) { return !v.multi && !v.bigaa; }
+
 template <bool CULL, bool COUNT, bool PROF = false, int STRIDE = 0, bool MULTI = false, int AA_X = 0, int AA_Y = 0, int SS = 0, bool BIGAA = false>
 __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(const FrameParams P) {
+  constexpr WaveVariant me{CULL, COUNT, PROF, STRIDE, MULTI, AA_X, AA_Y, SS, BIGAA};
   unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tlast = PROF ? __builtin_amdgcn_s_memtime() : 0ull;
   extern __shared__ float4 lds_dyn[];
@@ -505,7 +530,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
   // (profiles/wave_masks_ab.txt).  Those keep the three bools and the reduction, instruction for instruction.  The counting
   // build, which is never timed, takes the new form: its counters are what tests/test_gpu_wave_masks.py holds against the
   // parent's.
-  constexpr bool MASKS = !(SS > 0 && SS < 32) && (STRIDE != 0 || BIGAA || COUNT);
+  constexpr bool MASKS = masks(me);
   constexpr int kJkValid = 1, kJkSph = 2, kJkBlocked = 4;
   int jk_flags = 0;
   bool jk_valid = false, jk_sph = false, jk_blocked = false;
@@ -529,7 +554,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
   // nothing downstream knows where jk_* came from.  One wave-uniform load per job through the scalar cache (the table
   // is written by the launch in front of this one and read-only here).  The (4x2, 64) instantiation alone, like MASKS a
   // compile-time condition: the others hold the code they held.
-  constexpr bool SEED = CULL && !COUNT && !PROF && MASKS && STRIDE == 32 && AA_X == 4 && AA_Y == 2 && SS == 64 && !MULTI && !BIGAA;
+  constexpr bool SEED = takes_seed(me);
+  constexpr int PACKED3 = packed_level3_samples(me);
   bool seeded = false;
   if (SEED && PC(seed) != nullptr) {
     const int trow = (int)div_magic((uint32_t)y, PC(seed_rows_magic));
@@ -797,7 +823,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
       }
       wave_lds_sync();
       RT_STAMP(prof, 4)                     // 4: xorshift streams
-      if (CULL && !COUNT && !MULTI && ((SS > 0 && SS <= 32) || (SS == 0 && STRIDE == 32 && !BIGAA && NS <= 16))) {
+      if (PACKED3 != 0 && NS <= PACKED3) {
         // few samples: lane = (surface point, sample), 64 / SP points of one pixel per instance, two instances per pass
         // (the instantiations specialised on the sample count; the static-layout generic one for up to 16 samples)
         constexpr int SP = (SS > 16) ? 32 : 16, PK = 64 / SP;
@@ -933,21 +959,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, kMinWaves) void rt_draw_wave(c
     if (lane == 0) for (int q = 0; q < 8; ++q) if (xw.v[q]) atomicAdd(&PC(counters)[q], xw.v[q]);
   }
 }
-
-template __global__ void rt_draw_wave<false, false>(const FrameParams);
-template __global__ void rt_draw_wave<true, false>(const FrameParams);
-template __global__ void rt_draw_wave<false, true>(const FrameParams);
-template __global__ void rt_draw_wave<true, true>(const FrameParams);
-template __global__ void rt_draw_wave<true, false, true>(const FrameParams);
-template __global__ void rt_draw_wave<true, false, false, 32>(const FrameParams);
-template __global__ void rt_draw_wave<true, false, false, 0, true>(const FrameParams);
-// specialised on (AA grid, samples): BASELINE.json's configurations and the reference as shipped
-template __global__ void rt_draw_wave<true, false, false, 32, false, 4, 2, 64>(const FrameParams);   // the headline frame
-template __global__ void rt_draw_wave<true, false, false, 32, false, 2, 2, 64>(const FrameParams);
-template __global__ void rt_draw_wave<true, false, false, 32, false, 2, 2, 16>(const FrameParams);   // configs[1]
-template __global__ void rt_draw_wave<true, false, false, 32, false, 2, 2, 10>(const FrameParams);   // the reference's own constants, configs[2]
-template __global__ void rt_draw_wave<false, false, false, 0, true>(const FrameParams);
-template __global__ void rt_draw_wave<true, false, false, 0, false, 0, 0, 0, true>(const FrameParams);   // 65..256 AA samples per pixel
 
 // ---- the tile seeds ------------------------------------------------------------------------------------------------
 // One wave per screen tile (P.seed_rows rows of one job column), lane = triangle / caster throughout, in a loop over the
@@ -1085,14 +1096,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void rt_wave_seed(const FrameP
   }
 }
 
-// Does the frame take the seed?  launch_wave's own choice of instantiation (rt_draw_wave, SEED), asked by the host before it
-// sizes the table — and jobs of eight tasks, 64 pixels: the shorter jobs of frames with few rows (32 pixels from 1024 rows per
-// rank down) have half as many level 1s to save per tile and twice the tiles, and one rank's 512 rows of an 8-rank split ran
-// 3 % SLOWER with the pre-pass in front (0.447 -> 0.463 ms, profiles/tile_seed_ab.txt).  They start every job unseeded.
-bool wave_takes_seed(const FrameParams& P, bool cull) {
-  return cull && P.n <= 32 && !P.no_specialise && P.aa_x == 4 && P.aa_y == 2 && P.S == 64 && P.job_tasks == 8;
-}
-
 bool wave_kernel_supports(const FrameParams& P) {
   const int aa = P.aa_x * P.aa_y;
   // (more than 64 AA samples per pixel: the chunked instantiation exists for <= 64 shadow samples, with the cull)
@@ -1107,29 +1110,83 @@ static size_t wave_kernel_lds(const FrameParams& P, bool cull) {
 
 int wave_blocks_per_cu(bool leave_room) { return leave_room ? kMinWaves - 1 : kMinWaves; }
 
-static dim3 wave_grid(const FrameParams& P) {
+// The persistent grid for `items` pieces of work, one per wave: what the device holds at once, or fewer
+static dim3 wave_grid(const FrameParams& P, int items) {
   const int resident = P.wave_blocks > 0 ? P.wave_blocks : 256 * kMinWaves;     // set per device by the host API
-  const int needed = (P.njobs + kWavesPerBlock - 1) / kWavesPerBlock;
-  return dim3(needed < resident ? (needed > 0 ? needed : 1) : resident);
+  return dim3(grid_blocks((items + kWavesPerBlock - 1) / kWavesPerBlock, resident));
 }
 
-void launch_wave_prof(const FrameParams& P, hipStream_t stream) {
-  hipMemsetAsync(P.job_counter, 0, 2 * kJobHeads * kJobHeadStride * sizeof(unsigned int), stream);
-  hipLaunchKernelGGL((rt_draw_wave<true, false, true>), wave_grid(P), dim3(64 * kWavesPerBlock), wave_kernel_lds(P, true), stream, P);
+// ---- which instantiation renders a frame ---------------------------------------------------------------------------
+// What a caller wants of the frame P: the cull (not RT_FLAG_NO_CULL); rt_count_executed's counting build, or its per-phase
+// profile.  (Callers ask for a count only where has_counting_build holds of the frame's own variant, and render more than 64
+// AA samples per pixel only with the cull: launch_frame, rt_count_executed.)
+struct WaveAsk { bool cull, count, prof; };
+using WavePred = bool (*)(const WaveVariant& v, const FrameParams& P, WaveAsk a);
+
+static bool ask_prof(const WaveVariant&, const FrameParams&, WaveAsk a) { return a.prof; }
+static bool ask_bigaa(const WaveVariant&, const FrameParams& P, WaveAsk) { return P.aa_x * P.aa_y > 64; }
+static bool ask_count(const WaveVariant& v, const FrameParams&, WaveAsk a) { return a.count && a.cull == v.cull; }
+static bool ask_multi(const WaveVariant& v, const FrameParams& P, WaveAsk a) { return P.S > 64 && a.cull == v.cull; }
+// specialised on (AA grid, samples): BASELINE.json's configurations and the reference as shipped
+static bool ask_specialised(const WaveVariant& v, const FrameParams& P, WaveAsk a) {
+  return a.cull && P.n <= v.stride && !P.no_specialise && P.aa_x == v.aa_x && P.aa_y == v.aa_y && P.S == v.ss;
+}
+static bool ask_generic(const WaveVariant& v, const FrameParams& P, WaveAsk a) { return a.cull == v.cull && (!static_lds(v) || P.n <= v.stride); }
+
+// Every instantiation of rt_draw_wave there is, each with the question that selects it; the FIRST entry whose answer is yes
+// renders the frame (wave_choose).  The last one takes whatever is left.
+struct WaveEntry { WaveVariant v; WavePred pred; };
+constexpr WaveEntry kWaveVariants[] = {
+    {{true, false, true}, ask_prof},
+    {{true, false, false, 0, false, 0, 0, 0, true}, ask_bigaa},          // 65..256 AA samples per pixel
+    {{true, true}, ask_count},
+    {{false, true}, ask_count},
+    {{true, false, false, 0, true}, ask_multi},
+    {{false, false, false, 0, true}, ask_multi},
+    {{true, false, false, 32, false, 4, 2, 64}, ask_specialised},        // the headline frame
+    {{true, false, false, 32, false, 2, 2, 64}, ask_specialised},
+    {{true, false, false, 32, false, 2, 2, 16}, ask_specialised},        // configs[1]
+    {{true, false, false, 32, false, 2, 2, 10}, ask_specialised},        // the reference's own constants, configs[2]
+    {{true, false, false, 32}, ask_generic},
+    {{true, false}, ask_generic},
+    {{false, false}, ask_generic},
+};
+constexpr size_t kNumWaveVariants = sizeof kWaveVariants / sizeof kWaveVariants[0];
+
+static size_t wave_choose(const FrameParams& P, WaveAsk a) {
+  size_t i = 0;
+  while (i + 1 < kNumWaveVariants && !kWaveVariants[i].pred(kWaveVariants[i].v, P, a)) ++i;
+  return i;
+}
+// the variant that renders the frame itself
+static const WaveVariant& wave_frame_variant(const FrameParams& P, bool cull) { return kWaveVariants[wave_choose(P, {cull, false, false})].v; }
+
+// The instantiation of entry I: the table's fields in the order of the kernel's template parameters
+template <size_t I>
+static void launch_variant(const FrameParams& P, dim3 grid, hipStream_t stream) {
+  constexpr WaveVariant v = kWaveVariants[I].v;
+  hipLaunchKernelGGL((rt_draw_wave<v.cull, v.count, v.prof, v.stride, v.multi, v.aa_x, v.aa_y, v.ss, v.bigaa>), grid,
+                     dim3(64 * kWavesPerBlock), static_lds(v) ? 0 : wave_kernel_lds(P, v.cull), stream, P);
+}
+template <size_t... I>
+static void launch_chosen(size_t i, const FrameParams& P, dim3 grid, hipStream_t stream, std::index_sequence<I...>) {
+  ((i == I ? launch_variant<I>(P, grid, stream) : void()), ...);
 }
 
-void launch_wave(const FrameParams& P, bool cull, bool count, hipStream_t stream) {
-  const dim3 block(64 * kWavesPerBlock);
-  const dim3 grid = wave_grid(P);
-  const size_t lds_bytes = wave_kernel_lds(P, cull);
+// Does the frame take the seed?  Asked by the host before it sizes the table: the variant that will render the frame does
+// (takes_seed) — and jobs of eight tasks, 64 pixels: the shorter jobs of frames with few rows (32 pixels from 1024 rows per
+// rank down) have half as many level 1s to save per tile and twice the tiles, and one rank's 512 rows of an 8-rank split ran
+// 3 % SLOWER with the pre-pass in front (0.447 -> 0.463 ms, profiles/tile_seed_ab.txt).  They start every job unseeded.
+bool wave_takes_seed(const FrameParams& P, bool cull) { return takes_seed(wave_frame_variant(P, cull)) && P.job_tasks == 8; }
+
+// Has the variant that renders the frame a counting build (rt_count_executed)?
+bool wave_can_count(const FrameParams& P, bool cull) { return has_counting_build(wave_frame_variant(P, cull)); }
+
+void launch_wave(const FrameParams& P, bool cull, bool count, bool prof, hipStream_t stream) {
   // the tile seeds of this frame, directly in front of the draw kernel that reads them (the host sets P.seed only where
   // wave_takes_seed holds and the table has room)
-  if (P.seed != nullptr && !count) {
-    const int tiles = P.seed_tile_rows * P.nseg;
-    const int want = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int room = P.wave_blocks > 0 ? P.wave_blocks : 256 * kMinWaves;
-    hipLaunchKernelGGL(rt_wave_seed, dim3(want < room ? (want > 0 ? want : 1) : room), block, wave_kernel_lds(P, true) , stream, P);
-  }
+  if (P.seed != nullptr && !count)
+    hipLaunchKernelGGL(rt_wave_seed, wave_grid(P, P.seed_tile_rows * P.nseg), dim3(64 * kWavesPerBlock), wave_kernel_lds(P, true), stream, P);
   // one memset: the queue heads, and this frame's HeavyState, which lies directly before or behind them
   const size_t heads_bytes = 2 * kJobHeads * kJobHeadStride * sizeof(unsigned int), state_bytes = kJobHeadStride * sizeof(unsigned int);
   if (P.heavy_new != nullptr && !count) {
@@ -1138,24 +1195,7 @@ void launch_wave(const FrameParams& P, bool cull, bool count, hipStream_t stream
   } else {
     hipMemsetAsync(P.job_counter, 0, heads_bytes, stream);
   }
-  if (P.aa_x * P.aa_y > 64) {               // (callers: cull on, no counting — launch_frame / rt_count_executed check)
-    hipLaunchKernelGGL((rt_draw_wave<true, false, false, 0, false, 0, 0, 0, true>), grid, block, lds_bytes, stream, P);
-  } else if (count) {
-    if (cull) hipLaunchKernelGGL((rt_draw_wave<true, true>), grid, block, lds_bytes, stream, P);
-    else hipLaunchKernelGGL((rt_draw_wave<false, true>), grid, block, lds_bytes, stream, P);
-  } else if (P.S > 64) {
-    if (cull) hipLaunchKernelGGL((rt_draw_wave<true, false, false, 0, true>), grid, block, lds_bytes, stream, P);
-    else hipLaunchKernelGGL((rt_draw_wave<false, false, false, 0, true>), grid, block, lds_bytes, stream, P);
-  } else {
-    const bool spec = cull && P.n <= 32 && !P.no_specialise;
-    if (spec && P.aa_x == 4 && P.aa_y == 2 && P.S == 64) hipLaunchKernelGGL((rt_draw_wave<true, false, false, 32, false, 4, 2, 64>), grid, block, 0, stream, P);
-    else if (spec && P.aa_x == 2 && P.aa_y == 2 && P.S == 64) hipLaunchKernelGGL((rt_draw_wave<true, false, false, 32, false, 2, 2, 64>), grid, block, 0, stream, P);
-    else if (spec && P.aa_x == 2 && P.aa_y == 2 && P.S == 16) hipLaunchKernelGGL((rt_draw_wave<true, false, false, 32, false, 2, 2, 16>), grid, block, 0, stream, P);
-    else if (spec && P.aa_x == 2 && P.aa_y == 2 && P.S == 10) hipLaunchKernelGGL((rt_draw_wave<true, false, false, 32, false, 2, 2, 10>), grid, block, 0, stream, P);
-    else if (cull && P.n <= 32) hipLaunchKernelGGL((rt_draw_wave<true, false, false, 32>), grid, block, 0, stream, P);
-    else if (cull) hipLaunchKernelGGL((rt_draw_wave<true, false>), grid, block, lds_bytes, stream, P);
-    else hipLaunchKernelGGL((rt_draw_wave<false, false>), grid, block, lds_bytes, stream, P);
-  }
+  launch_chosen(wave_choose(P, {cull, count, prof}), P, wave_grid(P, P.njobs), stream, std::make_index_sequence<kNumWaveVariants>{});
 }
 
 }  // namespace uobrt
