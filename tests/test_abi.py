@@ -29,18 +29,26 @@ def test_every_declared_symbol_is_exported():
     assert sorted(rt.EXPORTS) == names       # the binding covers exactly the header
 
 
+# the structs the header's functions name, and their ctypes mirrors
+STRUCTS = {"rt_config": abi.RtConfig, "rt_sphere": abi.RtSphere, "rt_work": abi.RtWork, "rt_triangle": abi.RtTriangle,
+           "rt_band_copy": abi.RtBandCopy, "rt_aov_buffers": abi.RtAovBuffers, "rt_filter_params": abi.RtFilterParams,
+           "rt_accumulate_params": abi.RtAccumulateParams, "rt_history_texel": abi.RtHistoryTexel}
+
+
 def test_struct_layouts_match_the_header(tmp_path):
     prog = tmp_path / "sz.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "uob_rt.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n",'
-                    'sizeof(rt_config),sizeof(rt_sphere),sizeof(rt_work),sizeof(rt_triangle),'
+    sizes = "".join('printf("%%zu\\n",sizeof(%s));' % name for name in STRUCTS)
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "uob_rt.h"\nint main(){' + sizes +
+                    'printf("%zu %zu %zu %zu\\n",'
                     'offsetof(rt_config,spheres),offsetof(rt_config,band_rows),offsetof(rt_config,devices),'
                     'offsetof(rt_config,device_band_rows));return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    assert [int(x) for x in out] == [C.sizeof(abi.RtConfig), C.sizeof(abi.RtSphere), C.sizeof(abi.RtWork),
-                                     C.sizeof(abi.RtTriangle), abi.RtConfig.spheres.offset, abi.RtConfig.band_rows.offset,
-                                     abi.RtConfig.devices.offset, abi.RtConfig.device_band_rows.offset]
+    assert len(STRUCTS) == 9 and {C.sizeof(t) for t in STRUCTS.values()} != {0}
+    assert [int(x) for x in out] == [C.sizeof(t) for t in STRUCTS.values()] + [
+        abi.RtConfig.spheres.offset, abi.RtConfig.band_rows.offset, abi.RtConfig.devices.offset,
+        abi.RtConfig.device_band_rows.offset]
 
 
 def test_default_config_is_the_reference_constants():

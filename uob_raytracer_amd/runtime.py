@@ -182,6 +182,20 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+
+
+def _rays6(a):
+    """Caller rays (or points with normals) as a C-contiguous float32 [k, 6] array."""
+    return np.ascontiguousarray(a, np.float32).reshape(-1, 6)
+
+
+def _light3(a):
+    """The light position as the library takes it: a float32 [3] array of its own."""
+    return np.ascontiguousarray(a, np.float32)[:3].copy()
+
+
 def _need(name, t, dtype, shape, dev):
     """A tensor argument of a *_device method: a contiguous torch tensor of that dtype and shape on the context's device."""
     if not isinstance(t, _torch.Tensor):
@@ -189,6 +203,33 @@ def _need(name, t, dtype, shape, dev):
     if t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
         raise ValueError("%s must be a contiguous %s tensor of shape %s on %s (got %s %s on %s)"
                          % (name, dtype, shape, dev, t.dtype, tuple(t.shape), t.device))
+
+
+def _out(name, t, dtype, shape, dev):
+    """An output tensor of a *_device method: allocated when None, and a tensor argument like any other (_need)."""
+    if t is None:
+        t = _torch.empty(shape, dtype=dtype, device=dev)
+    _need(name, t, dtype, shape, dev)
+    return t
+
+
+def _rows(name, t, cols, dev):
+    """The k of a float32 [k, cols] input tensor of a *_device method (_need)."""
+    if not isinstance(t, _torch.Tensor) or t.dim() != 2:
+        raise ValueError("%s must be a torch tensor of shape [k, %d]" % (name, cols))
+    _need(name, t, _torch.float32, (t.shape[0], cols), dev)
+    return t.shape[0]
+
+
+def _guide_tensors(value, position4, normal4, dev):
+    """The input planes of a filter or accumulate call on the device: value float32 [h, w], the guides [h, w, 4] -> (h, w)."""
+    if not isinstance(value, _torch.Tensor) or value.dim() != 2:
+        raise ValueError("value must be a torch tensor of shape [height, width]")
+    h, w = value.shape
+    _need("value", value, _torch.float32, (h, w), dev)
+    _need("position4", position4, _torch.float32, (h, w, 4), dev)
+    _need("normal4", normal4, _torch.float32, (h, w, 4), dev)
+    return h, w
 
 
 def _seeds_ptr(seeds, k, what):
@@ -245,9 +286,8 @@ def selftest_shade(ns, lit, secondary, unshadowed, term, col, straight_line=Fals
     term = np.ascontiguousarray(term, np.float32).reshape(w, 64)
     col = np.ascontiguousarray(col, np.float32).reshape(w, 64, 4)
     out = np.zeros((w, 64, 3), np.float32)
-    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-    _check(lib().rt_selftest_shade(w, ip(ns), ip(ints[0]), ip(ints[1]), ip(ints[2]), _fp(term), _fp(col), int(bool(straight_line)),
-                                   _fp(out)))
+    _check(lib().rt_selftest_shade(w, _ip(ns), _ip(ints[0]), _ip(ints[1]), _ip(ints[2]), _fp(term), _fp(col),
+                                   int(bool(straight_line)), _fp(out)))
     return out
 
 
@@ -259,8 +299,7 @@ def selftest_all_within(lane_in, v, bound):
     lane_in = np.ascontiguousarray(lane_in, np.int32).reshape(w, 64)
     v = np.ascontiguousarray(v, np.float32).reshape(w, 64)
     out = np.zeros((w, 2), np.int32)
-    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-    _check(lib().rt_selftest_all_within(w, ip(lane_in), _fp(v), _fp(bound), ip(out)))
+    _check(lib().rt_selftest_all_within(w, _ip(lane_in), _fp(v), _fp(bound), _ip(out)))
     return out[:, 0] != 0, out[:, 1] != 0
 
 
@@ -274,19 +313,26 @@ def filter_params(width, height, passes=None, normal_min_dot=None, plane_eps=Non
     return p
 
 
-def _filter_host_planes(value, position4, normal4, out):
-    """The numpy planes of a blocking filter call: value float32 [h, w], the guides [h, w, 4]; out None, `value` itself (in
-    place) or another C-contiguous float32 [h, w] array."""
+def _host_planes(value, position4, normal4):
+    """The input planes of a blocking filter or accumulate call: value a numpy [h, w] array, the guides [h, w, 4] -> (h, w,
+    and the three as C-contiguous float32 arrays)."""
     if not isinstance(value, np.ndarray) or value.ndim != 2:
         raise ValueError("value must be a numpy array of shape [height, width]")
     h, w = value.shape
-    if out is value and not (value.dtype == np.float32 and value.flags.c_contiguous and value.flags.writeable):
-        raise ValueError("in place, value must be a writeable C-contiguous float32 array")
     v = np.ascontiguousarray(value, np.float32)
     pos = np.ascontiguousarray(position4, np.float32)
     nrm = np.ascontiguousarray(normal4, np.float32)
     if pos.shape != (h, w, 4) or nrm.shape != (h, w, 4):
         raise ValueError("position4 and normal4 must have the shape [%d, %d, 4]" % (h, w))
+    return h, w, v, pos, nrm
+
+
+def _filter_host_planes(value, position4, normal4, out):
+    """The numpy planes of a blocking filter call: _host_planes' inputs; out None, `value` itself (in place) or another
+    C-contiguous float32 [h, w] array."""
+    h, w, v, pos, nrm = _host_planes(value, position4, normal4)
+    if out is value and not (value.dtype == np.float32 and value.flags.c_contiguous and value.flags.writeable):
+        raise ValueError("in place, value must be a writeable C-contiguous float32 array")
     if out is None:
         out = np.empty((h, w), np.float32)
     elif out is value:
@@ -328,16 +374,9 @@ def accumulate_params(width, height, prev_rot=None, prev_cam=None, prev_focal=No
 
 
 def _accumulate_host_planes(value, position4, normal4, prim, prev):
-    """The numpy planes of a blocking accumulate call: value float32 [h, w], the guides [h, w, 4], prim int32 [h, w] or None,
-    prev float32 [h, w, 12] (abi.HISTORY_WORDS) or None; and fresh next / out_mean / out_variance."""
-    if not isinstance(value, np.ndarray) or value.ndim != 2:
-        raise ValueError("value must be a numpy array of shape [height, width]")
-    h, w = value.shape
-    v = np.ascontiguousarray(value, np.float32)
-    pos = np.ascontiguousarray(position4, np.float32)
-    nrm = np.ascontiguousarray(normal4, np.float32)
-    if pos.shape != (h, w, 4) or nrm.shape != (h, w, 4):
-        raise ValueError("position4 and normal4 must have the shape [%d, %d, 4]" % (h, w))
+    """The numpy planes of a blocking accumulate call: _host_planes' inputs, prim int32 [h, w] or None, prev float32
+    [h, w, 12] (abi.HISTORY_WORDS) or None; and fresh next / out_mean / out_variance."""
+    h, w, v, pos, nrm = _host_planes(value, position4, normal4)
     if prim is not None:
         prim = np.ascontiguousarray(prim, np.int32)
         if prim.shape != (h, w):
@@ -348,10 +387,6 @@ def _accumulate_host_planes(value, position4, normal4, prim, prev):
         prev = np.ascontiguousarray(prev)
     nxt = np.empty((h, w, abi.HISTORY_WORDS), np.float32)
     return h, w, v, pos, nrm, prim, prev, nxt, np.empty((h, w), np.float32), np.empty((h, w), np.float32)
-
-
-def _ip(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
 
 
 def accumulate_plane_host(value, position4, normal4, prim=None, prev=None, params=None, **kw):
@@ -576,8 +611,7 @@ class RayTracer:
         ranges = _object_ranges(ranges or (), self.n_triangles)
         first = np.asarray([r[0] for r in ranges], np.int32)
         count = np.asarray([r[1] for r in ranges], np.int32)
-        ip = C.POINTER(C.c_int32)
-        _check(lib().rt_set_objects(self._h, first.ctypes.data_as(ip), count.ctypes.data_as(ip), len(ranges)))
+        _check(lib().rt_set_objects(self._h, _ip(first), _ip(count), len(ranges)))
         self.objects = ranges or None
         if ranges:
             self.skin = None
@@ -680,7 +714,7 @@ class RayTracer:
         nt = _check(lib().rt_debug_tile_data(self._h, None, None, 0))
         orig = np.zeros(self.n_triangles, np.int32)
         tiles = np.zeros((nt, 12), np.float32)
-        _check(lib().rt_debug_tile_data(self._h, orig.ctypes.data_as(C.POINTER(C.c_int32)), _fp(tiles), nt))
+        _check(lib().rt_debug_tile_data(self._h, _ip(orig), _fp(tiles), nt))
         return orig, tiles
 
     def scene_data(self, tiled=False):
@@ -782,42 +816,38 @@ class RayTracer:
 
     def trace_in_shadow(self, rays, radius_sq):
         """Device in_shadow (kernels.cl:243) on caller rays [k,6] = start, direction -> uint8 [k]."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        rays = _rays6(rays)
         r2 = np.ascontiguousarray(radius_sq, np.float32)
         out = np.zeros(rays.shape[0], np.int32)
-        _check(lib().rt_debug_trace_rays(self._h, abi.RT_TRACE_IN_SHADOW, _fp(rays), _fp(r2), rays.shape[0],
-                                         out.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        _check(lib().rt_debug_trace_rays(self._h, abi.RT_TRACE_IN_SHADOW, _fp(rays), _fp(r2), rays.shape[0], _ip(out), None))
         return out.astype(np.uint8)
 
     def trace_closest_hit(self, rays):
         """Device single_ray_intersections (kernels.cl:168) on caller rays -> (tri [k], out [k,10])."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        rays = _rays6(rays)
         tri = np.zeros(rays.shape[0], np.int32)
         out = np.zeros((rays.shape[0], 10), np.float32)
-        _check(lib().rt_debug_trace_rays(self._h, abi.RT_TRACE_CLOSEST_HIT, _fp(rays), None, rays.shape[0],
-                                         tri.ctypes.data_as(C.POINTER(C.c_int32)), _fp(out)))
+        _check(lib().rt_debug_trace_rays(self._h, abi.RT_TRACE_CLOSEST_HIT, _fp(rays), None, rays.shape[0], _ip(tri), _fp(out)))
         return tri, out
 
     def query_in_shadow(self, rays, radius_sq):
         """Tile-culled in_shadow (rt_trace_rays) on caller rays [k,6] = start, direction -> uint8 [k]; the same bits as
         trace_in_shadow."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        rays = _rays6(rays)
         r2 = np.ascontiguousarray(radius_sq, np.float32).reshape(-1)
         if r2.shape[0] != rays.shape[0]:
             raise ValueError("radius_sq must have one entry per ray")
         out = np.zeros(rays.shape[0], np.int32)
-        _check(lib().rt_trace_rays(self._h, abi.RT_TRACE_IN_SHADOW, _fp(rays), _fp(r2), rays.shape[0],
-                                   out.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        _check(lib().rt_trace_rays(self._h, abi.RT_TRACE_IN_SHADOW, _fp(rays), _fp(r2), rays.shape[0], _ip(out), None))
         return out.astype(np.uint8)
 
     def query_closest_hit(self, rays):
         """Tile-culled closest hit (rt_trace_rays) on caller rays -> (tri [k], out [k,10]); the same bits as
         trace_closest_hit."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        rays = _rays6(rays)
         tri = np.zeros(rays.shape[0], np.int32)
         out = np.zeros((rays.shape[0], 10), np.float32)
-        _check(lib().rt_trace_rays(self._h, abi.RT_TRACE_CLOSEST_HIT, _fp(rays), None, rays.shape[0],
-                                   tri.ctypes.data_as(C.POINTER(C.c_int32)), _fp(out)))
+        _check(lib().rt_trace_rays(self._h, abi.RT_TRACE_CLOSEST_HIT, _fp(rays), None, rays.shape[0], _ip(tri), _fp(out)))
         return tri, out
 
     def query_device(self, what, rays, radius_sq=None, out_tri=None, out10=None, stream=None):
@@ -829,23 +859,15 @@ class RayTracer:
         if what not in (abi.RT_TRACE_IN_SHADOW, abi.RT_TRACE_CLOSEST_HIT):
             raise ValueError("unknown query mode %r" % (what,))
         dev = self._torch_device()
-
-        if not isinstance(rays, torch.Tensor) or rays.dim() != 2:
-            raise ValueError("rays must be a torch tensor of shape [k, 6]")
-        k = rays.shape[0]
-        _need("rays", rays, torch.float32, (k, 6), dev)
+        k = _rows("rays", rays, 6, dev)
         shadow = what == abi.RT_TRACE_IN_SHADOW
         if shadow:
             if radius_sq is None:
                 raise ValueError("in_shadow queries need radius_sq")
             _need("radius_sq", radius_sq, torch.float32, (k,), dev)
-        if out_tri is None:
-            out_tri = torch.empty(k, dtype=torch.int32, device=dev)
-        _need("out_tri", out_tri, torch.int32, (k,), dev)
+        out_tri = _out("out_tri", out_tri, torch.int32, (k,), dev)
         if not shadow:
-            if out10 is None:
-                out10 = torch.empty((k, 10), dtype=torch.float32, device=dev)
-            _need("out10", out10, torch.float32, (k, 10), dev)
+            out10 = _out("out10", out10, torch.float32, (k, 10), dev)
         raw = self._raw_stream(stream, dev)
         if k:
             _check(lib().rt_trace_rays_device(self._h, what, C.c_void_p(rays.data_ptr()),
@@ -889,8 +911,9 @@ class RayTracer:
         for name, t in out.items():
             shape = self._aov_shape(name, sample)
             dtype = torch.int32 if abi.AOV_PLANES[name][2] else torch.float32
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+            if not isinstance(t, torch.Tensor):
                 raise ValueError("plane %r must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
+            _need("plane %r" % name, t, dtype, shape, dev)
             setattr(bufs, abi.AOV_PLANES[name][0], t.data_ptr())
         raw = self._raw_stream(stream, dev)
         _check(lib().rt_render_aov_device(self._h, _fp(rot), _fp(cam), C.c_float(focal),
@@ -913,12 +936,11 @@ class RayTracer:
             raise ValueError("points and normals must have the same shape [k, 3]")
         k = p.shape[0]
         p6 = np.ascontiguousarray(np.concatenate([p, nr], 1), np.float32)
-        li = np.ascontiguousarray(light, np.float32)[:3].copy()
+        li = _light3(light)
         sp = _seeds_ptr(seeds, k, "point")
         out = np.zeros(k, np.float32)
         cnt = np.zeros(k, np.int32) if want_counts else None
-        _check(lib().rt_shade_points(self._h, _fp(p6), sp, k, _fp(li), _fp(out),
-                                     cnt.ctypes.data_as(C.POINTER(C.c_int32)) if want_counts else None))
+        _check(lib().rt_shade_points(self._h, _fp(p6), sp, k, _fp(li), _fp(out), _ip(cnt)))
         return (out, cnt) if want_counts else out
 
     def shade_points_device(self, points6, light, seeds=None, out_light=None, out_counts=None, want_counts=False, stream=None):
@@ -928,21 +950,13 @@ class RayTracer:
         (out_light, out_counts) when counts are asked for."""
         import torch
         dev = self._torch_device()
-
-        if not isinstance(points6, torch.Tensor) or points6.dim() != 2:
-            raise ValueError("points6 must be a torch tensor of shape [k, 6]")
-        k = points6.shape[0]
-        _need("points6", points6, torch.float32, (k, 6), dev)
+        k = _rows("points6", points6, 6, dev)
         if seeds is not None:
             _need("seeds", seeds, torch.int32, (k,), dev)
-        if out_light is None:
-            out_light = torch.empty(k, dtype=torch.float32, device=dev)
-        _need("out_light", out_light, torch.float32, (k,), dev)
-        if out_counts is None and want_counts:
-            out_counts = torch.empty(k, dtype=torch.int32, device=dev)
-        if out_counts is not None:
-            _need("out_counts", out_counts, torch.int32, (k,), dev)
-        li = np.ascontiguousarray(light, np.float32)[:3].copy()
+        out_light = _out("out_light", out_light, torch.float32, (k,), dev)
+        if out_counts is not None or want_counts:
+            out_counts = _out("out_counts", out_counts, torch.int32, (k,), dev)
+        li = _light3(light)
         raw = self._raw_stream(stream, dev)
         if k:
             _check(lib().rt_shade_points_device(self._h, C.c_void_p(points6.data_ptr()),
@@ -952,6 +966,49 @@ class RayTracer:
                                                 C.c_void_p(raw)))
         return out_light if out_counts is None else (out_light, out_counts)
 
+    def _primary_hits(self, method, rot, cam, focal, sample, bands_ok):
+        """What the render_*_light methods do up to their shade call.  Refuses, in `method`'s name, a `sample` that is not one
+        AA sample index, a context of row bands unless bands_ok, and a frame of more than 2^24 pixels; then an AOV pass of
+        that sample -> (planes: fresh prim / position / normal tensors, p6: the shade call's points float32 [rows * W, 6],
+        hit: bool [rows, W], the pixels that see something)."""
+        import torch
+        cfg = self.cfg
+        aa = cfg.aa_x * cfg.aa_y
+        if sample is None or isinstance(sample, bool) or int(sample) != sample or not 0 <= int(sample) < aa:
+            raise ValueError("sample must be one AA sample index in [0, %d)" % aa)
+        if not bands_ok and max(cfg.band_count, 1) != 1:
+            raise ValueError("%s: a context of row bands does not hold neighbouring rows" % method)
+        if cfg.width * cfg.height > abi.RT_SHADE_SEED_MAX:
+            raise ValueError("%s: %d x %d pixels exceed the seed domain of 2^24 ids" % (method, cfg.width, cfg.height))
+        dev = self._torch_device()
+        shape = (self.rows, self.width)
+        planes = {"prim": torch.empty(shape, dtype=torch.int32, device=dev),
+                  "position": torch.empty(shape + (4,), dtype=torch.float32, device=dev),
+                  "normal": torch.empty(shape + (4,), dtype=torch.float32, device=dev)}
+        self.render_aov_device(rot, cam, focal, sample=sample, out=planes)
+        p6 = torch.cat([planes["position"][..., :3], planes["normal"][..., :3]], -1).reshape(-1, 6).contiguous()
+        return planes, p6, planes["prim"] != -1
+
+    def _pixel_ids(self):
+        """The global id of every pixel the context owns, its rows top to bottom: int32 [rows * W], the frame's seeds."""
+        import torch
+        cfg, dev = self.cfg, self._torch_device()
+        br, bc = (cfg.band_rows if cfg.band_rows > 0 else cfg.height), max(cfg.band_count, 1)
+        ys = torch.tensor([y for y in range(cfg.height) if (y // br) % bc == cfg.band_index], dtype=torch.int32, device=dev)
+        return (ys[:, None] * self.width + torch.arange(self.width, dtype=torch.int32, device=dev)[None, :]).reshape(-1).contiguous()
+
+    def _visibility_and_term(self, pos, nrm, hit, counts, light):
+        """From a shade call's counts: (zero, V = counts / shadow_samples, term = 16 * max(dot(dir, N), 0) / (4 pi r^2) with
+        dir = light - P), float32 [rows, W] each, V and term 0 where the pixel sees nothing."""
+        import math
+        import torch
+        zero = torch.zeros(hit.shape, dtype=torch.float32, device=hit.device)
+        vis = torch.where(hit, counts.reshape(hit.shape).to(torch.float32) / float(self.cfg.shadow_samples), zero)
+        d = torch.tensor(_light3(light), device=hit.device) - pos[..., :3]
+        r2 = (d * d).sum(-1)
+        term = 16.0 * (d * nrm[..., :3]).sum(-1).clamp_min(0.0) / (4.0 * math.pi * r2)
+        return zero, vis, torch.where(hit, term, zero)
+
     def render_direct_light(self, rot, cam, light, focal, sample=0):
         """The direct light of every pixel's primary hit, on the device: an AOV pass (position, normal, prim of AA sample
         `sample`) and a shade call seeded with the global pixel id, as the frame seeds it -> torch float32 [rows, W], 0 where
@@ -960,24 +1017,9 @@ class RayTracer:
         result is one value per pixel); a context of row bands gets its owned rows, seeded with the global ids; frames of
         more than 2^24 pixels are refused (the ids leave the seed domain and the frame's own ids are formed in FP32)."""
         import torch
-        aa = self.cfg.aa_x * self.cfg.aa_y
-        if sample is None or isinstance(sample, bool) or int(sample) != sample or not 0 <= int(sample) < aa:
-            raise ValueError("sample must be one AA sample index in [0, %d)" % aa)
-        if self.cfg.width * self.cfg.height > abi.RT_SHADE_SEED_MAX:
-            raise ValueError("render_direct_light: %d x %d pixels exceed the seed domain of 2^24 ids" % (self.cfg.width, self.cfg.height))
-        dev = self._torch_device()
-        shape = (self.rows, self.width)
-        planes = {"prim": torch.empty(shape, dtype=torch.int32, device=dev),
-                  "position": torch.empty(shape + (4,), dtype=torch.float32, device=dev),
-                  "normal": torch.empty(shape + (4,), dtype=torch.float32, device=dev)}
-        self.render_aov_device(rot, cam, focal, sample=sample, out=planes)
-        cfg = self.cfg
-        br, bc = (cfg.band_rows if cfg.band_rows > 0 else cfg.height), max(cfg.band_count, 1)
-        ys = torch.tensor([y for y in range(cfg.height) if (y // br) % bc == cfg.band_index], dtype=torch.int32, device=dev)
-        seeds = (ys[:, None] * self.width + torch.arange(self.width, dtype=torch.int32, device=dev)[None, :]).reshape(-1).contiguous()
-        p6 = torch.cat([planes["position"][..., :3], planes["normal"][..., :3]], -1).reshape(-1, 6).contiguous()
-        out = self.shade_points_device(p6, light, seeds=seeds)
-        return torch.where(planes["prim"].reshape(-1) != -1, out, torch.zeros_like(out)).reshape(shape)
+        planes, p6, hit = self._primary_hits("render_direct_light", rot, cam, focal, sample, bands_ok=True)
+        out = self.shade_points_device(p6, light, seeds=self._pixel_ids())
+        return torch.where(hit.reshape(-1), out, torch.zeros_like(out)).reshape(hit.shape)
 
     def filter_plane(self, value, position4, normal4, out=None, **params):
         """The a-trous filter of a per-pixel plane on the device (rt_filter_plane), blocking: numpy planes as
@@ -993,15 +1035,8 @@ class RayTracer:
         itself for in-place use.  stream: a torch stream or a raw hipStream_t (default: torch's current stream)."""
         import torch
         dev = self._torch_device()
-        if not isinstance(value, torch.Tensor) or value.dim() != 2:
-            raise ValueError("value must be a torch tensor of shape [height, width]")
-        h, w = value.shape
-        _need("value", value, torch.float32, (h, w), dev)
-        _need("position4", position4, torch.float32, (h, w, 4), dev)
-        _need("normal4", normal4, torch.float32, (h, w, 4), dev)
-        if out is None:
-            out = torch.empty((h, w), dtype=torch.float32, device=dev)
-        _need("out", out, torch.float32, (h, w), dev)
+        h, w = _guide_tensors(value, position4, normal4, dev)
+        out = _out("out", out, torch.float32, (h, w), dev)
         p = filter_params(w, h, **params)
         raw = self._raw_stream(stream, dev)
         _check(lib().rt_filter_plane_device(self._h, C.byref(p), C.c_void_p(value.data_ptr()), C.c_void_p(position4.data_ptr()),
@@ -1021,32 +1056,11 @@ class RayTracer:
         exactly as they were: only penumbrae are noisy.  Float-accurate, not bit-pinned to the frame (the frame sums term per
         sample).  want_parts: also (term, V, V_f).  Runs on torch's current stream; does not synchronise.  Refuses contexts of
         row bands (their rows are not neighbours) and, like render_direct_light, frames beyond 2^24 pixels."""
-        import math
         import torch
-        aa = self.cfg.aa_x * self.cfg.aa_y
-        if sample is None or isinstance(sample, bool) or int(sample) != sample or not 0 <= int(sample) < aa:
-            raise ValueError("sample must be one AA sample index in [0, %d)" % aa)
-        if max(self.cfg.band_count, 1) != 1:
-            raise ValueError("render_filtered_light: a context of row bands does not hold neighbouring rows")
-        if self.cfg.width * self.cfg.height > abi.RT_SHADE_SEED_MAX:
-            raise ValueError("render_filtered_light: %d x %d pixels exceed the seed domain of 2^24 ids" % (self.cfg.width, self.cfg.height))
-        dev = self._torch_device()
-        shape = (self.rows, self.width)
-        planes = {"prim": torch.empty(shape, dtype=torch.int32, device=dev),
-                  "position": torch.empty(shape + (4,), dtype=torch.float32, device=dev),
-                  "normal": torch.empty(shape + (4,), dtype=torch.float32, device=dev)}
-        self.render_aov_device(rot, cam, focal, sample=sample, out=planes)
+        planes, p6, hit = self._primary_hits("render_filtered_light", rot, cam, focal, sample, bands_ok=False)
         pos, nrm = planes["position"], planes["normal"]
-        seeds = torch.arange(shape[0] * shape[1], dtype=torch.int32, device=dev)
-        p6 = torch.cat([pos[..., :3], nrm[..., :3]], -1).reshape(-1, 6).contiguous()
-        _, counts = self.shade_points_device(p6, light, seeds=seeds, want_counts=True)
-        hit = planes["prim"] != -1
-        zero = torch.zeros(shape, dtype=torch.float32, device=dev)
-        vis = torch.where(hit, counts.reshape(shape).to(torch.float32) / float(self.cfg.shadow_samples), zero)
-        d = torch.tensor(np.ascontiguousarray(light, np.float32)[:3], device=dev) - pos[..., :3]
-        r2 = (d * d).sum(-1)
-        term = 16.0 * (d * nrm[..., :3]).sum(-1).clamp_min(0.0) / (4.0 * math.pi * r2)
-        term = torch.where(hit, term, zero)
+        _, counts = self.shade_points_device(p6, light, seeds=self._pixel_ids(), want_counts=True)
+        zero, vis, term = self._visibility_and_term(pos, nrm, hit, counts, light)
         vis_f = self.filter_plane_device(vis, pos, nrm, **params)
         out = term * torch.where(hit, vis_f, zero)
         return (out, term, vis, vis_f) if want_parts else out
@@ -1069,26 +1083,16 @@ class RayTracer:
         variance), None for a plane that was not asked for."""
         import torch
         dev = self._torch_device()
-        if not isinstance(value, torch.Tensor) or value.dim() != 2:
-            raise ValueError("value must be a torch tensor of shape [height, width]")
-        h, w = value.shape
-        _need("value", value, torch.float32, (h, w), dev)
-        _need("position4", position4, torch.float32, (h, w, 4), dev)
-        _need("normal4", normal4, torch.float32, (h, w, 4), dev)
+        h, w = _guide_tensors(value, position4, normal4, dev)
         if prim is not None:
             _need("prim", prim, torch.int32, (h, w), dev)
         if prev is not None:
             _need("prev", prev, torch.float32, (h, w, abi.HISTORY_WORDS), dev)
-        if next is None:
-            next = torch.empty((h, w, abi.HISTORY_WORDS), dtype=torch.float32, device=dev)
-        _need("next", next, torch.float32, (h, w, abi.HISTORY_WORDS), dev)
-        if out_mean is None and want_mean:
-            out_mean = torch.empty((h, w), dtype=torch.float32, device=dev)
-        if out_variance is None and want_variance:
-            out_variance = torch.empty((h, w), dtype=torch.float32, device=dev)
-        for name, t in (("out_mean", out_mean), ("out_variance", out_variance)):
-            if t is not None:
-                _need(name, t, torch.float32, (h, w), dev)
+        next = _out("next", next, torch.float32, (h, w, abi.HISTORY_WORDS), dev)
+        if out_mean is not None or want_mean:
+            out_mean = _out("out_mean", out_mean, torch.float32, (h, w), dev)
+        if out_variance is not None or want_variance:
+            out_variance = _out("out_variance", out_variance, torch.float32, (h, w), dev)
         p = params if params is not None else accumulate_params(w, h, **kw)
         raw = self._raw_stream(stream, dev)
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
@@ -1114,37 +1118,16 @@ class RayTracer:
         float32 [rows, W], 0 where the pixel sees nothing.  filter=True runs the a-trous filter (its defaults) over V_mean
         first.  want_parts: also (term, V, V_mean, variance, count), V_mean as accumulated (unfiltered).  reset_history() starts a new sequence.  Runs on torch's
         current stream; does not synchronise.  The same refusals as render_filtered_light."""
-        import math
         import torch
-        aa = self.cfg.aa_x * self.cfg.aa_y
-        if sample is None or isinstance(sample, bool) or int(sample) != sample or not 0 <= int(sample) < aa:
-            raise ValueError("sample must be one AA sample index in [0, %d)" % aa)
-        if max(self.cfg.band_count, 1) != 1:
-            raise ValueError("render_accumulated_light: a context of row bands does not hold neighbouring rows")
-        if self.cfg.width * self.cfg.height > abi.RT_SHADE_SEED_MAX:
-            raise ValueError("render_accumulated_light: %d x %d pixels exceed the seed domain of 2^24 ids" % (self.cfg.width, self.cfg.height))
-        dev = self._torch_device()
-        shape = (self.rows, self.width)
-        count = shape[0] * shape[1]
+        planes, p6, hit = self._primary_hits("render_accumulated_light", rot, cam, focal, sample, bands_ok=False)
+        pos, nrm, shape = planes["position"], planes["normal"], tuple(hit.shape)
         if self._history is None:
-            hist = [torch.empty(shape + (abi.HISTORY_WORDS,), dtype=torch.float32, device=dev) for _ in range(2)]
+            hist = [torch.empty(shape + (abi.HISTORY_WORDS,), dtype=torch.float32, device=hit.device) for _ in range(2)]
             self._history = [hist, 0, None, 0]
         hist, cur, view, frame = self._history
-        planes = {"prim": torch.empty(shape, dtype=torch.int32, device=dev),
-                  "position": torch.empty(shape + (4,), dtype=torch.float32, device=dev),
-                  "normal": torch.empty(shape + (4,), dtype=torch.float32, device=dev)}
-        self.render_aov_device(rot, cam, focal, sample=sample, out=planes)
-        pos, nrm = planes["position"], planes["normal"]
-        seeds = ((torch.arange(count, dtype=torch.int64, device=dev) + frame * count) % abi.RT_SHADE_SEED_MAX).to(torch.int32)
-        p6 = torch.cat([pos[..., :3], nrm[..., :3]], -1).reshape(-1, 6).contiguous()
+        seeds = ((self._pixel_ids().to(torch.int64) + frame * hit.numel()) % abi.RT_SHADE_SEED_MAX).to(torch.int32)
         _, counts = self.shade_points_device(p6, light, seeds=seeds, want_counts=True)
-        hit = planes["prim"] != -1
-        zero = torch.zeros(shape, dtype=torch.float32, device=dev)
-        vis = torch.where(hit, counts.reshape(shape).to(torch.float32) / float(self.cfg.shadow_samples), zero)
-        d = torch.tensor(np.ascontiguousarray(light, np.float32)[:3], device=dev) - pos[..., :3]
-        r2 = (d * d).sum(-1)
-        term = 16.0 * (d * nrm[..., :3]).sum(-1).clamp_min(0.0) / (4.0 * math.pi * r2)
-        term = torch.where(hit, term, zero)
+        zero, vis, term = self._visibility_and_term(pos, nrm, hit, counts, light)
         if view is None:
             p, prev = accumulate_params(shape[1], shape[0], **params), None
         else:
@@ -1165,14 +1148,13 @@ class RayTracer:
         given), seeds int32 [k] = the global_id of each ray's jitter stream (None: k & 0xFFFFFF; the frame uses the pixel
         id) -> rgba float32 [k,4]: xyz the colour rt_render gives that ray (bounces and soft shadows included), w = 1 where
         the ray hits anything, else 0; with want_prim also the first hit int32 [k] (-1 / -2 / original triangle index)."""
-        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        rays = _rays6(rays)
         k = rays.shape[0]
-        li = np.ascontiguousarray(light, np.float32)[:3].copy()
+        li = _light3(light)
         sp = _seeds_ptr(seeds, k, "ray")
         out = np.zeros((k, 4), np.float32)
         prim = np.zeros(k, np.int32) if want_prim else None
-        _check(lib().rt_radiance_rays(self._h, _fp(rays), sp, k, _fp(li), _fp(out),
-                                      prim.ctypes.data_as(C.POINTER(C.c_int32)) if want_prim else None))
+        _check(lib().rt_radiance_rays(self._h, _fp(rays), sp, k, _fp(li), _fp(out), _ip(prim)))
         return (out, prim) if want_prim else out
 
     def radiance_rays_device(self, rays6, light, seeds=None, out=None, out_prim=None, stream=None):
@@ -1182,19 +1164,13 @@ class RayTracer:
         or (out, out_prim) when out_prim is given."""
         import torch
         dev = self._torch_device()
-
-        if not isinstance(rays6, torch.Tensor) or rays6.dim() != 2:
-            raise ValueError("rays6 must be a torch tensor of shape [k, 6]")
-        k = rays6.shape[0]
-        _need("rays6", rays6, torch.float32, (k, 6), dev)
+        k = _rows("rays6", rays6, 6, dev)
         if seeds is not None:
             _need("seeds", seeds, torch.int32, (k,), dev)
-        if out is None:
-            out = torch.empty((k, 4), dtype=torch.float32, device=dev)
-        _need("out", out, torch.float32, (k, 4), dev)
+        out = _out("out", out, torch.float32, (k, 4), dev)
         if out_prim is not None:
             _need("out_prim", out_prim, torch.int32, (k,), dev)
-        li = np.ascontiguousarray(light, np.float32)[:3].copy()
+        li = _light3(light)
         raw = self._raw_stream(stream, dev)
         if k:
             _check(lib().rt_radiance_rays_device(self._h, C.c_void_p(rays6.data_ptr()),
@@ -1249,33 +1225,31 @@ class RayTracer:
         return {"waves": int(out[0]), "span_us": (last - first) / 100.0, "mean_start_us": (int(out[3]) / n - first) / 100.0,
                 "mean_idle_tail_us": (last - int(out[4]) / n) / 100.0, "jobs": int(out[5]), "max_jobs_per_wave": int(out[6]), "listed_jobs": int(out[7])}
 
-    def wave_seeds(self):
-        """Wave kernel: the tile seeds of the last frame (rt_debug_wave_seeds).  -> dict: tile_rows, tiles_per_row, rows_per_tile
-        (all 0 when the frame took no seed), tiles_primary, tiles_shadow, jobs_primary, jobs_shadow, and `records`, a
-        structured array [tile_rows, tiles_per_row] of SEED_DTYPE."""
-        fn = lib().rt_debug_wave_seeds
+    def _wave_seed_records(self, export, ncounters):
+        """rt_debug_wave_seeds / rt_debug_wave_seeds_wide, asked for the tile grid first and then for its records: -> (dict
+        tile_rows, tiles_per_row, rows_per_tile, `records` [tile_rows, tiles_per_row] of SEED_DTYPE; the export's counters)."""
+        fn = getattr(lib(), export)
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
-        dims, cnt = (C.c_int32 * 3)(), (C.c_uint64 * 4)()
+        dims, cnt = (C.c_int32 * 3)(), (C.c_uint64 * ncounters)()
         _check(fn(self._h, None, 0, dims, cnt))
         rec = np.zeros((int(dims[0]), int(dims[1])), SEED_DTYPE)
         if rec.size:
             _check(fn(self._h, rec.ctypes.data_as(C.c_void_p), rec.size, dims, cnt))
-        return {"tile_rows": int(dims[0]), "tiles_per_row": int(dims[1]), "rows_per_tile": int(dims[2]),
-                "tiles_primary": int(cnt[0]), "tiles_shadow": int(cnt[1]), "jobs_primary": int(cnt[2]), "jobs_shadow": int(cnt[3]),
-                "records": rec}
+        return {"tile_rows": int(dims[0]), "tiles_per_row": int(dims[1]), "rows_per_tile": int(dims[2]), "records": rec}, cnt
+
+    def wave_seeds(self):
+        """Wave kernel: the tile seeds of the last frame (rt_debug_wave_seeds).  -> dict: tile_rows, tiles_per_row, rows_per_tile
+        (all 0 when the frame took no seed), tiles_primary, tiles_shadow, jobs_primary, jobs_shadow, and `records`, a
+        structured array [tile_rows, tiles_per_row] of SEED_DTYPE."""
+        d, cnt = self._wave_seed_records("rt_debug_wave_seeds", 4)
+        d.update(tiles_primary=int(cnt[0]), tiles_shadow=int(cnt[1]), jobs_primary=int(cnt[2]), jobs_shadow=int(cnt[3]))
+        return d
 
     def wave_seeds_wide(self):
         """Wave kernel: the tile seeds of the last frame as the draw kernel reads them (rt_debug_wave_seeds_wide).  -> dict:
         tile_rows, tiles_per_row, rows_per_tile, tiles_<k> and jobs_<k> for k in SEED_WIDE_KEYS (records with a primary part,
         a shadow part, and of those the ones with casters off h's plane, a sphere candidate, blocked), and the raw `records`."""
-        fn = lib().rt_debug_wave_seeds_wide
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
-        dims, cnt = (C.c_int32 * 3)(), (C.c_uint64 * 10)()
-        _check(fn(self._h, None, 0, dims, cnt))
-        rec = np.zeros((int(dims[0]), int(dims[1])), SEED_DTYPE)
-        if rec.size:
-            _check(fn(self._h, rec.ctypes.data_as(C.c_void_p), rec.size, dims, cnt))
-        d = {"tile_rows": int(dims[0]), "tiles_per_row": int(dims[1]), "rows_per_tile": int(dims[2]), "records": rec}
+        d, cnt = self._wave_seed_records("rt_debug_wave_seeds_wide", 10)
         for q, k in enumerate(SEED_WIDE_KEYS):
             d["tiles_" + k], d["jobs_" + k] = int(cnt[2 * q]), int(cnt[2 * q + 1])
         return d
