@@ -522,7 +522,8 @@ int rt_filter_plane_host(const rt_filter_params* params, const float* value, con
  * operation order it is a pure FP32 function of its inputs; every implementation (the device kernel,
  * rt_accumulate_plane_host) gives the same bits.
  * Scope: the scene is assumed static between the two views.  Camera and light may move; geometry that moved fails the
- * plane or prim test and restarts its history.  Motion vectors for posed or skinned objects are not built.
+ * plane or prim test and restarts its history; rt_accumulate_plane_moving below takes the place where a posed or skinned
+ * point was (rt_motion_planes) and carries its history along.
  * Planes of `height` rows x `width` pixels, row-major, of the CURRENT view:
  *   value      float32 [h][w]      this view's sample of the estimate;
  *   position4  float32 [h][w][4]   the guides, in the layouts of rt_render_aov's position4 / normal4 planes.  A pixel is
@@ -605,6 +606,88 @@ int rt_debug_accumulate_stats(rt_ctx* ctx, uint64_t out[8]);
 int rt_accumulate_plane_host(const rt_accumulate_params* params, const float* value, const float* position4,
                              const float* normal4, const int32_t* prim, const rt_history_texel* prev, rt_history_texel* next,
                              float* out_mean, float* out_variance);
+
+/* ---- motion planes: where posed and skinned geometry was in the previous view (rt_motion.hip) ----------
+ * rt_accumulate_plane assumes a static scene.  These entries carry the history across geometry that rt_pose_objects*,
+ * rt_pose_skin* or rt_update_scene* moved: the context keeps the scene as the previous view saw it (the SNAPSHOT), a motion
+ * call says where each pixel's surface point was in that scene, and rt_accumulate_plane_moving reprojects with that point
+ * while it stores the current guides.
+ * Scope: triangles.  Sphere motion is out of scope: a sphere element is copied, so a moved sphere (rt_update_spheres) fails
+ * the plane test and restarts, as it does with rt_accumulate_plane.  The motion planes are 64 bytes per pixel of
+ * intermediate data; a kernel that fuses the motion and the accumulate steps is not built.
+ *
+ * The snapshot.  rt_motion_snapshot copies the context's live scene, in the caller's original triangle order — vertices
+ * [3n] float4 and normals [n] float4 — device to device on hip_stream (NULL = default stream) into buffers the context owns,
+ * and records n; it returns without synchronising.  The buffers are sized by the scene, only grow, and are freed by
+ * rt_motion_release and rt_destroy; a context that never snapshots allocates nothing.  The caller takes the snapshot after the
+ * frame or AOV pass of view k and before the pose or update that makes view k+1.  Nothing in the scene edits changes: an
+ * rt_replace_scene* to another triangle count leaves a snapshot whose count no longer matches, and motion calls are
+ * refused until the next snapshot.  rt_debug_motion_info: the snapshot's triangle count, 0 without one.
+ * Ordering: snapshots and motion calls are one family of readers of the scene.  They wait for the context's pending device
+ * edit and for the family's previous call; scene edits wait for them; frames and AOV passes do not wait for them and they do
+ * not wait for frames; rt_destroy waits for them.  A multi-device context answers on devices[0].                          */
+int rt_motion_snapshot(rt_ctx* ctx, void* hip_stream);
+int rt_motion_release(rt_ctx* ctx);
+int rt_debug_motion_info(rt_ctx* ctx, int32_t* snapshot_triangles);
+/* The motion planes.  Element-wise over `count` elements (no width or height) of rt_render_aov's planes, one sample per
+ * pixel or all samples:
+ *   prim       int32   [count]      position4, normal4   float32 [count][4]
+ * and the outputs out_prev_position4, out_prev_normal4 float32 [count][4], both required.  A pure FP32 function without
+ * contraction in exactly this order; every implementation (the device kernel, rt_motion_planes_host) gives the same bits.
+ * For element k with P the xyz of position4, n the scene's triangle count, a, b, c the vertices of triangle prim[k] in the
+ * live scene and a', b', c' those in the snapshot:
+ *   1. INVALID iff position4.w > 0 is false (a NaN is invalid) or prim[k] is outside [-2, n): both outputs are all-zero
+ *      (w = 0): no place in the previous scene.
+ *   2. prim[k] == -1 (miss-coded but valid) or -2 (a sphere): both outputs are the input planes' bits, all four words.
+ *   3. UNMOVED triangle — all nine coordinates compare == with the snapshot's: both outputs are the input planes' bits.  So an
+ *      unmoved scene yields its inputs, and accumulation with them equals accumulation without them.
+ *   4. MOVED triangle, component-wise: e1 = b - a, e2 = c - a, d = P - a; dot products as (x*x + y*y) + z*z:
+ *      d11 = e1.e1, d12 = e1.e2, d22 = e2.e2, p1 = d.e1, p2 = d.e2; den = d11*d22 - d12*d12;
+ *      u = (d22*p1 - d12*p2) / den and v = (d11*p2 - d12*p1) / den, the divisions correctly rounded; e1' = b' - a',
+ *      e2' = c' - a'; out_prev_position4 = ((a'_c + u*e1'_c) + v*e2'_c for c = x, y, z; 1), a NaN component stored as the quiet
+ *      NaN 0x7FC00000 (the filter's and the accumulate's rule; it fails every comparison downstream);
+ *      out_prev_normal4 = (the xyz bits of the snapshot's normal of the triangle; 0).
+ * Accuracy of step 4 over random rigid moves: the point stays on the previous triangle's plane to about 1.5e-7 for every
+ * triangle shape; inside the plane the error is about 3e-7 for well-shaped unit triangles and grows with the aspect ratio
+ * (3e-4 at 1:100, 1.7e-2 at 1:1000).  A degenerate triangle (den == 0) gives infinities or the quiet NaN.
+ * A NULL ctx or plane and count outside [0, 2^31] are RT_E_INVALID before the context is looked at; so are, after that, a
+ * context without a snapshot and one whose snapshot count differs from its current n (the message gives both counts).
+ * count == 0 is a no-op.  rt_motion_planes: host arrays, blocking (staged through device memory the context keeps and only
+ * grows).  rt_motion_planes_device: planes in device memory on the context's device, the four float4 planes 16-byte
+ * aligned, enqueued on hip_stream after the caller's earlier work; returns without synchronising.                          */
+int rt_motion_planes(rt_ctx* ctx, const int32_t* prim, const float* position4, const float* normal4, int64_t count,
+                     float* out_prev_position4, float* out_prev_normal4);
+int rt_motion_planes_device(rt_ctx* ctx, const void* d_prim, const void* d_position4, const void* d_normal4, int64_t count,
+                            void* d_out_prev_position4, void* d_out_prev_normal4, void* hip_stream);
+/* The same function on the host (CPU only, no context) over a live scene and a previous one of n triangles each, in the
+ * layouts of rt_init: the statement the device kernel is pinned against.  Same checks; n >= 0.                             */
+int rt_motion_planes_host(const float* vertices4_now, const float* vertices4_then, const float* normals4_then, int32_t n,
+                          const int32_t* prim, const float* position4, const float* normal4, int64_t count,
+                          float* out_prev_position4, float* out_prev_normal4);
+/* Diagnostic: work counters of the context's most recent motion call (synchronises it; zeros before the first).  out[0]
+ * elements, out[1] valid elements, out[2] carried through a moved triangle, out[3] on an unmoved triangle, out[4] sphere or
+ * miss copies, out[5] valid w but prim out of range, out[6..7] 0.                                                          */
+int rt_debug_motion_stats(rt_ctx* ctx, uint64_t out[8]);
+/* rt_accumulate_plane with reprojection guides: exactly rt_accumulate_plane's definition with one difference in its steps 2
+ * and 3 — the projection, the normal test and the plane test use Pr / Nr, the xyz of
+ *   reproj_position4, reproj_normal4   float32 [h][w][4]   (rt_motion_planes' outputs for the view's guides),
+ * in place of P / N; a valid pixel whose reproj_position4.w > 0 is false has no candidate (counted in out[4] of
+ * rt_debug_accumulate_stats).  The prim test keeps comparing r.prim with prim[p] — triangle indices survive a pose — and
+ * step 7 still stores the current P, N and prim.  Both reprojection planes NULL give rt_accumulate_plane bit for bit; one
+ * NULL and one set is RT_E_INVALID; in the device entry both are 16-byte aligned.  Checks, ordering, staging and counters
+ * are the accumulate family's.                                                                                           */
+int rt_accumulate_plane_moving(rt_ctx* ctx, const rt_accumulate_params* params, const float* value, const float* position4,
+                               const float* normal4, const int32_t* prim, const float* reproj_position4,
+                               const float* reproj_normal4, const rt_history_texel* prev, rt_history_texel* next,
+                               float* out_mean, float* out_variance);
+int rt_accumulate_plane_moving_device(rt_ctx* ctx, const rt_accumulate_params* params, const void* d_value,
+                                      const void* d_position4, const void* d_normal4, const void* d_prim,
+                                      const void* d_reproj_position4, const void* d_reproj_normal4, const void* d_prev,
+                                      void* d_next, void* d_out_mean, void* d_out_variance, void* hip_stream);
+int rt_accumulate_plane_moving_host(const rt_accumulate_params* params, const float* value, const float* position4,
+                                    const float* normal4, const int32_t* prim, const float* reproj_position4,
+                                    const float* reproj_normal4, const rt_history_texel* prev, rt_history_texel* next,
+                                    float* out_mean, float* out_variance);
 
 /* Diagnostic, mesh kernel (n > 64): the cost of every 16x16-pixel block of the most recent frame in s_memtime ticks
  * (shader cycles) — the scheduling state "last frame's expensive blocks first" is built from it.  Row-major over

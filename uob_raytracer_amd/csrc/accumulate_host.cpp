@@ -1,5 +1,6 @@
-// accumulate_host.cpp — the temporal reprojection of include/uob_rt.h ("rt_accumulate_plane"), stated once on the host: a
-// plain loop nest that is the definition, line for line, and the checks of rt_accumulate_params that every entry applies.
+// accumulate_host.cpp — the temporal reprojection of include/uob_rt.h ("rt_accumulate_plane", and "rt_accumulate_plane_moving"
+// with its reprojection planes), stated once on the host: a plain loop nest that is the definition, line for line, and the
+// checks of rt_accumulate_params that every entry applies.
 // Host only (no device, no context); built with -ffp-contract=off like everything else, so that every product and sum below
 // is one FP32 operation.  The device kernel (rt_accumulate.hip) is pinned against this file bit for bit.
 #include <cmath>
@@ -36,6 +37,14 @@ int accumulate_check(const rt_accumulate_params* p, const void* value, const voi
   }
   return RT_OK;
 }
+
+// The reprojection planes of rt_accumulate_plane_moving: both or neither
+int accumulate_reproj_check(const void* reproj_position4, const void* reproj_normal4, const char* fn) {
+  if ((reproj_position4 == nullptr) != (reproj_normal4 == nullptr)) {
+    set_error("%s: reproj_position4 and reproj_normal4 must both be given or both be NULL", fn); return RT_E_INVALID;
+  }
+  return RT_OK;
+}
 }  // namespace uobrt
 
 namespace {
@@ -45,26 +54,12 @@ float quiet_if_nan(float v) {
   return v;
 }
 
-}  // namespace
-
-extern "C" {
-
-void rt_accumulate_params_default(rt_accumulate_params* p, int32_t width, int32_t height) {
-  if (!p) return;
-  p->width = width;
-  p->height = height;
-  for (int k = 0; k < 12; ++k) p->prev_rot[k] = (k == 0 || k == 5 || k == 10) ? 1.0f : 0.0f;
-  p->prev_cam[0] = p->prev_cam[1] = p->prev_cam[2] = 0.0f;
-  p->prev_focal_px = (float)width;
-  p->normal_min_dot = 0.9f;
-  p->plane_eps = 0.01f;
-  p->max_history = 32;
-}
-
-int rt_accumulate_plane_host(const rt_accumulate_params* p, const float* value, const float* position4, const float* normal4,
-                             const int32_t* prim, const rt_history_texel* prev, rt_history_texel* next, float* out_mean,
-                             float* out_variance) {
-  const int rc = uobrt::accumulate_check(p, value, position4, normal4, prev, next, "rt_accumulate_plane_host");
+// The definition over a plane; rpos / rnrm: the reprojection planes of rt_accumulate_plane_moving, or both NULL
+int accumulate_planes(const rt_accumulate_params* p, const float* value, const float* position4, const float* normal4,
+                      const int32_t* prim, const float* rpos, const float* rnrm, const rt_history_texel* prev, rt_history_texel* next,
+                      float* out_mean, float* out_variance, const char* fn) {
+  int rc = uobrt::accumulate_check(p, value, position4, normal4, prev, next, fn);
+  if (rc == RT_OK) rc = uobrt::accumulate_reproj_check(rpos, rnrm, fn);
   if (rc != RT_OK) return rc;
   const int64_t w = p->width, h = p->height;
   const float* rot = p->prev_rot;
@@ -75,13 +70,15 @@ int rt_accumulate_plane_host(const rt_accumulate_params* p, const float* value, 
       const int64_t c = y * w + x;
       const float* P = position4 + 4 * c;
       const float* N = normal4 + 4 * c;
+      const float* Pr = rpos ? rpos + 4 * c : P;         // what is projected and tested against the records
+      const float* Nr = rpos ? rnrm + 4 * c : N;
       const float v = value[c];
       const float vv = v * v;
       const bool valid = P[3] > 0.0f;
       float num = 0.0f, num2 = 0.0f, den = 0.0f, cmin = INFINITY;
       int taps = 0;
-      if (valid && prev) {
-        const float d0 = P[0] - p->prev_cam[0], d1 = P[1] - p->prev_cam[1], d2 = P[2] - p->prev_cam[2];
+      if (valid && prev && Pr[3] > 0.0f) {
+        const float d0 = Pr[0] - p->prev_cam[0], d1 = Pr[1] - p->prev_cam[1], d2 = Pr[2] - p->prev_cam[2];
         const float q0 = (d0 * rot[0] + d1 * rot[4]) + d2 * rot[8];
         const float q1 = (d0 * rot[1] + d1 * rot[5]) + d2 * rot[9];
         const float q2 = (d0 * rot[2] + d1 * rot[6]) + d2 * rot[10];
@@ -100,10 +97,10 @@ int rt_accumulate_plane_host(const rt_accumulate_params* p, const float* value, 
               const rt_history_texel& r = prev[qy * w + qx];
               if (!(r.count > 0.0f)) continue;
               if (prim && r.prim != prim[c]) continue;
-              const float nd = (N[0] * r.normal[0] + N[1] * r.normal[1]) + N[2] * r.normal[2];
+              const float nd = (Nr[0] * r.normal[0] + Nr[1] * r.normal[1]) + Nr[2] * r.normal[2];
               if (!(nd >= p->normal_min_dot)) continue;
-              const float e0 = r.position[0] - P[0], e1 = r.position[1] - P[1], e2 = r.position[2] - P[2];
-              const float pd = (N[0] * e0 + N[1] * e1) + N[2] * e2;
+              const float e0 = r.position[0] - Pr[0], e1 = r.position[1] - Pr[1], e2 = r.position[2] - Pr[2];
+              const float pd = (Nr[0] * e0 + Nr[1] * e1) + Nr[2] * e2;
               if (!(fabsf(pd) <= p->plane_eps)) continue;
               num = num + wt * r.mean;
               num2 = num2 + wt * r.m2;
@@ -143,6 +140,36 @@ int rt_accumulate_plane_host(const rt_accumulate_params* p, const float* value, 
       }
     }
   return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void rt_accumulate_params_default(rt_accumulate_params* p, int32_t width, int32_t height) {
+  if (!p) return;
+  p->width = width;
+  p->height = height;
+  for (int k = 0; k < 12; ++k) p->prev_rot[k] = (k == 0 || k == 5 || k == 10) ? 1.0f : 0.0f;
+  p->prev_cam[0] = p->prev_cam[1] = p->prev_cam[2] = 0.0f;
+  p->prev_focal_px = (float)width;
+  p->normal_min_dot = 0.9f;
+  p->plane_eps = 0.01f;
+  p->max_history = 32;
+}
+
+int rt_accumulate_plane_host(const rt_accumulate_params* p, const float* value, const float* position4, const float* normal4,
+                             const int32_t* prim, const rt_history_texel* prev, rt_history_texel* next, float* out_mean,
+                             float* out_variance) {
+  return accumulate_planes(p, value, position4, normal4, prim, nullptr, nullptr, prev, next, out_mean, out_variance,
+                           "rt_accumulate_plane_host");
+}
+
+int rt_accumulate_plane_moving_host(const rt_accumulate_params* p, const float* value, const float* position4, const float* normal4,
+                                    const int32_t* prim, const float* reproj_position4, const float* reproj_normal4,
+                                    const rt_history_texel* prev, rt_history_texel* next, float* out_mean, float* out_variance) {
+  return accumulate_planes(p, value, position4, normal4, prim, reproj_position4, reproj_normal4, prev, next, out_mean, out_variance,
+                           "rt_accumulate_plane_moving_host");
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 // four taps of a wave fall on two runs of about 65 consecutive 48-byte records, and vertically neighbouring waves share
 // their rows in the CU's cache.  A history record is three 16-byte loads, and three 16-byte stores when it is written.  The
 // taps are taken in the defined order: the summation order is part of the contract.  host statement: accumulate_host.cpp.
+// rt_accumulate_plane_moving is the same kernel with the reprojection planes in place of the guides in the projection and the
+// two geometric tests (two more 16-byte loads per pixel): the instantiation without them is the plain entry's code.
 #include "rt_host.h"
 
 namespace uobrt {
@@ -27,6 +29,8 @@ struct AccumulateArgs {
   const float4* pos;
   const float4* nrm;
   const int* prim;
+  const float4* rpos;              // the reprojection planes (kReproj instantiation only)
+  const float4* rnrm;
   const float4* prev;
   float4* next;
   float* out_mean;
@@ -70,6 +74,7 @@ __global__ __launch_bounds__(64) void rt_accumulate_counters(unsigned long long*
   stats[A_NOCAND] = sum[3];
 }
 
+template <bool kReproj>
 __global__ __launch_bounds__(kThreads) void rt_accumulate_pixels(AccumulateArgs a, unsigned long long* stats) {
   const long g = (long)blockIdx.z * kRowGroupsY + blockIdx.y;
   if (g >= a.groups) return;                            // (the whole workgroup: beyond the last row group)
@@ -89,13 +94,17 @@ __global__ __launch_bounds__(kThreads) void rt_accumulate_pixels(AccumulateArgs 
     float num = 0.0f, num2 = 0.0f, den = 0.0f, cmin = __builtin_inff();
     if (valid && a.prev) {
       const float* rot = p.prev_rot;
-      const float d0 = P.x - p.prev_cam[0], d1 = P.y - p.prev_cam[1], d2 = P.z - p.prev_cam[2];
+      // what is projected and tested against the records: the guides, or where the surface point was then (Pr.w > 0: it was)
+      float4 Pr = P, Nr = N;
+      if constexpr (kReproj) { Pr = a.rpos[c]; Nr = a.rnrm[c]; }
+      const float d0 = Pr.x - p.prev_cam[0], d1 = Pr.y - p.prev_cam[1], d2 = Pr.z - p.prev_cam[2];
       const float q0 = (d0 * rot[0] + d1 * rot[4]) + d2 * rot[8];
       const float q1 = (d0 * rot[1] + d1 * rot[5]) + d2 * rot[9];
       const float q2 = (d0 * rot[2] + d1 * rot[6]) + d2 * rot[10];
       const float fx = (q0 * p.prev_focal_px) / q2 + 0.5f * (float)p.width;   // correctly rounded (the compiler's IEEE division)
       const float fy = (q1 * p.prev_focal_px) / q2 + 0.5f * (float)p.height;
       nocand = !(q2 > 0.0f && fx >= -1.0f && fx < (float)p.width && fy >= -1.0f && fy < (float)p.height);
+      if constexpr (kReproj) nocand = nocand || !(Pr.w > 0.0f);
       if (!nocand) {
         const float xf = floorf(fx), yf = floorf(fy);
         const float ax = fx - xf, ay = fy - yf;
@@ -111,10 +120,10 @@ __global__ __launch_bounds__(kThreads) void rt_accumulate_pixels(AccumulateArgs 
             const float4 r0 = r[0], r1 = r[1], r2 = r[2];   // position | mean, normal | m2, count | prim | pad
             if (!(r2.x > 0.0f)) continue;
             if (a.prim && __float_as_int(r2.y) != pr) continue;
-            const float nd = (N.x * r1.x + N.y * r1.y) + N.z * r1.z;
+            const float nd = (Nr.x * r1.x + Nr.y * r1.y) + Nr.z * r1.z;
             if (!(nd >= p.normal_min_dot)) continue;
-            const float e0 = r0.x - P.x, e1 = r0.y - P.y, e2 = r0.z - P.z;
-            const float pd = (N.x * e0 + N.y * e1) + N.z * e2;
+            const float e0 = r0.x - Pr.x, e1 = r0.y - Pr.y, e2 = r0.z - Pr.z;
+            const float pd = (Nr.x * e0 + Nr.y * e1) + Nr.z * e2;
             if (!(fabsf(pd) <= p.plane_eps)) continue;
             num = num + wt * r0.w;
             num2 = num2 + wt * r1.w;
@@ -156,13 +165,16 @@ __global__ __launch_bounds__(kThreads) void rt_accumulate_pixels(AccumulateArgs 
 int accumulate_stats_words() { return kSlotBase + kCounterSlots * kSlotWords; }
 
 void launch_accumulate(const rt_accumulate_params& p, const float* d_value, const float4* d_pos, const float4* d_nrm, const int* d_prim,
-                       const float4* d_prev, float4* d_next, float* d_out_mean, float* d_out_variance, unsigned long long* stats,
-                       hipStream_t stream) {
+                       const float4* d_rpos, const float4* d_rnrm, const float4* d_prev, float4* d_next, float* d_out_mean,
+                       float* d_out_variance, unsigned long long* stats, hipStream_t stream) {
   const unsigned tiles_x = (unsigned)(((long)p.width + TX - 1) / TX);
   const long groups = ((long)p.height + TY - 1) / TY;
   const dim3 grid(tiles_x, (unsigned)(groups < kRowGroupsY ? groups : kRowGroupsY), (unsigned)((groups + kRowGroupsY - 1) / kRowGroupsY));
-  const AccumulateArgs a{p, groups, d_value, d_pos, d_nrm, d_prim, d_prev, d_next, d_out_mean, d_out_variance};
-  hipLaunchKernelGGL(rt_accumulate_pixels, grid, dim3(kThreads), 0, stream, a, stats);
+  const AccumulateArgs a{p, groups, d_value, d_pos, d_nrm, d_prim, d_rpos, d_rnrm, d_prev, d_next, d_out_mean, d_out_variance};
+  if (d_rpos)
+    hipLaunchKernelGGL(rt_accumulate_pixels<true>, grid, dim3(kThreads), 0, stream, a, stats);
+  else
+    hipLaunchKernelGGL(rt_accumulate_pixels<false>, grid, dim3(kThreads), 0, stream, a, stats);
   hipLaunchKernelGGL(rt_accumulate_counters, dim3(1), dim3(64), 0, stream, stats, (long)p.width * p.height);
 }
 

@@ -97,6 +97,7 @@ static Tuning read_tuning(const rt_config& cfg) {
   if (const char* e = getenv("UOB_RT_SEED_KP")) { const int v = atoi(e); if (v >= 1 && v <= 64) t.seed_kp = v; }
   if (const char* e = getenv("UOB_RT_SEED_CASTERS")) { const int v = atoi(e); if (v >= 0 && v <= 64) t.seed_casters = v; }
   if (const char* e = getenv("UOB_RT_SEED_SPH")) t.seed_sph = atoi(e) != 0;
+  if (const char* e = getenv("UOB_RT_MOTION_BLOCKS_X")) { const int v = atoi(e); if (v >= 1 && v <= kMotionBlocksX) t.motion_blocks_x = v; }
   if (const char* e = getenv("UOB_RT_FILTER_FORM")) t.filter_form = !strcmp(e, "direct") ? kFilterFormDirect : kFilterFormBuiltIn;
   return t;
 }
@@ -970,7 +971,7 @@ rt_ctx::~rt_ctx() {
   hipSetDevice(device);
   if (stream) hipStreamSynchronize(stream);
   if (aux_stream) hipStreamSynchronize(aux_stream);
-  for (SideCall* k : {&query, &shade, &rad, &aov, &filter, &accum})     // no call of any family may still be running
+  for (SideCall* k : {&query, &shade, &rad, &aov, &filter, &accum, &motion})     // no call of any family may still be running
     if (k->ev) hipEventSynchronize(k->ev);
   if (reg_host && reg_owner) hipHostUnregister(reg_host);
 }

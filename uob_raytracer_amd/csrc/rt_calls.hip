@@ -1,7 +1,7 @@
 // rt_calls.hip — the calls beside the frame, over the C ABI (include/uob_rt.h): ray queries (rt_trace_rays, rt_ray_query.hip),
 // shade calls (rt_shade_points, rt_shade.hip), radiance calls (rt_radiance_rays, rt_radiance.hip), AOV passes
-// (rt_render_aov, rt_aov.hip), filter calls (rt_filter_plane, rt_filter.hip) and accumulate calls (rt_accumulate_plane,
-// rt_accumulate.hip).  Each family has an enqueue on the caller's stream (the *_device entry), a blocking entry for
+// (rt_render_aov, rt_aov.hip), filter calls (rt_filter_plane, rt_filter.hip), accumulate calls (rt_accumulate_plane,
+// rt_accumulate.hip) and motion calls with their snapshot (rt_motion_planes, rt_motion.hip).  Each family has an enqueue on the caller's stream (the *_device entry), a blocking entry for
 // host arrays that stages them through the family's device buffer, and a stats export.  What the families share is written
 // once: the steps around a call (call_prepare / reader_begin / call_end), the blocking entry (run_blocking) and the stats
 // reader (read_stats).  Which operation waits for which is DESIGN.md 4.9 (rt_host.h wait_scene_readers, wait_aov, wait_scene).
@@ -261,14 +261,93 @@ static int enqueue_filter(rt_ctx* c, const rt_filter_params& p, const float* d_v
 // One accumulate call of a single-device context on stream s (device planes of c->device); arguments checked.  Not a reader
 // of the scene: it waits for the accumulate call before it, whose counters it takes over, and for nothing else.
 static int enqueue_accumulate(rt_ctx* c, const rt_accumulate_params& p, const float* d_value, const float4* d_pos, const float4* d_nrm,
-                              const int* d_prim, const float4* d_prev, float4* d_next, float* d_mean, float* d_var, hipStream_t s) {
+                              const int* d_prim, const float4* d_rpos, const float4* d_rnrm, const float4* d_prev, float4* d_next,
+                              float* d_mean, float* d_var, hipStream_t s) {
   const int words = accumulate_stats_words();
   const int rc = call_prepare(c, &c->accum, words);
   if (rc != RT_OK) return rc;
   if (c->accum.pending) HIP_TRY(hipStreamWaitEvent(s, c->accum.ev, 0));
   HIP_TRY(hipMemsetAsync(c->accum.d_stats, 0, (size_t)words * sizeof(unsigned long long), s));
-  launch_accumulate(p, d_value, d_pos, d_nrm, d_prim, d_prev, d_next, d_mean, d_var, c->accum.d_stats, s);
+  launch_accumulate(p, d_value, d_pos, d_nrm, d_prim, d_rpos, d_rnrm, d_prev, d_next, d_mean, d_var, c->accum.d_stats, s);
   return call_end(c, &c->accum, s);
+}
+
+// The two entries for device planes and the two for host arrays; reproj: the entry takes the reprojection planes (fn names it)
+static int accumulate_device_entry(rt_ctx* c, const rt_accumulate_params* p, const void* d_value, const void* d_position4,
+                                   const void* d_normal4, const void* d_prim, const void* d_rpos, const void* d_rnrm, const void* d_prev,
+                                   void* d_next, void* d_out_mean, void* d_out_variance, void* hip_stream, const char* fn) {
+  if (!c) { set_error("%s: ctx is NULL", fn); return RT_E_INVALID; }
+  int rc = accumulate_check(p, d_value, d_position4, d_normal4, d_prev, d_next, fn);
+  if (rc == RT_OK) rc = accumulate_reproj_check(d_rpos, d_rnrm, fn);
+  if (rc != RT_OK) return rc;
+  if ((((uintptr_t)d_position4 | (uintptr_t)d_normal4 | (uintptr_t)d_prev | (uintptr_t)d_next) & 15) != 0) {
+    set_error("%s: d_position4 / d_normal4 / d_prev / d_next is not 16-byte aligned", fn); return RT_E_INVALID;
+  }
+  if ((((uintptr_t)d_rpos | (uintptr_t)d_rnrm) & 15) != 0) {
+    set_error("%s: d_reproj_position4 / d_reproj_normal4 is not 16-byte aligned", fn); return RT_E_INVALID;
+  }
+  DeviceGuard guard;
+  return enqueue_accumulate(lead_ctx(c), *p, (const float*)d_value, (const float4*)d_position4, (const float4*)d_normal4,
+                            (const int*)d_prim, (const float4*)d_rpos, (const float4*)d_rnrm, (const float4*)d_prev, (float4*)d_next,
+                            (float*)d_out_mean, (float*)d_out_variance, (hipStream_t)hip_stream);
+}
+
+static int accumulate_blocking_entry(rt_ctx* c, const rt_accumulate_params* p, const float* value, const float* position4,
+                                     const float* normal4, const int32_t* prim, const float* rpos, const float* rnrm,
+                                     const rt_history_texel* prev, rt_history_texel* next, float* out_mean, float* out_variance,
+                                     const char* fn) {
+  if (!c) { set_error("%s: ctx is NULL", fn); return RT_E_INVALID; }
+  int rc = accumulate_check(p, value, position4, normal4, prev, next, fn);
+  if (rc == RT_OK) rc = accumulate_reproj_check(rpos, rnrm, fn);
+  if (rc != RT_OK) return rc;
+  c = lead_ctx(c);
+  DeviceGuard guard;
+  const size_t n = (size_t)p->width * p->height;
+  // (what the kernel loads and stores as float4 first: the start of the staging buffer is aligned for that, and every one
+  // of these is a multiple of 16 bytes long)
+  IoSlot io[10] = {{(void*)position4, n * 16, true}, {(void*)normal4, n * 16, true}, {(void*)rpos, n * 16, true}, {(void*)rnrm, n * 16, true},
+                   {(void*)prev, n * 48, true},      {next, n * 48, false},          {(void*)value, n * 4, true}, {(void*)prim, n * 4, true},
+                   {out_mean, n * 4, false},         {out_variance, n * 4, false}};
+  return run_blocking(c, &c->accum, io, 10, [&] {
+    return enqueue_accumulate(c, *p, (const float*)io[6].dev, (const float4*)io[0].dev, (const float4*)io[1].dev, (const int*)io[7].dev,
+                              (const float4*)io[2].dev, (const float4*)io[3].dev, (const float4*)io[4].dev, (float4*)io[5].dev,
+                              (float*)io[8].dev, (float*)io[9].dev, c->stream);
+  });
+}
+
+// ---- motion calls and their snapshot (rt_motion_snapshot / rt_motion_planes*, rt_motion.hip) ------------------------------
+// A snapshot or a motion call on stream s: prepared, behind the latest edit and the family's previous call.  Readers of the
+// scene (wait_scene_readers lists the family, so edits wait for them); frames and AOV passes neither wait nor are waited for.
+static int motion_begin(rt_ctx* c, hipStream_t s) {
+  const bool first = !c->motion.d_stats;
+  const int rc = call_prepare(c, &c->motion, motion_stats_words());
+  if (rc != RT_OK) return rc;
+  HIP_TRY(wait_scene(c, s));
+  if (c->motion.pending) HIP_TRY(hipStreamWaitEvent(s, c->motion.ev, 0));
+  // (a snapshot writes no counters: before the first motion call the export reads zeros)
+  if (first) HIP_TRY(hipMemsetAsync(c->motion.d_stats, 0, (size_t)motion_stats_words() * sizeof(unsigned long long), s));
+  return RT_OK;
+}
+
+// The context that answers a motion call holds a snapshot of its current triangle count
+static int check_snapshot(const rt_ctx* c, const char* fn) {
+  if (!c->motion_taken) { set_error("%s: the context holds no snapshot (rt_motion_snapshot)", fn); return RT_E_INVALID; }
+  if (c->motion_n != c->n) {
+    set_error("%s: the snapshot holds %d triangles, the scene %d (take a new rt_motion_snapshot)", fn, c->motion_n, c->n); return RT_E_INVALID;
+  }
+  return RT_OK;
+}
+
+// One motion call of a single-device context on stream s (device planes of c->device); count > 0, arguments checked
+static int enqueue_motion(rt_ctx* c, const int* d_prim, const float4* d_pos, const float4* d_nrm, long count, float4* d_out_pos,
+                          float4* d_out_nrm, hipStream_t s) {
+  const int words = motion_stats_words();
+  const int rc = motion_begin(c, s);
+  if (rc != RT_OK) return rc;
+  HIP_TRY(hipMemsetAsync(c->motion.d_stats, 0, (size_t)words * sizeof(unsigned long long), s));
+  launch_motion(c->d_verts, c->motion_verts, c->motion_normals, c->n, d_prim, d_pos, d_nrm, count, d_out_pos, d_out_nrm,
+                c->tune.motion_blocks_x, c->motion.d_stats, s);
+  return call_end(c, &c->motion, s);
 }
 
 extern "C" {
@@ -276,35 +355,117 @@ extern "C" {
 int rt_accumulate_plane_device(rt_ctx* c, const rt_accumulate_params* p, const void* d_value, const void* d_position4,
                                const void* d_normal4, const void* d_prim, const void* d_prev, void* d_next, void* d_out_mean,
                                void* d_out_variance, void* hip_stream) {
-  if (!c) { set_error("rt_accumulate_plane_device: ctx is NULL"); return RT_E_INVALID; }
-  const int rc = accumulate_check(p, d_value, d_position4, d_normal4, d_prev, d_next, "rt_accumulate_plane_device");
-  if (rc != RT_OK) return rc;
-  if ((((uintptr_t)d_position4 | (uintptr_t)d_normal4 | (uintptr_t)d_prev | (uintptr_t)d_next) & 15) != 0) {
-    set_error("rt_accumulate_plane_device: d_position4 / d_normal4 / d_prev / d_next is not 16-byte aligned"); return RT_E_INVALID;
-  }
-  DeviceGuard guard;
-  return enqueue_accumulate(lead_ctx(c), *p, (const float*)d_value, (const float4*)d_position4, (const float4*)d_normal4,
-                            (const int*)d_prim, (const float4*)d_prev, (float4*)d_next, (float*)d_out_mean, (float*)d_out_variance,
-                            (hipStream_t)hip_stream);
+  return accumulate_device_entry(c, p, d_value, d_position4, d_normal4, d_prim, nullptr, nullptr, d_prev, d_next, d_out_mean,
+                                 d_out_variance, hip_stream, "rt_accumulate_plane_device");
 }
 
 int rt_accumulate_plane(rt_ctx* c, const rt_accumulate_params* p, const float* value, const float* position4, const float* normal4,
                         const int32_t* prim, const rt_history_texel* prev, rt_history_texel* next, float* out_mean,
                         float* out_variance) {
-  if (!c) { set_error("rt_accumulate_plane: ctx is NULL"); return RT_E_INVALID; }
-  const int rc = accumulate_check(p, value, position4, normal4, prev, next, "rt_accumulate_plane");
-  if (rc != RT_OK) return rc;
+  return accumulate_blocking_entry(c, p, value, position4, normal4, prim, nullptr, nullptr, prev, next, out_mean, out_variance,
+                                   "rt_accumulate_plane");
+}
+
+int rt_accumulate_plane_moving_device(rt_ctx* c, const rt_accumulate_params* p, const void* d_value, const void* d_position4,
+                                      const void* d_normal4, const void* d_prim, const void* d_reproj_position4,
+                                      const void* d_reproj_normal4, const void* d_prev, void* d_next, void* d_out_mean,
+                                      void* d_out_variance, void* hip_stream) {
+  return accumulate_device_entry(c, p, d_value, d_position4, d_normal4, d_prim, d_reproj_position4, d_reproj_normal4, d_prev, d_next,
+                                 d_out_mean, d_out_variance, hip_stream, "rt_accumulate_plane_moving_device");
+}
+
+int rt_accumulate_plane_moving(rt_ctx* c, const rt_accumulate_params* p, const float* value, const float* position4,
+                               const float* normal4, const int32_t* prim, const float* reproj_position4, const float* reproj_normal4,
+                               const rt_history_texel* prev, rt_history_texel* next, float* out_mean, float* out_variance) {
+  return accumulate_blocking_entry(c, p, value, position4, normal4, prim, reproj_position4, reproj_normal4, prev, next, out_mean,
+                                   out_variance, "rt_accumulate_plane_moving");
+}
+
+int rt_motion_snapshot(rt_ctx* c, void* hip_stream) {
+  if (!c) { set_error("rt_motion_snapshot: ctx is NULL"); return RT_E_INVALID; }
   c = lead_ctx(c);
   DeviceGuard guard;
-  const size_t n = (size_t)p->width * p->height;
-  // (what the kernel loads and stores as float4 first: the start of the staging buffer is aligned for that, and every one
-  // of these is a multiple of 16 bytes long)
-  IoSlot io[8] = {{(void*)position4, n * 16, true}, {(void*)normal4, n * 16, true}, {(void*)prev, n * 48, true}, {next, n * 48, false},
-                  {(void*)value, n * 4, true},      {(void*)prim, n * 4, true},     {out_mean, n * 4, false},    {out_variance, n * 4, false}};
-  return run_blocking(c, &c->accum, io, 8, [&] {
-    return enqueue_accumulate(c, *p, (const float*)io[4].dev, (const float4*)io[0].dev, (const float4*)io[1].dev, (const int*)io[5].dev,
-                              (const float4*)io[2].dev, (float4*)io[3].dev, (float*)io[6].dev, (float*)io[7].dev, c->stream);
+  const hipStream_t s = (hipStream_t)hip_stream;
+  const int rc = motion_begin(c, s);
+  if (rc != RT_OK) return rc;
+  const size_t n = (size_t)c->n;
+  // (a larger scene than any snapshot before: hipFree waits for the motion call still reading the old buffers)
+  if (3 * n * sizeof(float4) > c->motion_verts.bytes || !c->motion_verts) {
+    c->motion_taken = false;
+    if (c->motion_verts.alloc(3 * n) != hipSuccess || c->motion_normals.alloc(n) != hipSuccess) {
+      c->motion_verts.reset(); c->motion_normals.reset();
+      return alloc_failed();
+    }
+  }
+  if (n) {
+    HIP_TRY(hipMemcpyAsync(c->motion_verts, c->d_verts, 3 * n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c->motion_normals, c->d_normals, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
+  }
+  c->motion_n = c->n;
+  c->motion_taken = true;
+  return call_end(c, &c->motion, s);
+}
+
+int rt_motion_release(rt_ctx* c) {
+  if (!c) { set_error("rt_motion_release: ctx is NULL"); return RT_E_INVALID; }
+  c = lead_ctx(c);
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->motion.pending) HIP_TRY(hipEventSynchronize(c->motion.ev));   // (no snapshot copy or motion call still uses the buffers)
+  c->motion_verts.reset();
+  c->motion_normals.reset();
+  c->motion_n = 0;
+  c->motion_taken = false;
+  return RT_OK;
+}
+
+int rt_debug_motion_info(rt_ctx* c, int32_t* snapshot_triangles) {
+  if (!c || !snapshot_triangles) { set_error("rt_debug_motion_info: NULL argument"); return RT_E_INVALID; }
+  c = lead_ctx(c);
+  *snapshot_triangles = c->motion_taken ? c->motion_n : 0;
+  return RT_OK;
+}
+
+int rt_motion_planes_device(rt_ctx* c, const void* d_prim, const void* d_position4, const void* d_normal4, int64_t count,
+                            void* d_out_prev_position4, void* d_out_prev_normal4, void* hip_stream) {
+  if (!c) { set_error("rt_motion_planes_device: ctx is NULL"); return RT_E_INVALID; }
+  int rc = motion_check(d_prim, d_position4, d_normal4, count, d_out_prev_position4, d_out_prev_normal4, "rt_motion_planes_device");
+  if (rc != RT_OK) return rc;
+  if ((((uintptr_t)d_position4 | (uintptr_t)d_normal4 | (uintptr_t)d_out_prev_position4 | (uintptr_t)d_out_prev_normal4) & 15) != 0) {
+    set_error("rt_motion_planes_device: d_position4 / d_normal4 / d_out_prev_position4 / d_out_prev_normal4 is not 16-byte aligned");
+    return RT_E_INVALID;
+  }
+  c = lead_ctx(c);
+  rc = check_snapshot(c, "rt_motion_planes_device");
+  if (rc != RT_OK || count == 0) return rc;
+  DeviceGuard guard;
+  return enqueue_motion(c, (const int*)d_prim, (const float4*)d_position4, (const float4*)d_normal4, (long)count,
+                        (float4*)d_out_prev_position4, (float4*)d_out_prev_normal4, (hipStream_t)hip_stream);
+}
+
+int rt_motion_planes(rt_ctx* c, const int32_t* prim, const float* position4, const float* normal4, int64_t count,
+                     float* out_prev_position4, float* out_prev_normal4) {
+  if (!c) { set_error("rt_motion_planes: ctx is NULL"); return RT_E_INVALID; }
+  int rc = motion_check(prim, position4, normal4, count, out_prev_position4, out_prev_normal4, "rt_motion_planes");
+  if (rc != RT_OK) return rc;
+  c = lead_ctx(c);
+  rc = check_snapshot(c, "rt_motion_planes");
+  if (rc != RT_OK || count == 0) return rc;
+  DeviceGuard guard;
+  const size_t n = (size_t)count;
+  // (the float4 planes first: the start of the staging buffer is aligned for them)
+  IoSlot io[5] = {{(void*)position4, n * 16, true}, {(void*)normal4, n * 16, true}, {out_prev_position4, n * 16, false},
+                  {out_prev_normal4, n * 16, false}, {(void*)prim, n * 4, true}};
+  return run_blocking(c, &c->motion, io, 5, [&] {
+    return enqueue_motion(c, (const int*)io[4].dev, (const float4*)io[0].dev, (const float4*)io[1].dev, (long)count, (float4*)io[2].dev,
+                          (float4*)io[3].dev, c->stream);
   });
+}
+
+int rt_debug_motion_stats(rt_ctx* c, uint64_t out[8]) {
+  const int rc = read_stats(c, &rt_ctx::motion, -1, out);
+  if (rc == RT_OK) out[6] = out[7] = 0;
+  return rc;
 }
 
 int rt_debug_accumulate_stats(rt_ctx* c, uint64_t out[8]) {

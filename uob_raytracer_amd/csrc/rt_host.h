@@ -100,13 +100,26 @@ int filter_check(const rt_filter_params* p, const void* value, const void* posit
                  const char* fn);
 // rt_accumulate.hip: the temporal reprojection of per-pixel planes (include/uob_rt.h rt_accumulate_plane): one
 // launch over the plane in the filter's tiles (kFilterTX x kFilterTY adjacent pixels) and one that sums the counters
+// d_rpos / d_rnrm: the reprojection planes of rt_accumulate_plane_moving, both or neither (then the launch is the plain entry's)
 int accumulate_stats_words();
 void launch_accumulate(const rt_accumulate_params& p, const float* d_value, const float4* d_pos, const float4* d_nrm, const int* d_prim,
-                       const float4* d_prev, float4* d_next, float* d_out_mean, float* d_out_variance, unsigned long long* stats,
-                       hipStream_t stream);
+                       const float4* d_rpos, const float4* d_rnrm, const float4* d_prev, float4* d_next, float* d_out_mean,
+                       float* d_out_variance, unsigned long long* stats, hipStream_t stream);
 // accumulate_host.cpp: the ranges of rt_accumulate_params and the plane pointers, before anything else is looked at
 int accumulate_check(const rt_accumulate_params* p, const void* value, const void* position4, const void* normal4, const void* prev,
                      const void* next, const char* fn);
+int accumulate_reproj_check(const void* reproj_position4, const void* reproj_normal4, const char* fn);
+// rt_motion.hip: where each element's surface point was in the snapshot's scene (include/uob_rt.h rt_motion_planes, DESIGN.md
+// 4.8c): one launch over the elements, kMotionBlocksX workgroups of 256 per grid.x (HIP keeps grid.x * block.x below 2^32;
+// this is 2^30 elements) and the rest in grid.y, and one launch that sums the counters.  blocks_x: Tuning::motion_blocks_x
+constexpr int kMotionBlocksX = 1 << 22;
+int motion_stats_words();
+void launch_motion(const float4* d_v_now, const float4* d_v_then, const float4* d_n_then, int n, const int* d_prim, const float4* d_pos,
+                   const float4* d_nrm, long count, float4* d_out_pos, float4* d_out_nrm, int blocks_x, unsigned long long* stats,
+                   hipStream_t stream);
+// motion_host.cpp: the element planes and their count, before anything else is looked at
+int motion_check(const void* prim, const void* position4, const void* normal4, int64_t count, const void* out_prev_position4,
+                 const void* out_prev_normal4, const char* fn);
 // rt_tile_sort.hip: the vertices' box, and the mesh kernel's tiled order and per-tile data (host arithmetic)
 void vertex_box(const float* vertices4, int n, float lo[3], float hi[3]);
 std::vector<int> tiled_order(const float* v4, int n, bool morton);
@@ -140,6 +153,7 @@ struct Tuning {
   int mask_debug = 0;         // UOB_RT_MASK_DEBUG: mesh kernel, switch single tile-mask stages off (fault isolation)
   bool tile_morton = false;   // UOB_RT_TILE_ORDER=morton: the mesh kernel's tiles in plain Morton order (tiled_order)
   int filter_form = 0;        // UOB_RT_FILTER_FORM=direct: every filter pass takes its taps from the caches (tools/filter_time.py)
+  int motion_blocks_x = 0;    // UOB_RT_MOTION_BLOCKS_X: workgroups per grid.x of the motion kernel (1 .. 2^22; tests of its grid.y)
   bool no_seed = false;       // UOB_RT_NO_SEED=1: no tile-seed pre-pass, every job of the wave kernel starts unseeded
   int seed_rows = 16;         // UOB_RT_SEED_ROWS: rows of a seed tile (1 .. 64); the default is the default band height
   // what the pre-pass keeps (rt_device.h FrameParams seed_*_cap; the defaults by profiles/tile_seed_wide_ab.txt).  (1, 0, 0)
@@ -325,6 +339,14 @@ struct rt_ctx {
   // before them (they share the counters and the staging) and are waited for by the next one and the destructor.  They
   // need no scratch: the history buffers are the caller's
   uobrt::SideCall accum;
+  // Motion calls (rt_motion.hip) and the snapshot they read (rt_motion_snapshot): the live scene in original order as the
+  // previous view saw it, vertices [3 * motion_n] and normals [motion_n]; the buffers exist from the first snapshot to
+  // rt_motion_release and only grow.  motion_taken: there is a snapshot, of motion_n triangles.  Snapshots and motion calls are one family of scene
+  // readers (wait_scene_readers): they wait for a pending edit and for each other, and edits wait for them
+  uobrt::SideCall motion;
+  uobrt::DevMem<float4> motion_verts, motion_normals;
+  int motion_n = 0;
+  bool motion_taken = false;
 };
 
 namespace uobrt {
@@ -352,7 +374,7 @@ inline hipError_t wait_aov(const rt_ctx* c, hipStream_t s) {
 // Whatever rewrites the scene, or shares a reader family's counters and staging, waits for the latest call of every
 // reader family.  The ONE place that lists them: a new family of readers is added here and nowhere else.
 inline int wait_scene_readers(const rt_ctx* c, hipStream_t s) {
-  for (const SideCall* k : {&c->query, &c->shade, &c->rad})
+  for (const SideCall* k : {&c->query, &c->shade, &c->rad, &c->motion})
     if (k->pending) HIP_TRY(hipStreamWaitEvent(s, k->ev, 0));
   return RT_OK;
 }

@@ -40,6 +40,9 @@ EXPORTS = (
     "rt_filter_params_default", "rt_filter_plane", "rt_filter_plane_device", "rt_debug_filter_stats", "rt_filter_plane_host",
     "rt_accumulate_params_default", "rt_accumulate_plane", "rt_accumulate_plane_device", "rt_debug_accumulate_stats",
     "rt_accumulate_plane_host",
+    "rt_motion_snapshot", "rt_motion_release", "rt_debug_motion_info", "rt_motion_planes", "rt_motion_planes_device",
+    "rt_motion_planes_host", "rt_debug_motion_stats",
+    "rt_accumulate_plane_moving", "rt_accumulate_plane_moving_device", "rt_accumulate_plane_moving_host",
 )
 
 # rt_debug_live_device_objects slots
@@ -63,6 +66,9 @@ FILTER_STATS_KEYS = ("pixels", "passes", "accepted_taps", "valid_pixels", "kept"
 # rt_debug_accumulate_stats slots
 ACCUMULATE_STATS_KEYS = ("pixels", "valid_pixels", "found_history", "accepted_taps", "no_candidate", "reserved5", "reserved6",
                          "reserved7")
+
+# rt_debug_motion_stats slots
+MOTION_STATS_KEYS = ("elements", "valid_elements", "moved", "unmoved", "copied", "prim_out_of_range", "reserved6", "reserved7")
 
 _lib = None
 
@@ -154,6 +160,16 @@ def lib():
         L.rt_accumulate_plane_device.argtypes = [vp, ap] + [vp] * 9
         L.rt_debug_accumulate_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_accumulate_plane_host.argtypes = [ap, fp, fp, fp, ip, fp, fp, fp, fp]
+        L.rt_motion_snapshot.argtypes = [vp, vp]
+        L.rt_motion_release.argtypes = [vp]
+        L.rt_debug_motion_info.argtypes = [vp, ip]
+        L.rt_motion_planes.argtypes = [vp, ip, fp, fp, C.c_int64, fp, fp]
+        L.rt_motion_planes_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
+        L.rt_motion_planes_host.argtypes = [fp, fp, fp, C.c_int32, ip, fp, fp, C.c_int64, fp, fp]
+        L.rt_debug_motion_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_accumulate_plane_moving.argtypes = [vp, ap, fp, fp, fp, ip, fp, fp, fp, fp, fp, fp]
+        L.rt_accumulate_plane_moving_device.argtypes = [vp, ap] + [vp] * 11
+        L.rt_accumulate_plane_moving_host.argtypes = [ap, fp, fp, fp, ip, fp, fp, fp, fp, fp, fp]
         L.rt_debug_block_costs.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int32]
         L.rt_debug_world_masks.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.rt_debug_wave_timeline.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -389,16 +405,66 @@ def _accumulate_host_planes(value, position4, normal4, prim, prev):
     return h, w, v, pos, nrm, prim, prev, nxt, np.empty((h, w), np.float32), np.empty((h, w), np.float32)
 
 
-def accumulate_plane_host(value, position4, normal4, prim=None, prev=None, params=None, **kw):
+def _reproj_host_planes(reproj_position4, reproj_normal4, h, w):
+    """The optional reprojection planes of a blocking accumulate call as C-contiguous float32 [h, w, 4] arrays (None stays None;
+    one without the other is the library's to refuse)."""
+    out = []
+    for name, a in (("reproj_position4", reproj_position4), ("reproj_normal4", reproj_normal4)):
+        if a is not None:
+            a = np.ascontiguousarray(a, np.float32)
+            if a.shape != (h, w, 4):
+                raise ValueError("%s must have the shape [%d, %d, 4]" % (name, h, w))
+        out.append(a)
+    return out
+
+
+def _fp_or_none(a):
+    return _fp(a) if a is not None else None
+
+
+def accumulate_plane_host(value, position4, normal4, prim=None, prev=None, params=None, reproj_position4=None, reproj_normal4=None,
+                          **kw):
     """The temporal reprojection on the host (rt_accumulate_plane_host; needs no device): value float32 [h, w], position4 /
     normal4 float32 [h, w, 4], prim int32 [h, w] or None, prev = the `next` of the previous call or None -> (next float32
     [h, w, 12], mean [h, w], variance [h, w]).  params: an abi.RtAccumulateParams, or kw for accumulate_params (prev_rot,
-    prev_cam, prev_focal, aa_x, normal_min_dot, plane_eps, max_history)."""
+    prev_cam, prev_focal, aa_x, normal_min_dot, plane_eps, max_history).  reproj_position4 / reproj_normal4 float32 [h, w, 4]
+    (motion_planes' outputs): rt_accumulate_plane_moving_host."""
     h, w, v, pos, nrm, prim, prev, nxt, mean, var = _accumulate_host_planes(value, position4, normal4, prim, prev)
+    rpos, rnrm = _reproj_host_planes(reproj_position4, reproj_normal4, h, w)
     p = params if params is not None else accumulate_params(w, h, **kw)
-    _check(lib().rt_accumulate_plane_host(C.byref(p), _fp(v), _fp(pos), _fp(nrm), _ip(prim), _fp(prev) if prev is not None else None,
-                                          _fp(nxt), _fp(mean), _fp(var)))
+    if rpos is None and rnrm is None:
+        _check(lib().rt_accumulate_plane_host(C.byref(p), _fp(v), _fp(pos), _fp(nrm), _ip(prim), _fp_or_none(prev), _fp(nxt), _fp(mean),
+                                              _fp(var)))
+    else:
+        _check(lib().rt_accumulate_plane_moving_host(C.byref(p), _fp(v), _fp(pos), _fp(nrm), _ip(prim), _fp_or_none(rpos),
+                                                     _fp_or_none(rnrm), _fp_or_none(prev), _fp(nxt), _fp(mean), _fp(var)))
     return nxt, mean, var
+
+
+def _motion_host_planes(prim, position4, normal4):
+    """The element planes of a blocking motion call: prim int32 [...], position4 / normal4 float32 [..., 4] of the same
+    leading shape -> (count, the three C-contiguous, and fresh outputs shaped like the float4 inputs)."""
+    prim = np.ascontiguousarray(prim, np.int32)
+    pos = np.ascontiguousarray(position4, np.float32)
+    nrm = np.ascontiguousarray(normal4, np.float32)
+    if pos.shape != prim.shape + (4,) or nrm.shape != pos.shape:
+        raise ValueError("position4 and normal4 must have the shape of prim with a last axis of 4")
+    return prim.size, prim, pos, nrm, np.empty_like(pos), np.empty_like(pos)
+
+
+def motion_planes_host(vertices_now, vertices_then, normals_then, prim, position4, normal4):
+    """Where each element's surface point was in a previous scene, on the host (rt_motion_planes_host; needs no device):
+    vertices_now, vertices_then float32 [3n, 4], normals_then [n, 4] (the layouts of Scene.packed / scene_data), prim int32
+    [...], position4 / normal4 float32 [..., 4] -> (prev_position4, prev_normal4) shaped like position4."""
+    vn = np.ascontiguousarray(vertices_now, np.float32)
+    vt = np.ascontiguousarray(vertices_then, np.float32)
+    nt = np.ascontiguousarray(normals_then, np.float32)
+    n = nt.shape[0]
+    if vn.shape != (3 * n, 4) or vt.shape != (3 * n, 4) or nt.shape != (n, 4):
+        raise ValueError("vertices_now and vertices_then must be [3n, 4] and normals_then [n, 4]")
+    count, prim, pos, nrm, opos, onrm = _motion_host_planes(prim, position4, normal4)
+    _check(lib().rt_motion_planes_host(_fp(vn), _fp(vt), _fp(nt), n, _ip(prim), _fp(pos), _fp(nrm), count, _fp(opos), _fp(onrm)))
+    return opos, onrm
 
 
 def default_config():
@@ -546,6 +612,7 @@ class RayTracer:
         # the device the context's queries run on (devices[0]; None: the device that was current at rt_init)
         self.device = cfg.devices[0] if cfg.num_devices >= 1 else (cfg.device if cfg.device >= 0 else None)
         self._history = None        # render_accumulated_light: [the two history tensors, which is current, the view, frames]
+        self._moving = False        # a moving=True call of render_accumulated_light left a snapshot
 
     @staticmethod
     def _update_flags(reorder, device_tiles):
@@ -1065,22 +1132,78 @@ class RayTracer:
         out = term * torch.where(hit, vis_f, zero)
         return (out, term, vis, vis_f) if want_parts else out
 
-    def accumulate_plane(self, value, position4, normal4, prim=None, prev=None, params=None, **kw):
+    def motion_snapshot(self, stream=None):
+        """Keep the scene as it is now as "the previous view's" (rt_motion_snapshot): enqueued on stream (a torch stream or a
+        raw hipStream_t; default: torch's current stream), without synchronising.  Take it after the frame or AOV pass of a view
+        and before the pose or update that makes the next one."""
+        _check(lib().rt_motion_snapshot(self._h, C.c_void_p(self._raw_stream(stream, self._torch_device()))))
+
+    def motion_release(self):
+        """Free the snapshot (rt_motion_release); motion calls are refused until the next motion_snapshot."""
+        _check(lib().rt_motion_release(self._h))
+
+    def motion_info(self):
+        """Triangles of the context's snapshot, 0 without one (rt_debug_motion_info)."""
+        out = C.c_int32()
+        _check(lib().rt_debug_motion_info(self._h, C.byref(out)))
+        return int(out.value)
+
+    def motion_planes(self, prim, position4, normal4):
+        """Where each element's surface point was in the snapshot's scene (rt_motion_planes), blocking: numpy planes as
+        runtime.motion_planes_host takes them, and the same bits -> (prev_position4, prev_normal4)."""
+        count, prim, pos, nrm, opos, onrm = _motion_host_planes(prim, position4, normal4)
+        _check(lib().rt_motion_planes(self._h, _ip(prim), _fp(pos), _fp(nrm), count, _fp(opos), _fp(onrm)))
+        return opos, onrm
+
+    def motion_planes_device(self, prim, position4, normal4, out_position4=None, out_normal4=None, stream=None):
+        """Enqueue rt_motion_planes_device on torch tensors of the context's device, without synchronising.  prim: int32 [...];
+        position4, normal4: float32 [..., 4] of the same leading shape (the AOV planes); out_position4, out_normal4: like
+        position4, allocated when None.  stream: a torch stream or a raw hipStream_t (default: torch's current stream)."""
+        import torch
+        dev = self._torch_device()
+        if not isinstance(prim, torch.Tensor):
+            raise TypeError("prim must be a torch tensor")
+        shape = tuple(prim.shape)
+        _need("prim", prim, torch.int32, shape, dev)
+        _need("position4", position4, torch.float32, shape + (4,), dev)
+        _need("normal4", normal4, torch.float32, shape + (4,), dev)
+        out_position4 = _out("out_position4", out_position4, torch.float32, shape + (4,), dev)
+        out_normal4 = _out("out_normal4", out_normal4, torch.float32, shape + (4,), dev)
+        raw = self._raw_stream(stream, dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        _check(lib().rt_motion_planes_device(self._h, ptr(prim), ptr(position4), ptr(normal4), prim.numel(), ptr(out_position4),
+                                             ptr(out_normal4), C.c_void_p(raw)))
+        return out_position4, out_normal4
+
+    def motion_stats(self):
+        """Work counters of the context's most recent motion call (rt_debug_motion_stats): dict of MOTION_STATS_KEYS."""
+        return self._stats("rt_debug_motion_stats", MOTION_STATS_KEYS)
+
+    def accumulate_plane(self, value, position4, normal4, prim=None, prev=None, params=None, reproj_position4=None,
+                         reproj_normal4=None, **kw):
         """The temporal reprojection of a per-pixel plane on the device (rt_accumulate_plane), blocking: numpy planes as
-        runtime.accumulate_plane_host takes them, and the same bits -> (next, mean, variance)."""
+        runtime.accumulate_plane_host takes them, and the same bits -> (next, mean, variance).  With reproj_position4 /
+        reproj_normal4 (motion_planes' outputs): rt_accumulate_plane_moving."""
         h, w, v, pos, nrm, prim, prev, nxt, mean, var = _accumulate_host_planes(value, position4, normal4, prim, prev)
+        rpos, rnrm = _reproj_host_planes(reproj_position4, reproj_normal4, h, w)
         p = params if params is not None else accumulate_params(w, h, **kw)
-        _check(lib().rt_accumulate_plane(self._h, C.byref(p), _fp(v), _fp(pos), _fp(nrm), _ip(prim),
-                                         _fp(prev) if prev is not None else None, _fp(nxt), _fp(mean), _fp(var)))
+        if rpos is None and rnrm is None:
+            _check(lib().rt_accumulate_plane(self._h, C.byref(p), _fp(v), _fp(pos), _fp(nrm), _ip(prim), _fp_or_none(prev), _fp(nxt),
+                                             _fp(mean), _fp(var)))
+        else:
+            _check(lib().rt_accumulate_plane_moving(self._h, C.byref(p), _fp(v), _fp(pos), _fp(nrm), _ip(prim), _fp_or_none(rpos),
+                                                    _fp_or_none(rnrm), _fp_or_none(prev), _fp(nxt), _fp(mean), _fp(var)))
         return nxt, mean, var
 
     def accumulate_plane_device(self, value, position4, normal4, prim=None, prev=None, next=None, out_mean=None, out_variance=None,
-                                want_mean=True, want_variance=True, stream=None, params=None, **kw):
+                                want_mean=True, want_variance=True, stream=None, params=None, reproj_position4=None,
+                                reproj_normal4=None, **kw):
         """Enqueue rt_accumulate_plane_device on torch tensors of the context's device, without synchronising.  value: float32
         [h, w]; position4, normal4: float32 [h, w, 4] (the AOV planes); prim: int32 [h, w] or None; prev: float32 [h, w, 12]
         (the `next` of the previous call) or None; next, out_mean, out_variance: allocated when None (the two planes only
         when wanted).  stream: a torch stream or a raw hipStream_t (default: torch's current stream).  Returns (next, mean,
-        variance), None for a plane that was not asked for."""
+        variance), None for a plane that was not asked for.  With reproj_position4 / reproj_normal4, float32 [h, w, 4]
+        (motion_planes_device's outputs): rt_accumulate_plane_moving_device."""
         import torch
         dev = self._torch_device()
         h, w = _guide_tensors(value, position4, normal4, dev)
@@ -1096,8 +1219,16 @@ class RayTracer:
         p = params if params is not None else accumulate_params(w, h, **kw)
         raw = self._raw_stream(stream, dev)
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-        _check(lib().rt_accumulate_plane_device(self._h, C.byref(p), ptr(value), ptr(position4), ptr(normal4), ptr(prim), ptr(prev),
-                                                ptr(next), ptr(out_mean), ptr(out_variance), C.c_void_p(raw)))
+        for name, t in (("reproj_position4", reproj_position4), ("reproj_normal4", reproj_normal4)):
+            if t is not None:
+                _need(name, t, torch.float32, (h, w, 4), dev)
+        if reproj_position4 is None and reproj_normal4 is None:
+            _check(lib().rt_accumulate_plane_device(self._h, C.byref(p), ptr(value), ptr(position4), ptr(normal4), ptr(prim), ptr(prev),
+                                                    ptr(next), ptr(out_mean), ptr(out_variance), C.c_void_p(raw)))
+        else:
+            _check(lib().rt_accumulate_plane_moving_device(self._h, C.byref(p), ptr(value), ptr(position4), ptr(normal4), ptr(prim),
+                                                           ptr(reproj_position4), ptr(reproj_normal4), ptr(prev), ptr(next),
+                                                           ptr(out_mean), ptr(out_variance), C.c_void_p(raw)))
         return next, out_mean, out_variance
 
     def accumulate_stats(self):
@@ -1106,10 +1237,14 @@ class RayTracer:
         return self._stats("rt_debug_accumulate_stats", ACCUMULATE_STATS_KEYS)
 
     def reset_history(self):
-        """Forget what render_accumulated_light keeps between its calls: the next one is a first frame again."""
+        """Forget what render_accumulated_light keeps between its calls: the next one is a first frame again.  A snapshot
+        that a moving=True call left is released with it."""
         self._history = None
+        if self._moving:
+            self._moving = False
+            self.motion_release()
 
-    def render_accumulated_light(self, rot, cam, light, focal, sample=0, filter=False, want_parts=False, **params):
+    def render_accumulated_light(self, rot, cam, light, focal, sample=0, filter=False, want_parts=False, moving=False, **params):
         """render_filtered_light's direct light with its shadow term accumulated over the calls of a sequence, on the device:
         an AOV pass (position, normal, prim of AA sample `sample`), a shade call with counts whose seeds are (pixel id +
         frame index * rows * width) mod 2^24, so that every frame of a sequence draws another jitter stream, the visibility
@@ -1117,7 +1252,10 @@ class RayTracer:
         call (two history tensors alternate; params: normal_min_dot, plane_eps, max_history), and term * V_mean -> torch
         float32 [rows, W], 0 where the pixel sees nothing.  filter=True runs the a-trous filter (its defaults) over V_mean
         first.  want_parts: also (term, V, V_mean, variance, count), V_mean as accumulated (unfiltered).  reset_history() starts a new sequence.  Runs on torch's
-        current stream; does not synchronise.  The same refusals as render_filtered_light."""
+        current stream; does not synchronise.  The same refusals as render_filtered_light.
+        moving=True carries the history across triangles that a pose, a skin or an update moved between the calls: a call
+        that has history computes the motion planes of its AOV planes against the snapshot (motion_planes_device) and hands
+        them to the moving accumulate, and every call ends with motion_snapshot on the current stream, for the next one."""
         import torch
         planes, p6, hit = self._primary_hits("render_accumulated_light", rot, cam, focal, sample, bands_ok=False)
         pos, nrm, shape = planes["position"], planes["normal"], tuple(hit.shape)
@@ -1132,7 +1270,14 @@ class RayTracer:
             p, prev = accumulate_params(shape[1], shape[0], **params), None
         else:
             p, prev = accumulate_params(shape[1], shape[0], view[0], view[1], view[2], aa_x=self.cfg.aa_x, **params), hist[cur]
-        nxt, vis_m, var = self.accumulate_plane_device(vis, pos, nrm, prim=planes["prim"], prev=prev, next=hist[1 - cur], params=p)
+        rpos = rnrm = None
+        if moving and prev is not None and self._moving:
+            rpos, rnrm = self.motion_planes_device(planes["prim"], pos, nrm)
+        nxt, vis_m, var = self.accumulate_plane_device(vis, pos, nrm, prim=planes["prim"], prev=prev, next=hist[1 - cur], params=p,
+                                                       reproj_position4=rpos, reproj_normal4=rnrm)
+        if moving:
+            self.motion_snapshot()
+            self._moving = True
         r, c, _ = self._args(rot, cam, cam)
         self._history = [hist, 1 - cur, (r, c, float(focal)), frame + 1]
         vis_o = self.filter_plane_device(vis_m, pos, nrm) if filter else vis_m
