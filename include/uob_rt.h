@@ -509,11 +509,66 @@ int rt_filter_plane_device(rt_ctx* ctx, const rt_filter_params* params, const vo
                            const void* d_normal4, void* d_out, void* hip_stream);
 /* Diagnostic: work counters of the context's most recent filter call (synchronises it; zeros before the first).  out[0] pixels,
  * out[1] passes, out[2] accepted taps summed over valid centres and passes (the centre included), out[3] valid pixels, out[4]
- * (valid pixel, pass) pairs that kept their value because only the centre was accepted, out[5..7] 0.                       */
+ * (valid pixel, pass) pairs that kept their value because only the centre was accepted, out[5] 0 (a count only after rt_filter_plane_variance,
+ * below), out[6..7] 0.                                                                                                    */
 int rt_debug_filter_stats(rt_ctx* ctx, uint64_t out[8]);
 /* The same filter on the host (CPU only, no context): the statement the device kernels are pinned against.  Same checks. */
 int rt_filter_plane_host(const rt_filter_params* params, const float* value, const float* position4, const float* normal4,
                          float* out);
+
+/* ---- variance-guided a-trous filter (rt_filter_variance.hip, DESIGN.md 4.8a') -------------------------------------------
+ * rt_filter_plane with the value stop of SVGF: besides the value it carries the value's variance (rt_accumulate_plane's
+ * out_variance), and a tap is also rejected when its value differs from the centre's by more than sigma_value standard
+ * deviations of the centre.  So a noisy pixel averages with its neighbours and a clean step keeps its edge, which one global
+ * value_max_diff cannot tell apart.  A pure FP32 function of its inputs like rt_filter_plane; every implementation (the
+ * device kernels, rt_filter_plane_variance_host) gives the same bits.
+ * Planes as rt_filter_plane's, and variance float32 [h][w].  The definition is exactly rt_filter_plane's, carrying a second
+ * plane Var_i with Var_0 = variance, with four differences.  All arithmetic is FP32 without contraction.
+ *   1. Threshold.  For every pass i and valid pixel p: g starts at +0; the 3 x 3 taps (dx, dy) in {-1, 0, 1}^2 at spacing 1
+ *      (not dilated by the pass) are visited with dy outer and dx inner, both ascending; k = 1/4 (centre), 1/8
+ *      (|dx| + |dy| = 1), 1/16 (corners); c = Var_i[q] if q = (x + dx, y + dy) lies inside the plane and is valid, else
+ *      Var_i[p]; g = g + k * c (one multiply, one add).  T = sigma_value * sqrtf(g) + value_eps: the correctly rounded square
+ *      root, one multiply, one add.  A negative g, or 0 * INFINITY, gives a NaN T.
+ *   2. Test 5, in addition to the tests 1 to 4 (test 4 with base.value_max_diff * 2^-i stays in force):
+ *      fabsf(V_i[q] - V_i[p]) <= T, on the same difference as test 4.  A NaN T rejects every tap but the centre; the pixel
+ *      is then kept.
+ *   3. Sums.  Beside num and den: num2 = num2 + (w * w) * Var_i[q] from +0, over the accepted taps in visiting order (w * w is
+ *      exact; the centre contributes like any accepted tap).
+ *   4. Store.  An invalid pixel, or one where only the centre was accepted (den == 9/64), keeps the bits of both V_i[p] and
+ *      Var_i[p].  Otherwise V_{i+1}[p] = num / den and Var_{i+1}[p] = num2 / (den * den) (den * den is exact: den is a
+ *      multiple of 1/256 not above 1); both divisions correctly rounded, a NaN quotient stored as the quiet NaN 0x7FC00000.
+ * The outputs are V_passes and Var_passes.
+ * What follows exactly: with value_eps = +INFINITY, a finite sigma_value and a variance plane of finite non-negative values,
+ * T is +INFINITY everywhere and out_value has rt_filter_plane's bits; a region of valid pixels with value 1.0f (or 0.0f) and
+ * variance +0 keeps both at the default value_eps = 0, because test 5 accepts a difference of 0 (num == den, num2 == 0);
+ * normal_min_dot = 2 with unit normals returns both inputs bit for bit.
+ * Scope: Var is used as SVGF uses its temporally integrated variance.  With a history of one frame rt_accumulate_plane's
+ * out_variance is 0, so at value_eps = 0 the filter only averages equal values there; SVGF's spatial variance estimate for
+ * short histories is not built.                                                                                            */
+typedef struct rt_filter_variance_params {   /* 32 bytes */
+  rt_filter_params base;      /* ranges and checks of rt_filter_params, unchanged                */
+  float sigma_value;          /* >= 0 or +INFINITY, not NaN                                      */
+  float value_eps;            /* >= 0 or +INFINITY, not NaN                                      */
+} rt_filter_variance_params;
+/* base = rt_filter_params_default's; sigma_value 4 (SVGF's); value_eps 0.  Stated, not tuned on images.                     */
+void rt_filter_variance_params_default(rt_filter_variance_params* params, int32_t width, int32_t height);
+/* out_variance is nullable.  out_value may be value and out_variance may be variance (in place); any other overlap of the
+ * planes is the caller's error.  The checks are rt_filter_plane's, with the fields of base under their own names, sigma_value
+ * and value_eps under theirs, "NULL plane" for value, variance, the guides and out_value, and the 16-byte alignment of the
+ * device guides; all of them run before the context is looked at.  Ordering is the filter family's: a variance call and a
+ * plain call wait for each other (they share the scratch), nothing else waits for them but rt_destroy.  The scratch is 52
+ * bytes per pixel (the guides 32, two value planes 8, two variance planes 8, the thresholds 4), kept and grown like
+ * rt_filter_plane's; a context that only ever calls rt_filter_plane allocates its 40.  UOB_RT_FILTER_FORM=direct applies.
+ * rt_debug_filter_stats after a variance call: out[2] counts the taps that passed all five tests, and out[5] the taps that
+ * passed tests 1 to 4 and failed test 5, over valid centres and passes (0 after a plain rt_filter_plane call).               */
+int rt_filter_plane_variance(rt_ctx* ctx, const rt_filter_variance_params* params, const float* value, const float* variance,
+                             const float* position4, const float* normal4, float* out_value, float* out_variance);
+int rt_filter_plane_variance_device(rt_ctx* ctx, const rt_filter_variance_params* params, const void* d_value,
+                                    const void* d_variance, const void* d_position4, const void* d_normal4, void* d_out_value,
+                                    void* d_out_variance, void* hip_stream);
+/* The same filter on the host (CPU only, no context): the statement the device kernels are pinned against.  Same checks. */
+int rt_filter_plane_variance_host(const rt_filter_variance_params* params, const float* value, const float* variance,
+                                  const float* position4, const float* normal4, float* out_value, float* out_variance);
 
 /* ---- temporal reprojection of per-pixel planes (rt_accumulate.hip) ------------------------------------
  * Carries a per-pixel estimate from one view to the next: last view's history is gathered at the place where this view's

@@ -72,6 +72,11 @@ class RtFilterParams(C.Structure):
 RT_FILTER_MAX_PASSES = 8
 
 
+class RtFilterVarianceParams(C.Structure):
+    """rt_filter_variance_params: rt_filter_params and the variance-guided value stop of rt_filter_plane_variance (32 bytes)."""
+    _fields_ = [("base", RtFilterParams), ("sigma_value", C.c_float), ("value_eps", C.c_float)]
+
+
 class RtAccumulateParams(C.Structure):
     """rt_accumulate_params: the plane size, the previous view and the acceptance tests of rt_accumulate_plane (84 bytes)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("prev_rot", C.c_float * 12), ("prev_cam", C.c_float * 3),

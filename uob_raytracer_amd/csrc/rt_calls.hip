@@ -1,6 +1,6 @@
 // rt_calls.hip — the calls beside the frame, over the C ABI (include/uob_rt.h): ray queries (rt_trace_rays, rt_ray_query.hip),
 // shade calls (rt_shade_points, rt_shade.hip), radiance calls (rt_radiance_rays, rt_radiance.hip), AOV passes
-// (rt_render_aov, rt_aov.hip), filter calls (rt_filter_plane, rt_filter.hip), accumulate calls (rt_accumulate_plane,
+// (rt_render_aov, rt_aov.hip), filter calls (rt_filter_plane, rt_filter.hip; rt_filter_plane_variance, rt_filter_variance.hip), accumulate calls (rt_accumulate_plane,
 // rt_accumulate.hip) and motion calls with their snapshot (rt_motion_planes, rt_motion.hip).  Each family has an enqueue on the caller's stream (the *_device entry), a blocking entry for
 // host arrays that stages them through the family's device buffer, and a stats export.  What the families share is written
 // once: the steps around a call (call_prepare / reader_begin / call_end), the blocking entry (run_blocking) and the stats
@@ -257,6 +257,47 @@ static int enqueue_filter(rt_ctx* c, const rt_filter_params& p, const float* d_v
   return call_end(c, &c->filter, s);
 }
 
+// One variance-guided filter call (rt_filter_plane_variance*, rt_filter_variance.hip) of a single-device context on stream s;
+// arguments checked, d_out_var may be NULL.  A call of the filter family: the plain calls' event, counters, guides and value
+// planes, and 12 bytes per pixel of its own (two variance planes, the thresholds).
+static int enqueue_filter_variance(rt_ctx* c, const rt_filter_variance_params& vp, const float* d_value, const float* d_var,
+                                   const float4* d_pos, const float4* d_nrm, float* d_out, float* d_out_var, hipStream_t s) {
+  const rt_filter_params& p = vp.base;
+  const size_t count = (size_t)p.width * p.height;
+  const int words = filter_stats_words();
+  int rc = call_prepare(c, &c->filter, words);
+  if (rc != RT_OK) return rc;
+  rc = ensure_bytes(&c->filter_guides, count * 32);   // (a larger call than any before: hipFree waits for the call still using the old one)
+  if (rc == RT_OK) rc = ensure_bytes(&c->filter_planes, count * 8);
+  if (rc == RT_OK) rc = ensure_bytes(&c->filter_variance, count * 12);
+  if (rc != RT_OK) return rc;
+  if (c->filter.pending) HIP_TRY(hipStreamWaitEvent(s, c->filter.ev, 0));
+  HIP_TRY(hipMemsetAsync(c->filter.d_stats, 0, (size_t)words * sizeof(unsigned long long), s));
+  float4* rec = (float4*)c->filter_guides.p;
+  float* plane[2] = {(float*)c->filter_planes.p, (float*)c->filter_planes.p + count};
+  float* vplane[2] = {(float*)c->filter_variance.p, (float*)c->filter_variance.p + count};
+  float* T = (float*)c->filter_variance.p + 2 * count;
+  launch_filter_pack(d_pos, d_nrm, (long)count, p.passes, rec, c->filter.d_stats, s);
+  // no pass reads what it writes: the passes alternate between the scratch planes and the last one writes the outputs —
+  // through a scratch plane and a copy where it is also the first and that plane is filtered in place.  Without
+  // d_out_var the last pass leaves the variance in the scratch
+  const bool bounce = p.passes == 1 && d_out == d_value, vbounce = p.passes == 1 && d_out_var == d_var;
+  const float *src = d_value, *vsrc = d_var;
+  for (int i = 0; i < p.passes; ++i) {
+    const bool last = i == p.passes - 1;
+    float* dst = (last && !bounce) ? d_out : plane[i & 1];
+    float* vdst = (last && !vbounce && d_out_var) ? d_out_var : vplane[i & 1];
+    launch_filter_variance_threshold(vp, rec, vsrc, T, s);
+    launch_filter_variance_pass(vp, i, c->tune.filter_form, rec, T, src, vsrc, dst, vdst, c->filter.d_stats, s);
+    src = dst;
+    vsrc = vdst;
+  }
+  launch_filter_variance_counters(c->filter.d_stats, s);
+  if (bounce) HIP_TRY(hipMemcpyAsync(d_out, src, count * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (vbounce) HIP_TRY(hipMemcpyAsync(d_out_var, vsrc, count * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return call_end(c, &c->filter, s);
+}
+
 // ---- accumulate calls (rt_accumulate_plane / rt_accumulate_plane_device, rt_accumulate.hip) ---------------------------
 // One accumulate call of a single-device context on stream s (device planes of c->device); arguments checked.  Not a reader
 // of the scene: it waits for the accumulate call before it, whose counters it takes over, and for nothing else.
@@ -503,8 +544,42 @@ int rt_filter_plane(rt_ctx* c, const rt_filter_params* p, const float* value, co
 
 int rt_debug_filter_stats(rt_ctx* c, uint64_t out[8]) {
   const int rc = read_stats(c, &rt_ctx::filter, -1, out);
-  if (rc == RT_OK) out[5] = out[6] = out[7] = 0;
+  if (rc == RT_OK) out[6] = out[7] = 0;             // (out[5]: written by a variance call only, 0 after a plain one)
   return rc;
+}
+
+int rt_filter_plane_variance_device(rt_ctx* c, const rt_filter_variance_params* p, const void* d_value, const void* d_variance,
+                                    const void* d_position4, const void* d_normal4, void* d_out_value, void* d_out_variance,
+                                    void* hip_stream) {
+  const char* fn = "rt_filter_plane_variance_device";
+  if (!c) { set_error("%s: ctx is NULL", fn); return RT_E_INVALID; }
+  const int rc = filter_variance_check(p, d_value, d_variance, d_position4, d_normal4, d_out_value, fn);
+  if (rc != RT_OK) return rc;
+  if ((((uintptr_t)d_position4 | (uintptr_t)d_normal4) & 15) != 0) {
+    set_error("%s: d_position4 / d_normal4 is not 16-byte aligned", fn); return RT_E_INVALID;
+  }
+  DeviceGuard guard;
+  return enqueue_filter_variance(lead_ctx(c), *p, (const float*)d_value, (const float*)d_variance, (const float4*)d_position4,
+                                 (const float4*)d_normal4, (float*)d_out_value, (float*)d_out_variance, (hipStream_t)hip_stream);
+}
+
+int rt_filter_plane_variance(rt_ctx* c, const rt_filter_variance_params* p, const float* value, const float* variance,
+                             const float* position4, const float* normal4, float* out_value, float* out_variance) {
+  const char* fn = "rt_filter_plane_variance";
+  if (!c) { set_error("%s: ctx is NULL", fn); return RT_E_INVALID; }
+  const int rc = filter_variance_check(p, value, variance, position4, normal4, out_value, fn);
+  if (rc != RT_OK) return rc;
+  c = lead_ctx(c);
+  DeviceGuard guard;
+  const size_t n = (size_t)p->base.width * p->base.height;
+  // (the guides first: the kernels load them as float4, and the start of the staging buffer is aligned for that.  The device
+  // copies of the outputs are planes of their own, so an in-place call needs no bounce there)
+  IoSlot io[6] = {{(void*)position4, n * 16, true}, {(void*)normal4, n * 16, true}, {(void*)value, n * 4, true},
+                  {(void*)variance, n * 4, true},   {out_value, n * 4, false},      {out_variance, n * 4, false}};
+  return run_blocking(c, &c->filter, io, 6, [&] {
+    return enqueue_filter_variance(c, *p, (const float*)io[2].dev, (const float*)io[3].dev, (const float4*)io[0].dev,
+                                   (const float4*)io[1].dev, (float*)io[4].dev, (float*)io[5].dev, c->stream);
+  });
 }
 
 int rt_trace_rays_device(rt_ctx* c, int32_t what, const void* d_rays6, const void* d_radius_sq, int64_t nray, void* d_out_tri,

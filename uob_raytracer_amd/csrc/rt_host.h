@@ -98,6 +98,20 @@ void launch_filter_counters(unsigned long long* stats, hipStream_t stream);
 // filter_host.cpp: the ranges of rt_filter_params and the plane pointers, before anything else is looked at
 int filter_check(const rt_filter_params* p, const void* value, const void* position4, const void* normal4, const void* out,
                  const char* fn);
+// rt_filter_variance.hip: the variance-guided filter (include/uob_rt.h rt_filter_plane_variance, DESIGN.md 4.8a').  It shares
+// the tile, the guide packing and the layout of the counters (filter_stats_words) with rt_filter.hip; its tiled form stages a
+// third plane, so the largest spacing it serves is its own constant.  Per pass: the thresholds T from the variance, then the
+// pass (d_src, d_vsrc) -> (d_dst, d_vdst)
+constexpr int kFilterVarianceMaxTiledSpacing = 32;
+void launch_filter_variance_threshold(const rt_filter_variance_params& vp, const float4* d_rec, const float* d_var, float* d_T,
+                                      hipStream_t stream);
+void launch_filter_variance_pass(const rt_filter_variance_params& vp, int pass, int form, const float4* d_rec, const float* d_T,
+                                 const float* d_src, const float* d_vsrc, float* d_dst, float* d_vdst, unsigned long long* stats,
+                                 hipStream_t stream);
+void launch_filter_variance_counters(unsigned long long* stats, hipStream_t stream);
+// filter_variance_host.cpp: the ranges of rt_filter_variance_params and the plane pointers, before anything else is looked at
+int filter_variance_check(const rt_filter_variance_params* p, const void* value, const void* variance, const void* position4,
+                          const void* normal4, const void* out_value, const char* fn);
 // rt_accumulate.hip: the temporal reprojection of per-pixel planes (include/uob_rt.h rt_accumulate_plane): one
 // launch over the plane in the filter's tiles (kFilterTX x kFilterTY adjacent pixels) and one that sums the counters
 // d_rpos / d_rnrm: the reprojection planes of rt_accumulate_plane_moving, both or neither (then the launch is the plain entry's)
@@ -333,8 +347,10 @@ struct rt_ctx {
   // Filter calls (rt_filter.hip): they read no scene data and none of the buffers above, so they wait only for the filter
   // call before them (they share the scratch) and nothing but the next filter call and the destructor waits for them.
   // filter_guides: the packed guide records, 32 bytes per pixel; filter_planes: the two planes the passes alternate between
+  // filter_variance: what a variance call (rt_filter_variance.hip) needs beyond that, 12 bytes per pixel: the two variance
+  // planes and the thresholds; a context that only makes plain calls never allocates it
   uobrt::SideCall filter;
-  uobrt::DevBuffer filter_guides, filter_planes;
+  uobrt::DevBuffer filter_guides, filter_planes, filter_variance;
   // Accumulate calls (rt_accumulate.hip): like the filter calls they read no scene data, wait only for the accumulate call
   // before them (they share the counters and the staging) and are waited for by the next one and the destructor.  They
   // need no scratch: the history buffers are the caller's

@@ -38,6 +38,8 @@ EXPORTS = (
     "rt_scene_skin", "rt_set_skin", "rt_pose_skin", "rt_pose_skin_device", "rt_debug_skin_info",
     "rt_debug_live_device_objects",
     "rt_filter_params_default", "rt_filter_plane", "rt_filter_plane_device", "rt_debug_filter_stats", "rt_filter_plane_host",
+    "rt_filter_variance_params_default", "rt_filter_plane_variance", "rt_filter_plane_variance_device",
+    "rt_filter_plane_variance_host",
     "rt_accumulate_params_default", "rt_accumulate_plane", "rt_accumulate_plane_device", "rt_debug_accumulate_stats",
     "rt_accumulate_plane_host",
     "rt_motion_snapshot", "rt_motion_release", "rt_debug_motion_info", "rt_motion_planes", "rt_motion_planes_device",
@@ -62,6 +64,8 @@ RADIANCE_STATS_KEYS = ("rays", "bounce_rays", "shaded_points", "sample_rays", "c
 
 # rt_debug_filter_stats slots
 FILTER_STATS_KEYS = ("pixels", "passes", "accepted_taps", "valid_pixels", "kept", "reserved5", "reserved6", "reserved7")
+# the same slots after a variance-guided call (rt_filter_plane_variance): slot 5 counts the taps that its value stop alone rejected
+FILTER_VARIANCE_STATS_KEYS = FILTER_STATS_KEYS[:5] + ("variance_stopped",) + FILTER_STATS_KEYS[6:]
 
 # rt_debug_accumulate_stats slots
 ACCUMULATE_STATS_KEYS = ("pixels", "valid_pixels", "found_history", "accepted_taps", "no_candidate", "reserved5", "reserved6",
@@ -153,6 +157,12 @@ def lib():
         L.rt_filter_plane_device.argtypes = [vp, C.POINTER(abi.RtFilterParams), vp, vp, vp, vp, vp]
         L.rt_debug_filter_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_filter_plane_host.argtypes = [C.POINTER(abi.RtFilterParams), fp, fp, fp, fp]
+        fvp = C.POINTER(abi.RtFilterVarianceParams)
+        L.rt_filter_variance_params_default.argtypes = [fvp, C.c_int32, C.c_int32]
+        L.rt_filter_variance_params_default.restype = None
+        L.rt_filter_plane_variance.argtypes = [vp, fvp, fp, fp, fp, fp, fp, fp]
+        L.rt_filter_plane_variance_device.argtypes = [vp, fvp, vp, vp, vp, vp, vp, vp, vp]
+        L.rt_filter_plane_variance_host.argtypes = [fvp, fp, fp, fp, fp, fp, fp]
         ap, ip = C.POINTER(abi.RtAccumulateParams), C.POINTER(C.c_int32)
         L.rt_accumulate_params_default.argtypes = [ap, C.c_int32, C.c_int32]
         L.rt_accumulate_params_default.restype = None
@@ -366,6 +376,53 @@ def filter_plane_host(value, position4, normal4, out=None, **params):
     p = filter_params(w, h, **params)
     _check(lib().rt_filter_plane_host(C.byref(p), _fp(v), _fp(pos), _fp(nrm), _fp(out)))
     return out
+
+
+def filter_variance_params(width, height, sigma_value=None, value_eps=None, **base):
+    """rt_filter_variance_params of a width x height plane: rt_filter_variance_params_default's values (rt_filter_params'
+    defaults, sigma_value 4, value_eps 0) unless given.  base: passes, normal_min_dot, plane_eps, value_max_diff."""
+    p = abi.RtFilterVarianceParams()
+    lib().rt_filter_variance_params_default(C.byref(p), int(width), int(height))
+    for key, v in base.items():
+        if key not in ("passes", "normal_min_dot", "plane_eps", "value_max_diff"):
+            raise TypeError("filter_variance_params: unknown parameter %r" % key)
+        if v is not None:
+            setattr(p.base, key, v)
+    for key, v in (("sigma_value", sigma_value), ("value_eps", value_eps)):
+        if v is not None:
+            setattr(p, key, v)
+    return p
+
+
+def _filter_variance_host_planes(value, variance, position4, normal4, out, out_variance, want_variance):
+    """The numpy planes of a blocking variance-guided filter call: _filter_host_planes' for the value, and the same rules for
+    variance / out_variance (None: a fresh plane when wanted, else not computed; `variance` itself: in place)."""
+    h, w, v, pos, nrm, out = _filter_host_planes(value, position4, normal4, out)
+    if not isinstance(variance, np.ndarray) or variance.shape != (h, w):
+        raise ValueError("variance must be a numpy array of shape [%d, %d]" % (h, w))
+    var = np.ascontiguousarray(variance, np.float32)
+    if out_variance is variance:
+        if not (variance.dtype == np.float32 and variance.flags.c_contiguous and variance.flags.writeable):
+            raise ValueError("in place, variance must be a writeable C-contiguous float32 array")
+        out_variance = var
+    elif out_variance is None:
+        out_variance = np.empty((h, w), np.float32) if want_variance else None
+    elif (not isinstance(out_variance, np.ndarray) or out_variance.dtype != np.float32 or out_variance.shape != (h, w)
+          or not out_variance.flags.c_contiguous):
+        raise ValueError("out_variance must be a C-contiguous float32 array of shape (%d, %d)" % (h, w))
+    return h, w, v, var, pos, nrm, out, out_variance
+
+
+def filter_plane_variance_host(value, variance, position4, normal4, out=None, out_variance=None, want_variance=True, **params):
+    """The variance-guided a-trous filter on the host (rt_filter_plane_variance_host; needs no device): value, variance
+    float32 [h, w], position4 / normal4 float32 [h, w, 4] -> (value, variance) float32 [h, w], the variance None with
+    want_variance=False and no out_variance.  params: filter_variance_params'.  out=value / out_variance=variance filter in
+    place."""
+    h, w, v, var, pos, nrm, out, ovar = _filter_variance_host_planes(value, variance, position4, normal4, out, out_variance,
+                                                                      want_variance)
+    p = filter_variance_params(w, h, **params)
+    _check(lib().rt_filter_plane_variance_host(C.byref(p), _fp(v), _fp(var), _fp(pos), _fp(nrm), _fp(out), _fp_or_none(ovar)))
+    return out, ovar
 
 
 def accumulate_params(width, height, prev_rot=None, prev_cam=None, prev_focal=None, aa_x=1, **overrides):
@@ -1114,6 +1171,41 @@ class RayTracer:
         """Work counters of the context's most recent filter call (rt_debug_filter_stats): dict of FILTER_STATS_KEYS."""
         return self._stats("rt_debug_filter_stats", FILTER_STATS_KEYS)
 
+    def filter_plane_variance(self, value, variance, position4, normal4, out=None, out_variance=None, want_variance=True, **params):
+        """The variance-guided a-trous filter on the device (rt_filter_plane_variance), blocking: numpy planes as
+        runtime.filter_plane_variance_host takes them, and the same bits -> (value, variance)."""
+        h, w, v, var, pos, nrm, out, ovar = _filter_variance_host_planes(value, variance, position4, normal4, out, out_variance,
+                                                                          want_variance)
+        p = filter_variance_params(w, h, **params)
+        _check(lib().rt_filter_plane_variance(self._h, C.byref(p), _fp(v), _fp(var), _fp(pos), _fp(nrm), _fp(out), _fp_or_none(ovar)))
+        return out, ovar
+
+    def filter_plane_variance_device(self, value, variance, position4, normal4, out=None, out_variance=None, want_variance=True,
+                                     stream=None, **params):
+        """Enqueue rt_filter_plane_variance_device on torch tensors of the context's device, without synchronising.  value,
+        variance: float32 [h, w]; position4, normal4: float32 [h, w, 4] (the AOV planes); out, out_variance: float32 [h, w],
+        allocated when None (the variance only when wanted), `value` / `variance` themselves for in-place use.  stream: a
+        torch stream or a raw hipStream_t (default: torch's current stream).  Returns (out, out_variance), None for a variance
+        that was not asked for."""
+        import torch
+        dev = self._torch_device()
+        h, w = _guide_tensors(value, position4, normal4, dev)
+        _need("variance", variance, torch.float32, (h, w), dev)
+        out = _out("out", out, torch.float32, (h, w), dev)
+        if out_variance is not None or want_variance:
+            out_variance = _out("out_variance", out_variance, torch.float32, (h, w), dev)
+        p = filter_variance_params(w, h, **params)
+        raw = self._raw_stream(stream, dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        _check(lib().rt_filter_plane_variance_device(self._h, C.byref(p), ptr(value), ptr(variance), ptr(position4), ptr(normal4),
+                                                     ptr(out), ptr(out_variance), C.c_void_p(raw)))
+        return out, out_variance
+
+    def filter_variance_stats(self):
+        """Work counters of the context's most recent filter call as a variance-guided call names them
+        (rt_debug_filter_stats): dict of FILTER_VARIANCE_STATS_KEYS."""
+        return self._stats("rt_debug_filter_stats", FILTER_VARIANCE_STATS_KEYS)
+
     def render_filtered_light(self, rot, cam, light, focal, sample=0, want_parts=False, **params):
         """The direct light of every pixel's primary hit with its shadow term reconstructed by the a-trous filter, on the
         device: an AOV pass (position, normal, prim of AA sample `sample`), a shade call with counts seeded like the frame,
@@ -1251,12 +1343,17 @@ class RayTracer:
         V = counts / shadow_samples, an accumulate call against the history and the view the object kept from its previous
         call (two history tensors alternate; params: normal_min_dot, plane_eps, max_history), and term * V_mean -> torch
         float32 [rows, W], 0 where the pixel sees nothing.  filter=True runs the a-trous filter (its defaults) over V_mean
-        first.  want_parts: also (term, V, V_mean, variance, count), V_mean as accumulated (unfiltered).  reset_history() starts a new sequence.  Runs on torch's
+        first; filter="variance" runs the variance-guided filter (its defaults) over V_mean and the accumulate's variance.
+        want_parts: also (term, V, V_mean, variance, count), V_mean as accumulated (unfiltered), and with filter="variance" the
+        filtered variance as a sixth part; sigma_value and value_eps among params are then the filter's.  reset_history() starts a new sequence.  Runs on torch's
         current stream; does not synchronise.  The same refusals as render_filtered_light.
         moving=True carries the history across triangles that a pose, a skin or an update moved between the calls: a call
         that has history computes the motion planes of its AOV planes against the snapshot (motion_planes_device) and hands
         them to the moving accumulate, and every call ends with motion_snapshot on the current stream, for the next one."""
         import torch
+        if isinstance(filter, str) and filter != "variance":
+            raise ValueError("filter must be False, True or \"variance\"")
+        stop = {k: params.pop(k) for k in ("sigma_value", "value_eps") if filter == "variance" and k in params}
         planes, p6, hit = self._primary_hits("render_accumulated_light", rot, cam, focal, sample, bands_ok=False)
         pos, nrm, shape = planes["position"], planes["normal"], tuple(hit.shape)
         if self._history is None:
@@ -1280,9 +1377,16 @@ class RayTracer:
             self._moving = True
         r, c, _ = self._args(rot, cam, cam)
         self._history = [hist, 1 - cur, (r, c, float(focal)), frame + 1]
-        vis_o = self.filter_plane_device(vis_m, pos, nrm) if filter else vis_m
+        var_f = None
+        if filter == "variance":
+            vis_o, var_f = self.filter_plane_variance_device(vis_m, var, pos, nrm, **stop)
+        else:
+            vis_o = self.filter_plane_device(vis_m, pos, nrm) if filter else vis_m
         out = term * torch.where(hit, vis_o, zero)
-        return (out, term, vis, vis_m, var, nxt[..., abi.HISTORY_COUNT].clone()) if want_parts else out
+        if not want_parts:
+            return out
+        parts = (out, term, vis, vis_m, var, nxt[..., abi.HISTORY_COUNT].clone())
+        return parts + (var_f,) if var_f is not None else parts
 
     def shade_stats(self):
         """Work counters of the context's most recent shade call (rt_debug_shade_stats): dict of SHADE_STATS_KEYS."""
